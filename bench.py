@@ -23,7 +23,15 @@ P_HOT thresholds (every compressor branch fires: the envelope solve's worst case
 measured here).
 
 Timing: W warm-up steps, then K steps timed with no instrumentation, bracketed
-by a barrier + device sync on both sides (max over ranks).  A separate pass with
+by a barrier + device sync on both sides (max over ranks).  A plain run stops
+there: it prints the line with the metric, ms_per_step, the configuration and the
+whole chain's roofline fraction.  `--dump-outputs DIR` writes, after the timed
+steps, the f32 output buffers as the last timed step left them to DIR/out<t>.npy
+(rank<r>_out<t>.npy with N > 1); the inputs are seeded, so two builds run with the
+same arguments dump comparable arrays (a buffer over its share of 64 MB is
+written as a fixed seeded sample of its frames).
+
+Everything below runs only with `--full`.  A separate pass with
 HIP events around every launch on the library's streams gives per-kernel device
 times.  roofline: the chain's algorithmic bytes (16 B per stereo frame: f32 L,R
 in + f32 L,R out) over ms_per_step is the headline; the dominant
@@ -36,7 +44,8 @@ reference's numpy/scipy stages + pydub's per-frame Python compressor loop) on
 whole chunks, extrapolated, on 1 core and on the box's cores; it runs before
 anything touches the GPU (its worker processes are forked).
 
-Run:  python bench.py [--workload C2|C3|C4|C5] [--gpus N] [--steps K] [--warmup W]
+Run:  python bench.py [--workload C2|C3|C4|C5] [--gpus N] [--steps K] [--warmup W] [--full]
+      [--dump-outputs DIR]
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ... (each rank
 reads RANK / LOCAL_RANK / WORLD_SIZE; --gpus must equal WORLD_SIZE), or `python bench.py
 --gpus N` alone: that process becomes the launcher (launch_ranks) and starts the N ranks itself.
@@ -139,6 +148,13 @@ def parse(argv=None):
     ap.add_argument("--cpu-baseline-from", default=None, help=argparse.SUPPRESS)  # launcher -> rank 0
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the CPU baseline leg, the per-kernel "
+                         "event-timed pass and the roofline / VALU-floor fields it feeds")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step left in every output buffer as "
+                         "DIR/<name>.npy (float32; a fixed seeded sample of frames where a buffer is larger than "
+                         "its share of 64 MB)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="C2")
     ap.add_argument("--params", choices=sorted(PARAMS), default=None,
                     help="settings (default: the workload's own: eqlufs for C1, else full)")
@@ -153,6 +169,8 @@ def parse(argv=None):
                     help="tuning experiments only: set engine.NAME (COMP_WARMUP, COMP_SUPER_FRAMES) or "
                          "design.DEFAULT_TILE before the jobs are planned")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.params is None:
         args.params = WORKLOADS[args.workload].get("params", "full")
     for kv in args.tune:
@@ -301,6 +319,35 @@ class Runner:
                 self.results = r
 
 
+DUMP_BUDGET_BYTES = 60 * 2 ** 20  # every rank's .npy files together stay under 64 MB
+DUMP_SEED = 20260
+
+
+def dump_outputs(run, out_dir):
+    """Write the rank's output buffers (what the last step left in them: the f32
+    frames a caller of the timed path receives) as <out_dir>/<name>.npy.  A buffer
+    larger than its share of the budget is written as a sample of its frames: row
+    indices drawn once from a seeded generator (seed, frame count and sample size
+    fix them, so two builds dump the same frames), in ascending order."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch = run.torch
+    bufs = [run.out] if run.kind == "C4" else run.outs
+    prefix = f"rank{run.rank}_" if run.world > 1 else ""
+    share = DUMP_BUDGET_BYTES // (len(bufs) * run.world)
+    written = {}
+    for t, buf in enumerate(bufs):
+        n, row_bytes = buf.shape[0], buf.shape[1] * 4
+        if n * row_bytes > share:
+            k = share // row_bytes
+            idx = np.sort(np.random.default_rng(DUMP_SEED + t).integers(0, n, size=k))
+            buf = buf.index_select(0, torch.from_numpy(idx).to(buf.device))
+        a = buf.cpu().numpy().astype(np.float32, copy=False)
+        name = f"{prefix}out{t}"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = {"frames": int(a.shape[0]), "of": int(n)}
+    return written
+
+
 def valu_ceiling(prof, dom):
     """The f64-VALU ceiling beside the HBM one, from the profile's SQ pass:
     SQ_INSTS_VALU (wave64 VALU instructions per launch, chip total) over the
@@ -409,7 +456,7 @@ def launch_ranks(args, argv) -> int:
     wl, params = WORKLOADS[args.workload], PARAMS[args.params]
     child_argv = list(argv)
     tmp = tempfile.mkdtemp(prefix="mm_bench_")
-    if not args.no_cpu_baseline and not args.dry_run:
+    if args.full and not args.no_cpu_baseline and not args.dry_run:
         cpu = cpu_baseline(args, wl, params)
         path = os.path.join(tmp, "cpu_baseline.json")
         with open(path, "w") as f:
@@ -451,6 +498,33 @@ def launch_ranks(args, argv) -> int:
     return rc
 
 
+def headline(args, wl, run, world, dt, dumped=None):
+    """The result line of the timed steps alone (rank 0): the metric, the step time,
+    the configuration and the whole chain's share of the HBM roofline."""
+    n_frames = run.frames_step
+    ms_step = dt / args.steps * 1e3
+    chain_gbs = CHAIN_BYTES_PER_FRAME * n_frames / (ms_step / 1e3) / 1e9
+    line = {
+        "metric": METRIC, "value": run.total_frames_step * args.steps / dt, "unit": "stereo frames/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
+        "higher_is_better": True, "scaling": "strong" if args.workload == "C4" else "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "config": {"workload": wl["desc"] + ", " + PARAMS_DESC[args.params],
+                   "frames_per_track": int(wl["seconds"] * wl["rate"]), "tracks_per_gpu": wl["tracks"],
+                   "rate": wl["rate"], "frames_per_rank_step": n_frames,
+                   "parallelism": (f"time-sharded x{world} (library RCCL)" if args.workload == "C4"
+                                   else f"file-sharded x{world}"),
+                   "in": "f32 interleaved (decoded PCM16)", "out": "f32 interleaved"},
+        "roofline": {"bound": "hbm", "achieved": chain_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": chain_gbs / HBM_PEAK_GBS,
+                     "algorithmic_bytes_per_step": CHAIN_BYTES_PER_FRAME * n_frames,
+                     "scope": "whole chain: 16 B per stereo frame over ms_per_step", "source_sha": source_sha()},
+    }
+    if dumped is not None:
+        line["dumped_outputs"] = dumped
+    return line
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse(argv)
@@ -486,7 +560,7 @@ def main(argv=None):
     if rank == 0 and args.cpu_baseline_from:
         with open(args.cpu_baseline_from) as f:
             cpu = json.load(f)  # measured by the launcher before it started the ranks
-    elif rank == 0 and not args.no_cpu_baseline:
+    elif rank == 0 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, wl, params)
 
     import torch
@@ -520,6 +594,16 @@ def main(argv=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
+    dumped = dump_outputs(run, args.dump_outputs) if args.dump_outputs else None
+    line = headline(args, wl, run, world, dt, dumped) if rank == 0 else None
+    if not args.full:  # the plain run ends here: set-up, warm-up, the timed steps, the line
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     # ---- profiling pass: HIP events around every launch
     run.ctx.timing(True)
     P = max(1, args.profile_steps)
@@ -537,8 +621,7 @@ def main(argv=None):
 
     if rank == 0:
         from mastering_amd import native
-        ms_step = dt / args.steps * 1e3
-        value = run.total_frames_step * args.steps / dt
+        ms_step = line["ms_per_step"]
         per = {k: (ms / P, n / P) for k, (ms, n) in stats.items()}  # per step: ms, launches
         dom = max(per, key=lambda k: per[k][0])
         dom_ms, launches = per[dom]
@@ -560,9 +643,8 @@ def main(argv=None):
         # its launches per step (a kernel launched once per step: every frame)
         bpl = CHAIN_BYTES_PER_FRAME * n_frames / max(launches, 1)
         k_achieved = bpl / avg_s / 1e9
-        chain_gbs = CHAIN_BYTES_PER_FRAME * n_frames / (ms_step / 1e3) / 1e9
         # PMC traffic and SQ shares, only from a profile of these exact sources
-        sha = source_sha()
+        sha = line["roofline"]["source_sha"]
         default_params = WORKLOADS[args.workload].get("params", "full")
         tag = args.profile_tag or f"{PROFILE_ROUND}_{args.workload}" + ("" if args.params == default_params else args.params)
         prof, prof_path = profile_summary(tag)
@@ -585,42 +667,29 @@ def main(argv=None):
             vfloor = {}
         vfloor["needed"] = needed_floor({k: v[0] for k, v in per.items()}, n_frames, active, walked, ms_step)
         vfloor["needed_floor_ms"] = vfloor["needed"]["needed_floor_ms"]
-        line = {
-            "metric": METRIC, "value": value, "unit": "stereo frames/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True,
-            "scaling": "strong" if args.workload == "C4" else "weak", "vs_baseline": None, "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": wl["desc"] + ", " + PARAMS_DESC[args.params],
-                       "frames_per_track": int(wl["seconds"] * wl["rate"]), "tracks_per_gpu": wl["tracks"],
-                       "rate": wl["rate"], "frames_per_rank_step": n_frames,
-                       "parallelism": (f"time-sharded x{world} (library RCCL)" if args.workload == "C4"
-                                       else f"file-sharded x{world}"),
-                       "in": "f32 interleaved (decoded PCM16)", "out": "f32 interleaved"},
-            "roofline": {"bound": "hbm", "limiter": limiter, "achieved": chain_gbs, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": chain_gbs / HBM_PEAK_GBS, "traffic": traffic,
-                         "algorithmic_bytes_per_step": CHAIN_BYTES_PER_FRAME * n_frames,
-                         "scope": "whole chain: 16 B per stereo frame over ms_per_step",
-                         "profile": prof_note, "source_sha": sha,
-                         "dominant_kernel": {"name": dom, "achieved": k_achieved,
-                                             "frac": k_achieved / HBM_PEAK_GBS,
-                                             "algorithmic_bytes_per_launch": bpl,
-                                             "scope": "16 B per stereo frame (SURVEY §8(d)) x frames per launch "
-                                                      "(the step's frames / launches per step), over the "
-                                                      "kernel's event-timed average launch",
-                                             "intermediate_bytes_per_launch": ibl,
-                                             "intermediate_frac": (ibl / avg_s / 1e9 / HBM_PEAK_GBS
-                                                                   if ibl is not None else None),
-                                             "avg_launch_ms": avg_s * 1e3,
-                                             "launches_per_step": launches, "traffic": dom_traffic},
-                         "valu_ceiling": valu, "valu": vfloor},
-            "chain": {"device_ms_per_step": sum(v[0] for v in per.values()),
-                      "comp_iters": iters, "comp_active_frames": active, "comp_rewalked_frames": walked, "comp_jumped_frames": jumped,
-                      "kernels_ms_per_step": {k: round(v[0], 4) for k, v in per.items()},
-                      # launches per step (library kernels; comp_fix counts every queued sweep,
-                      # quiet ones included; runtime copies / fills are not library launches)
-                      "launches_per_step": round(sum(v[1] for v in per.values()), 2),
-                      "kernel_launches_per_step": {k: round(v[1], 2) for k, v in per.items()}},
-        }
+        line["roofline"].update({
+            "limiter": limiter, "traffic": traffic, "profile": prof_note,
+            "dominant_kernel": {"name": dom, "achieved": k_achieved,
+                                "frac": k_achieved / HBM_PEAK_GBS,
+                                "algorithmic_bytes_per_launch": bpl,
+                                "scope": "16 B per stereo frame (SURVEY §8(d)) x frames per launch "
+                                         "(the step's frames / launches per step), over the "
+                                         "kernel's event-timed average launch",
+                                "intermediate_bytes_per_launch": ibl,
+                                "intermediate_frac": (ibl / avg_s / 1e9 / HBM_PEAK_GBS
+                                                      if ibl is not None else None),
+                                "avg_launch_ms": avg_s * 1e3,
+                                "launches_per_step": launches, "traffic": dom_traffic},
+            "valu_ceiling": valu, "valu": vfloor})
+        line["chain"] = {
+            "device_ms_per_step": sum(v[0] for v in per.values()),
+            "comp_iters": iters, "comp_active_frames": active, "comp_rewalked_frames": walked,
+            "comp_jumped_frames": jumped,
+            "kernels_ms_per_step": {k: round(v[0], 4) for k, v in per.items()},
+            # launches per step (library kernels; comp_fix counts every queued sweep,
+            # quiet ones included; runtime copies / fills are not library launches)
+            "launches_per_step": round(sum(v[1] for v in per.values()), 2),
+            "kernel_launches_per_step": {k: round(v[1], 2) for k, v in per.items()}}
         if args.workload == "C4":
             line["chain"]["loudness"] = res[0]["loudness"] if res else None
         if cpu is not None:

@@ -21,7 +21,7 @@ mkdir -p gpurun_out gpurun_out/profiles
 bench_line() {  # tag, env-or-"-", bench args...
   local tag=$1 envs=$2; shift 2
   [ "$envs" = "-" ] && envs=""
-  env $envs timeout -k 10 300 python -u bench.py --no-cpu-baseline --steps 10 --warmup 3 --profile-steps 3 "$@" \
+  env $envs timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --steps 10 --warmup 3 --profile-steps 3 "$@" \
     > gpurun_out/it_$tag.json 2> gpurun_out/it_$tag.err || { echo "FAILED $tag"; tail -5 gpurun_out/it_$tag.err; return 1; }
   python -c "import json; d=json.load(open('gpurun_out/it_$tag.json')); k=d['chain']['kernels_ms_per_step']; print('$tag', round(d['ms_per_step'],4), 'ms', round(d['value']/1e9,2), 'G/s it', d['chain']['comp_iters'], {n: round(v,4) for n, v in sorted(k.items(), key=lambda kv: -kv[1])[:12]})"
 }
@@ -80,7 +80,7 @@ mode_measure() {  # measure <round> [notest] [workloads...]
     case $w in C2hot) wl=C2; args="--params hot" ;; *) wl=$w; args="" ;; esac
     LABEL=${round}_$w bash tools/pmc.sh ${round}$w $wl $args || return 1
     cp profiles/${round}_${w}_* gpurun_out/profiles/
-    cb="--no-cpu-baseline"; case $w in C1|C2) cb="" ;; esac
+    cb="--full --no-cpu-baseline"; case $w in C1|C2) cb="--full" ;; esac
     timeout -k 10 400 python -u bench.py --workload $wl $args $cb > gpurun_out/bench_${round}_$w.json \
       2> gpurun_out/bench_${round}_$w.err
     local rc=$?; echo "bench $w rc=$rc"; [ $rc -ne 0 ] && { tail -20 gpurun_out/bench_${round}_$w.err; return $rc; }
@@ -93,7 +93,7 @@ mode_lines() {  # lines <round> [workloads...]: the bench lines alone (profiles 
   local w wl args cb
   for w in ${@:-C2 C2hot C3 C4 C5 C1}; do
     case $w in C2hot) wl=C2; args="--params hot" ;; *) wl=$w; args="" ;; esac
-    cb="--no-cpu-baseline"; case $w in C1|C2) cb="" ;; esac
+    cb="--full --no-cpu-baseline"; case $w in C1|C2) cb="--full" ;; esac
     timeout -k 10 400 python -u bench.py --workload $wl $args $cb > gpurun_out/bench_${round}_$w.json \
       2> gpurun_out/bench_${round}_$w.err
     local rc=$?; echo "bench $w rc=$rc"; [ $rc -ne 0 ] && { tail -20 gpurun_out/bench_${round}_$w.err; return $rc; }

@@ -13,7 +13,7 @@ mkdir -p $out
 run() {  # name, rocprofv3 args...
   local name=$1; shift
   timeout -s KILL 240 rocprofv3 "$@" --output-format csv -d $out/$name -o run -- \
-    python3 bench.py --workload $wl $extra --steps 5 --warmup 2 --profile-steps 2 --no-cpu-baseline \
+    python3 bench.py --full --workload $wl $extra --steps 5 --warmup 2 --profile-steps 2 --no-cpu-baseline \
     > $out/$name.log 2>&1
   local rc=$?
   echo "$name rc=$rc"

@@ -10,7 +10,7 @@ mkdir -p $out
 run() {
   local name=$1; shift
   timeout -s KILL 240 rocprofv3 "$@" --output-format csv -d $out/$name -o run -- \
-    python3 bench.py --workload $wl $extra --steps 3 --warmup 2 --profile-steps 1 --no-cpu-baseline \
+    python3 bench.py --full --workload $wl $extra --steps 3 --warmup 2 --profile-steps 1 --no-cpu-baseline \
     > $out/$name.log 2>&1
   local rc=$?; echo "$name rc=$rc"; [ $rc -ne 0 ] && { tail -5 $out/$name.log; exit $rc; }
   return 0
