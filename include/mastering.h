@@ -126,6 +126,12 @@ typedef struct mm_job {
        off the grid (f32 WAV) always take tanhf. */
     const float *sat_table;
     uint64_t sat_key;        /* content key of sat_table (nonzero; cached per context) */
+    /* mastering report (ABI 5): meter the delivered output at the end of the chain,
+       before any copy-out (mm_last_meters).  The loudness of the output is included
+       when the job carries loudness geometry (kweight, blocks, segments), whether or
+       not lufs_on is set.  0: the chain queues exactly what it queued before. */
+    int32_t meter_on;
+    int32_t _pad;
 } mm_job;
 
 typedef struct mm_result {
@@ -138,6 +144,27 @@ typedef struct mm_result {
     int64_t comp_walked;     /* frames re-walked by the fix-up sweeps            */
     int64_t comp_jumped;     /* frames the sweeps crossed by exact release jumps */
 } mm_result;
+
+/* What was delivered (no reference counterpart: the reference never measures its
+ * output).  Peaks are exact integers: with C = H * 8192 the taps of ITU-R BS.1770-4
+ * Annex 2 (order 48, 4 phases x 12 taps, all multiples of 2^-13; the -12 dB
+ * attenuate / restore pair of the standard is fixed-point headroom and is omitted)
+ * and s = 0 outside [0, frames), the oversampled signal of a channel is
+ *   Y[m][p] = sum_{k<12} C[p][k] * s[m-k],  m in [0, frames + 11), p in 0..3
+ * (the full convolution: the 11-frame tail belongs to it), exact in int32. */
+typedef struct mm_meter {
+    int64_t frames;
+    int32_t channels;
+    int32_t _pad;
+    int32_t sample_peak[2];     /* max |s|, 0..32768                                */
+    int32_t true_peak_q28[2];   /* max |Y|; linear true peak = this / 2^28          */
+    int64_t true_peak_frame[2]; /* smallest m at which it occurs (may be >= frames) */
+    int64_t clipped[2];         /* samples with |s| >= 32767                        */
+    int64_t overs[2];           /* m with max_p |Y[m][p]| > 2^28 (above 0 dBFS)     */
+    double loudness;            /* pyloudnorm integrated loudness of the channel mean of
+                                   s / 32768 as f32 (AME:213-218 applied to the output);
+                                   NaN when not requested or shorter than 0.4 s      */
+} mm_meter;
 
 /* Geometry of the compressor's envelope solve for a job (mm_solve_geometry: the
    planning arithmetic stage C runs on, computed on the host without a GPU). */
@@ -166,9 +193,11 @@ int mm_sync(mm_ctx *ctx);
    path in composable steps with a world check and the applied gain returned,
    device-pointer collectives (round 5); 4 = mm_job.sat_table / sat_key,
    mm_op_saturation_table, mm_np_sum_f32, mm_check_compressor_math,
-   mm_solve_geom.col_block / rms_group_tiles (round 6).  A caller built against an older header must
+   mm_solve_geom.col_block / rms_group_tiles (round 6); 5 = mm_job.meter_on, mm_meter and
+   the metering entry points (mm_meter_device, mm_meter_pcm, mm_last_meters,
+   mm_op_true_peak, mm_true_peak_host, mm_meter_span).  A caller built against an older header must
    refuse a library whose version differs from its own MM_ABI_VERSION. */
-#define MM_ABI_VERSION 4
+#define MM_ABI_VERSION 5
 int mm_version(void);
 /* The envelope-solve geometry of a job (no context, no GPU).  MM_ERR_ARG if a
    chunk's plane would not fit 32-bit offsets (no track length below 2^31 frames
@@ -193,6 +222,29 @@ int mm_master_device(mm_ctx *ctx, const mm_job *job, const void *d_in, void *d_o
 #define MM_BATCH_STREAMS 8
 int mm_master_batch(mm_ctx *ctx, int n, const mm_job *jobs, const void *const *d_in, void *const *d_out,
                     mm_result *res);
+
+/* ---- mastering report ----------------------------------------------------- */
+/* Meter a device-resident signal, interleaved [frames][channels] of `kind`
+ * (MM_OUT_I16, or MM_OUT_F32 = the same PCM / 32768: both give the same mm_meter).
+ * loud: a job carrying the loudness geometry of this signal (frames_proc, channels,
+ * rate, kweight with tpb 256, blocks, segments), or NULL for peaks only; a signal
+ * shorter than one 0.4 s block gets loudness NaN, not an error.  The audio is never
+ * altered.  Synchronous on return. */
+int mm_meter_device(mm_ctx *ctx, const void *d_pcm, int kind, int64_t frames, int channels, const mm_job *loud,
+                    mm_meter *out);
+/* The same on a host buffer. */
+int mm_meter_pcm(mm_ctx *ctx, const void *pcm, int kind, int64_t frames, int channels, const mm_job *loud,
+                 mm_meter *out);
+/* The meters of the last mm_master / mm_master_device / mm_master_wav (1) or
+ * mm_master_batch (n, in job order; tracks whose job had meter_on == 0 report
+ * frames 0) call on this context: copies min(cap, n) of them and returns n.
+ * MM_ERR_STATE if that call did not meter. */
+int mm_last_meters(mm_ctx *ctx, int cap, mm_meter *out);
+/* The integer definition of mm_meter restated in plain C on the host (no context,
+ * no GPU; loudness stays NaN): a CPU check of what the meter kernel computes. */
+int mm_true_peak_host(const int16_t *pcm, int64_t frames, int channels, mm_meter *out);
+/* Frames of m per workgroup of the meter kernel (where its seams lie). */
+int mm_meter_span(void);
 
 /* ---- WAV files (AME:43 decode, AME:98 export) ------------------------------ */
 typedef struct mm_wav_info {
@@ -303,6 +355,10 @@ int mm_op_sosfilt(mm_ctx *ctx, int dtype, const void *in, int64_t frames, int ch
  * job: channels, frames_proc, kweight (tpb 256), loudness geometry, lufs_target.
  * out[0] = loudness (LUFS), out[1] = 10 ** ((lufs_target - L) / 20). */
 int mm_op_loudness(mm_ctx *ctx, const mm_job *job, int dtype, const void *in, double *out);
+/* Linear true peak of off-grid samples [frames][channels] (no reference counterpart):
+ * the Annex 2 FIR of mm_meter in f64, y = sum_k H[p][k] * x[m-k] accumulated for
+ * k = 0..11 in that order without contraction; out[c] = max |y| of channel c. */
+int mm_op_true_peak(mm_ctx *ctx, int dtype, const void *in, int64_t frames, int channels, double *out);
 /* The legacy engine's variants (main.py:94-192, mastering_amd/legacy.py):
  * saturation tanh(x*g)/g with g = 1 + 4*amount/100 (main.py:94-97); limiter
  * |x| > threshold -> tanh(x)*threshold (main.py:189-192); an EQ stage as the

@@ -102,6 +102,8 @@ struct mm_ctx {
     size_t rb_cap = 0;
     // batch execution (mm_master_batch): child contexts, one stream each
     std::vector<mm_ctx *> children;
+    // mastering report of the last master call (mm_last_meters; empty: it did not meter)
+    std::vector<mm_meter> meters;
     // rccl
     ncclComm_t comm = nullptr;
     int rank = 0, nranks = 1;
@@ -202,6 +204,9 @@ static void resolve_events(mm_ctx *c) {
     } while (0)
 
 static inline unsigned blocks_for(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
+
+// meter.hip: meter track `slot` of `n` of the current master call into c->meters
+static int chain_meter(mm_ctx *c, const mm_job *j, const void *d_out, int slot, int n);
 
 // ------------------------------------------------------- look-back plumbing
 // Transition tables of one filter stage (uploaded only when they change).
@@ -1360,8 +1365,10 @@ static int complete_chain(mm_ctx *c, const mm_job *j, void *d_out, mm_result *re
 }
 
 static int master_device(mm_ctx *c, const mm_job *j, const void *d_in, void *d_out, mm_result *res) {
+    c->meters.clear();
     RET(enqueue_chain(c, j, d_in, d_out));
-    return complete_chain(c, j, d_out, res);
+    RET(complete_chain(c, j, d_out, res));
+    return j->meter_on ? chain_meter(c, j, d_out, 0, 1) : MM_OK;
 }
 
 // Stage the chunk chain of a range (time-sharded ranks) to convergence.
@@ -1809,6 +1816,7 @@ int mm_master_batch(mm_ctx *c, int n, const mm_job *jobs, const void *const *d_i
     if (!c || n < 0 || (n > 0 && (!jobs || !d_in || !d_out))) return set_err(c, MM_ERR_ARG, "bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
     for (int i = 0; i < n; ++i) RET(validate(c, &jobs[i]));
+    c->meters.clear();
     std::vector<BatchUnit> units = batch_units(jobs, n);
     const int nu = (int)units.size();
     const int S = std::min(nu, MM_BATCH_STREAMS);
@@ -1870,6 +1878,9 @@ int mm_master_batch(mm_ctx *c, int n, const mm_job *jobs, const void *const *d_i
         k->stats.clear();
         k->stat_order.clear();
     }
+    bool meter = false;
+    for (int i = 0; i < n; ++i) meter = meter || jobs[i].meter_on;
+    for (int i = 0; i < n && meter; ++i) RET(chain_meter(c, &jobs[i], d_out[i], i, n));
     return MM_OK;
 }
 
@@ -2301,3 +2312,4 @@ int mm_allgather_f64(mm_ctx *c, const double *host_in, double *host_out, int64_t
 
 // per-stage operators (AME:117-227 one at a time)
 #include "ops.hip"
+#include "meter.hip"

@@ -376,6 +376,8 @@ int launch_iir_op(mm_ctx *c, int nsec, bool r32, unsigned nblk, const IirOpArgs 
     }
 }
 
+int loudness_device(mm_ctx *c, const mm_job *j, int dtype, const void *din, double *out);
+
 // cascade f over a tile-major array in place (zero initial state, one line per channel)
 int iir_in_place(mm_ctx *c, const mm_iir *f, int64_t N, int ch, int64_t G, double *tm, int round_f32,
                  const double *mix = nullptr, int mix_a_f32 = 0) {
@@ -643,6 +645,27 @@ int mm_op_loudness(mm_ctx *c, const mm_job *j, int dtype, const void *in, double
     const int64_t N = j->frames_proc;
     if (ch != 1 && ch != 2) return set_err(c, MM_ERR_ARG, "channels must be 1 or 2");
     if (N < 1 || N >= (int64_t)1 << 31) return set_err(c, MM_ERR_ARG, "frames %lld out of range", (long long)N);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t in_bytes = (size_t)N * ch * dtype_size(dtype);
+    char *din;
+    RET(get_buf(c, "op_in", in_bytes, &din));
+    HIPCHK(c, hipMemcpyAsync(din, in, in_bytes, hipMemcpyHostToDevice, c->stream));
+    return loudness_device(c, j, dtype, din, out);
+}
+
+}  // extern "C"
+
+namespace {
+
+// The device part of mm_op_loudness: din = the job's [frames_proc][channels] samples
+// of `dtype` in device memory (left unchanged); out (host) as mm_op_loudness.
+// Synchronous on return.
+int loudness_device(mm_ctx *c, const mm_job *j, int dtype, const void *din, double *out) {
+    RET(check_dtype(c, dtype));
+    const int ch = j->channels;
+    const int64_t N = j->frames_proc;
+    if (ch != 1 && ch != 2) return set_err(c, MM_ERR_ARG, "channels must be 1 or 2");
+    if (N < 1 || N >= (int64_t)1 << 31) return set_err(c, MM_ERR_ARG, "frames %lld out of range", (long long)N);
     if (j->kweight.nsec != 2 || j->kweight.tpb != LB_THREADS) return set_err(c, MM_ERR_ARG, "K-weighting tables");
     if (j->n_segs < 1 || !j->seg_bounds || !j->block_lo || !j->block_hi || j->n_blocks < 1)
         return set_err(c, MM_ERR_ARG, "missing loudness geometry");
@@ -651,33 +674,30 @@ int mm_op_loudness(mm_ctx *c, const mm_job *j, int dtype, const void *in, double
     for (int64_t s = 0; s + 1 < j->n_segs; ++s)
         if (std::min<int64_t>(j->seg_bounds[s + 1], N) - j->seg_bounds[s] < T)
             return set_err(c, MM_ERR_ARG, "loudness segment shorter than a tile");
-    HIPCHK(c, hipSetDevice(c->device));
     const int64_t G = (N + T - 1) / T;
     const size_t esz = dtype_size(dtype);
-    double *tm;
+    const void *mono = din;
     if (ch == 2) {  // mean(axis=1) on the device, then the mono line
-        char *din, *dmono;
-        RET(get_buf(c, "op_in", (size_t)N * 2 * esz, &din));
+        char *dmono;
         RET(get_buf(c, "op_mono", (size_t)N * esz, &dmono));
-        HIPCHK(c, hipMemcpyAsync(din, in, (size_t)N * 2 * esz, hipMemcpyHostToDevice, c->stream));
         PwArgs pa{};
         pa.n = N;
         pa.in = din;
         pa.out = dmono;
         if (dtype == MM_F32) RET(launch(c, "op_mono", pointwise_kernel<PW_MONO, float>, dim3(pw_blocks(N)), dim3(256), 0, pa));
         else RET(launch(c, "op_mono", pointwise_kernel<PW_MONO, double>, dim3(pw_blocks(N)), dim3(256), 0, pa));
-        RET(get_buf(c, "op_tm", (size_t)G * T, &tm));
-        const unsigned nb = blocks_for(G, OPS_TILES);
-        const size_t lds = ((size_t)OPS_TILES * (T + 1)) * sizeof(double);
-        if (dtype == MM_F32)
-            RET(launch(c, "to_tile_major", to_tile_major_kernel<float, 1>, dim3(nb), dim3(256), lds,
-                       (const float *)dmono, tm, N, G, T));
-        else
-            RET(launch(c, "to_tile_major", to_tile_major_kernel<double, 1>, dim3(nb), dim3(256), lds,
-                       (const double *)dmono, tm, N, G, T));
-    } else {
-        RET(upload_tile_major(c, dtype, in, N, 1, G, &tm, T));
+        mono = dmono;
     }
+    double *tm;
+    RET(get_buf(c, "op_tm", (size_t)G * T, &tm));
+    const unsigned nb = blocks_for(G, OPS_TILES);
+    const size_t lds = ((size_t)OPS_TILES * (T + 1)) * sizeof(double);
+    if (dtype == MM_F32)
+        RET(launch(c, "to_tile_major", to_tile_major_kernel<float, 1>, dim3(nb), dim3(256), lds, (const float *)mono, tm,
+                   N, G, T));
+    else
+        RET(launch(c, "to_tile_major", to_tile_major_kernel<double, 1>, dim3(nb), dim3(256), lds, (const double *)mono,
+                   tm, N, G, T));
     RET(iir_in_place(c, &j->kweight, N, 1, G, tm, dtype == MM_F32));
     // segment energies -> gating on the device (gate.hip)
     double *part, *seg, *gout;
@@ -718,6 +738,10 @@ int mm_op_loudness(mm_ctx *c, const mm_job *j, int dtype, const void *in, double
     resolve_events(c);
     return MM_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 // apply_multiband_compressor (AME:196-210) on int16 PCM [frames][channels]: the
 // chain's crossover + compressor + overlay stages on ONE line (the job's chunk

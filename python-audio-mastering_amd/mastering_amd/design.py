@@ -177,6 +177,16 @@ def eq_sections(rate, params):
 
 LOW_CROSSOVER, HIGH_CROSSOVER = 250, 4000  # apply_multiband_compressor defaults (AME:196)
 
+# ITU-R BS.1770-4 Annex 2 true-peak interpolator: order 48, 4 phases x 12 taps, every
+# tap a multiple of 2^-13 (written here as the integers H * 8192; phases 2 and 3 are
+# phases 1 and 0 reversed).  The -12 dB attenuate / restore pair of the standard is
+# fixed-point headroom and is omitted.  csrc/meter.hip carries the same integers.
+_TRUE_PEAK_C = ((14, 90, -161, 272, -487, 1125, 7964, -838, 390, -218, 122, -68),
+                (-239, 240, -424, 730, -1364, 3810, 6388, -1641, 832, -477, 271, -155))
+TRUE_PEAK_TAPS = np.array([_TRUE_PEAK_C[0], _TRUE_PEAK_C[1], _TRUE_PEAK_C[1][::-1], _TRUE_PEAK_C[0][::-1]],
+                          dtype=np.float64) / 8192.0
+TRUE_PEAK_TAPS.setflags(write=False)
+
 
 def crossover_sections(rate, low_hz=LOW_CROSSOVER, high_hz=HIGH_CROSSOVER):
     """AME:197-198: butter(4) LP and HP as 2 SOS sections each."""

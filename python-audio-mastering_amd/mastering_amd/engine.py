@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import ctypes
 import functools
+import math
 import os
 
 import numpy as np
@@ -50,14 +51,17 @@ class Job:
 
     def __init__(self, frames_in: int, rate: int, channels: int, params: dict, out_kind: int = native.MM_OUT_I16,
                  seg_bounds=None, check_length: bool = True, single_chunk: bool = False,
-                 crossover=(design.LOW_CROSSOVER, design.HIGH_CROSSOVER)):
+                 crossover=(design.LOW_CROSSOVER, design.HIGH_CROSSOVER), report: bool = False):
         """`seg_bounds` (time-sharded ranks, distributed.py): this range's loudness
         segment bounds relative to its first frame; the whole-track gating then
         happens on the host after the all-reduce.  `check_length=False` skips
         pyloudnorm's minimum-length check (it applies to the whole track).
         `single_chunk`: the whole input is ONE line (the per-stage operators of
         ops.py, which the reference calls on one chunk) instead of AME:48's 30 s
-        chunks; `crossover`: apply_multiband_compressor's (low, high) Hz."""
+        chunks; `crossover`: apply_multiband_compressor's (low, high) Hz.  `report`:
+        meter the delivered output at the end of the chain (mm_job.meter_on); its
+        loudness is measured too whenever the track spans one 0.4 s block, with or
+        without a LUFS target."""
         if channels not in (1, 2):
             raise ValueError("only mono and stereo are supported (AME:119,137,152)")
         params = dict(params or {})
@@ -125,8 +129,9 @@ class Job:
         j.comp_warmup = COMP_WARMUP
         j.comp_max_iters = COMP_MAX_ITERS
         j.comp_super = comp_super_frames(self.rate, self.tile)
-        # --- loudness
-        if lufs is not None:
+        j.meter_on = int(bool(report))
+        # --- loudness (with `report` alone: the geometry only, for the meter)
+        if lufs is not None or (report and self.frames_proc >= 0.4 * self.rate):
             self._fill_iir(j.kweight, design.kweight_sections(self.rate), [2],
                            self.tile // design.kweight_sub(self.tile), design.LB_THREADS)
             if seg_bounds is None:
@@ -188,11 +193,74 @@ def _info(job: "Job", res: native.MMResult) -> dict:
             "chunks": len(job.chunks), "tile": job.tile}
 
 
+def _db(x: float) -> float:
+    return 20.0 * math.log10(x) if x > 0 else -math.inf
+
+
+def report_dict(m: native.MMMeter, lufs_target=None) -> dict:
+    """An mm_meter as the report of `info["report"]`: per-channel lists of the sample
+    peak (dBFS), the BS.1770-4 true peak (dBTP) and its frame, clipped samples and
+    inter-sample overs, the raw integers they come from, and the loudness of the
+    delivered output (None when it was not measured or the track is shorter than one
+    0.4 s block).  No reference counterpart: the reference never measures its output."""
+    ch = int(m.channels)
+    sp = [int(m.sample_peak[c]) for c in range(ch)]
+    tp = [int(m.true_peak_q28[c]) for c in range(ch)]
+    loud = None if math.isnan(m.loudness) else float(m.loudness)
+    rep = {"frames": int(m.frames), "channels": ch,
+           "sample_peak": sp, "true_peak_q28": tp,
+           "sample_peak_dbfs": [_db(v / 32768.0) for v in sp],
+           "true_peak_dbtp": [_db(v / 2.0 ** 28) for v in tp],
+           "true_peak_frame": [int(m.true_peak_frame[c]) for c in range(ch)],
+           "clipped": [int(m.clipped[c]) for c in range(ch)],
+           "overs": [int(m.overs[c]) for c in range(ch)],
+           "max_true_peak_dbtp": _db(max(tp, default=0) / 2.0 ** 28),
+           "output_loudness": loud}
+    if lufs_target is not None and loud is not None:
+        rep["loudness_error"] = loud - float(lufs_target)
+    return rep
+
+
+def meters(ctx: native.Context, cap: int = native.BATCH_STREAMS) -> list:
+    """The mm_meter of every track of the context's last master call (mm_last_meters):
+    one for master_device, one per job for master_batch.  RuntimeError if that call did
+    not meter (no job had `report`)."""
+    arr = (native.MMMeter * max(cap, 1))()
+    n = ctx.check(ctx.lib.mm_last_meters(ctx.ptr, cap, arr), "mm_last_meters")
+    if n > cap:
+        return meters(ctx, n)
+    return list(arr[:n])
+
+
+def _add_report(info: dict, job: "Job", ctx: native.Context) -> dict:
+    if job.job.meter_on:
+        info["report"] = report_dict(meters(ctx, 1)[0], job.job.lufs_target if job.job.lufs_on else None)
+    return info
+
+
+def meter_pcm(pcm: np.ndarray, rate: int, loudness: bool = True, device: int = 0) -> dict:
+    """Meter an int16 (or float32 = int16 / 32768) array [N] or [N, ch] without
+    mastering it: the report of `report_dict` (mm_meter_pcm)."""
+    ch = 1 if pcm.ndim == 1 else pcm.shape[1]
+    x, in_kind = _device_input(pcm)
+    kind = native.MM_OUT_I16 if in_kind == native.MM_IN_I16 else native.MM_OUT_F32
+    job = Job(x.shape[0], rate, ch, {}, single_chunk=True, report=True) if loudness else None
+    ctx = native.context(device)
+    m = native.MMMeter()
+    ctx.check(ctx.lib.mm_meter_pcm(ctx.ptr, x.ctypes.data_as(ctypes.c_void_p), kind, x.shape[0], ch,
+                                   ctypes.byref(job.job) if job is not None else None, ctypes.byref(m)),
+              "mm_meter_pcm")
+    return report_dict(m)
+
+
 def master_pcm(pcm: np.ndarray, rate: int, params: dict, out_kind: int = native.MM_OUT_I16, device: int = 0):
     """Run the whole chain (AME:48-89) on a PCM array [N] or [N, ch] on the GPU.
-    Returns (out_pcm, info) with out_pcm int16 (or f32 = int16/32768)."""
+    Returns (out_pcm, info) with out_pcm int16 (or f32 = int16/32768).
+    params['report'] (truthy) adds info['report'] (report_dict) on the output."""
     ch = 1 if pcm.ndim == 1 else pcm.shape[1]
-    job = Job(pcm.shape[0], rate, ch, params, out_kind)
+    params = dict(params or {})
+    report = bool(params.pop("report", False))
+    job = Job(pcm.shape[0], rate, ch, params, out_kind, report=report)
     x, job.job.in_kind = _device_input(pcm)
     shape = (job.frames_proc,) if ch == 1 else (job.frames_proc, ch)
     out = np.empty(shape, np.int16 if out_kind == native.MM_OUT_I16 else np.float32)
@@ -200,7 +268,7 @@ def master_pcm(pcm: np.ndarray, rate: int, params: dict, out_kind: int = native.
     res = native.MMResult()
     ctx.check(ctx.lib.mm_master(ctx.ptr, ctypes.byref(job.job), x.ctypes.data_as(ctypes.c_void_p),
                                 out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(res)), "mm_master")
-    return out, _info(job, res)
+    return out, _add_report(_info(job, res), job, ctx)
 
 
 def wav_info(path: str, device: int = 0) -> native.MMWavInfo:
@@ -213,7 +281,8 @@ def wav_info(path: str, device: int = 0) -> native.MMWavInfo:
 
 def master_device(ctx: native.Context, job: Job, d_in: int, d_out: int, res: native.MMResult | None = None):
     """Device-resident variant (pointers from e.g. torch tensors).  With `res`
-    the loudness, gain and compressor statistics are returned in it."""
+    the loudness, gain and compressor statistics are returned in it.  A job planned
+    with `report=True` is metered: `meters(ctx)[0]` (see report_dict)."""
     ctx.check(ctx.lib.mm_master_device(ctx.ptr, ctypes.byref(job.job), ctypes.c_void_p(d_in),
                                        ctypes.c_void_p(d_out), ctypes.byref(res) if res is not None else None),
               "mm_master_device")
@@ -225,7 +294,8 @@ def master_batch(ctx: native.Context, jobs, d_ins, d_outs, with_results: bool = 
     (mm_master_batch).  Tracks with the same settings run as ONE timeline (each on
     whole chunks, every stage launched once for the batch); otherwise up to
     native.BATCH_STREAMS of them are in flight at once, each on its own stream.
-    Returns one MMResult per job (or None)."""
+    Returns one MMResult per job (or None).  Jobs planned with `report=True` are
+    metered: `meters(ctx, len(jobs))` holds one mm_meter per job, in job order."""
     n = len(jobs)
     arr = (native.MMJob * n)(*[j.job for j in jobs])
     ins = (ctypes.c_void_p * n)(*[ctypes.c_void_p(int(p)) for p in d_ins])
@@ -239,20 +309,22 @@ def process(input_path: str, output_path: str, params: dict, device: int = 0, ve
     """Master `input_path` (16-bit PCM or 32-bit float WAV) into `output_path`
     (16-bit PCM WAV, as AME:98 exports; params['output_format']='f32' writes float).
     The file streams through pinned staging into HBM and back (mm_master_wav).
+    params['report'] (truthy) adds info['report'] (report_dict) on the written samples.
     Raises ValueError for unreadable/unsupported input and RuntimeError for device
     failures, like the reference (AME:110-113)."""
     params = dict(params or {})
     fmt = params.pop("output_format", "pcm16")
+    report = bool(params.pop("report", False))
     kind = native.MM_OUT_F32 if fmt == "f32" else native.MM_OUT_I16
     wi = wav_info(input_path, device)
     if verbose:
         print(f"Loaded {input_path}: {wi.frames} frames @ {wi.rate} Hz")
-    job = Job(wi.frames, wi.rate, wi.channels, params, kind)
+    job = Job(wi.frames, wi.rate, wi.channels, params, kind, report=report)
     ctx = native.context(device)
     res = native.MMResult()
     ctx.check(ctx.lib.mm_master_wav(ctx.ptr, ctypes.byref(job.job), os.fsencode(input_path), os.fsencode(output_path),
                                     ctypes.byref(res)), "mm_master_wav")
-    info = _info(job, res)
+    info = _add_report(_info(job, res), job, ctx)
     if verbose and info["loudness"] is not None:
         print(f"Current loudness: {info['loudness']:.2f} LUFS. Applying {info['gain_db']:.2f} dB gain...")
     info["output_path"] = os.path.abspath(output_path)

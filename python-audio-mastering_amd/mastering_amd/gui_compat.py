@@ -58,9 +58,19 @@ def _status(cb):
     return cb if cb is not None else (lambda message: None)
 
 
+def report_line(report: dict) -> str:
+    """One status line for a mastering report (engine.report_dict):
+    `Output: -14.21 LUFS, true peak -0.42 dBTP`."""
+    loud = report.get("output_loudness")
+    head = f"Output: {loud:.2f} LUFS, " if loud is not None else "Output: "
+    return f"{head}true peak {report['max_true_peak_dbtp']:.2f} dBTP"
+
+
 def process_audio(settings: dict, status_callback=None, device: int = 0):
     """Master settings['input_file'] into settings['output_file'] (mastering_gui.py:192-206).
-    Reports through `status_callback`; returns the engine's info dict, or None on error."""
+    Reports through `status_callback`; returns the engine's info dict, or None on error.
+    With a truthy settings['report'] the delivered output is metered (info['report'])
+    and one extra status line (report_line) precedes the completion message."""
     cb = _status(status_callback)
     src, dst = (settings or {}).get("input_file"), (settings or {}).get("output_file")
     if not src or not dst:
@@ -72,6 +82,8 @@ def process_audio(settings: dict, status_callback=None, device: int = 0):
     except Exception as e:  # the GUI shows the message; AME:110-113 re-raises to its caller
         cb(f"Error: {e}")
         return None
+    if isinstance(info, dict) and info.get("report"):
+        cb(report_line(info["report"]))
     cb(f"Processing complete: {os.path.basename(dst)}")
     return info
 
@@ -85,7 +97,8 @@ def batch_process_audio(settings: dict, input_folder: str, output_folder: str, s
                         devices=None) -> dict:
     """Master every WAV in `input_folder` into `output_folder` (mastering_gui.py:208-222).
     `devices`: GPU ids to spread the files over (default: GPU 0).  Returns
-    {input file name: info dict or the error message}."""
+    {input file name: info dict or the error message}; with a truthy
+    settings['report'] every info dict carries its file's 'report'."""
     cb = _status(status_callback)
     try:
         files = list_audio_files(input_folder)

@@ -51,7 +51,8 @@ class MMJob(ctypes.Structure):
                 ("comp_super", ctypes.c_int32), ("in_kind", ctypes.c_int32),
                 ("n_blocks", ctypes.c_int64), ("block_lo", c_int64_p), ("block_hi", c_int64_p),
                 ("n_segs", ctypes.c_int64), ("seg_bounds", c_int64_p), ("block_scale", ctypes.c_double),
-                ("sat_table", ctypes.POINTER(ctypes.c_float)), ("sat_key", ctypes.c_uint64)]
+                ("sat_table", ctypes.POINTER(ctypes.c_float)), ("sat_key", ctypes.c_uint64),
+                ("meter_on", ctypes.c_int32), ("_pad", ctypes.c_int32)]
 
 
 class MMResult(ctypes.Structure):
@@ -68,7 +69,14 @@ class MMSolveGeom(ctypes.Structure):
                 ("col_block", ctypes.c_int32), ("rms_group_tiles", ctypes.c_int32)]
 
 
-ABI_VERSION = 4  # MM_ABI_VERSION of include/mastering.h
+class MMMeter(ctypes.Structure):
+    _fields_ = [("frames", ctypes.c_int64), ("channels", ctypes.c_int32), ("_pad", ctypes.c_int32),
+                ("sample_peak", ctypes.c_int32 * 2), ("true_peak_q28", ctypes.c_int32 * 2),
+                ("true_peak_frame", ctypes.c_int64 * 2), ("clipped", ctypes.c_int64 * 2),
+                ("overs", ctypes.c_int64 * 2), ("loudness", ctypes.c_double)]
+
+
+ABI_VERSION = 5  # MM_ABI_VERSION of include/mastering.h
 
 
 class MMWavInfo(ctypes.Structure):
@@ -88,7 +96,9 @@ EXPORTS = ("mm_create", "mm_destroy", "mm_last_error", "mm_sync", "mm_version", 
            "mm_op_pcm_to_float", "mm_op_saturation", "mm_op_saturation_table", "mm_op_stereo_width", "mm_op_quantize", "mm_op_soft_limiter",
            "mm_op_gain", "mm_op_sosfilt", "mm_op_loudness", "mm_op_multiband", "mm_master_batch",
            "mm_op_saturation_legacy", "mm_op_soft_limiter_legacy", "mm_op_sosfilt_mix", "mm_op_compress_bands",
-           "mm_solve_geometry", "mm_np_sum_f32", "mm_check_compressor_math")
+           "mm_solve_geometry", "mm_np_sum_f32", "mm_check_compressor_math",
+           "mm_meter_device", "mm_meter_pcm", "mm_last_meters", "mm_op_true_peak", "mm_true_peak_host",
+           "mm_meter_span")
 
 _lib = None
 _lock = threading.Lock()
@@ -166,6 +176,14 @@ def load():
             "mm_np_sum_f32": ([P(ctypes.c_float), ctypes.c_int64, P(ctypes.c_float)], ctypes.c_int),
             "mm_check_compressor_math": ([vp, ctypes.c_int, c_double_p, c_double_p, ctypes.c_int64, c_double_p],
                                          ctypes.c_int),
+            "mm_meter_device": ([vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, P(MMJob), P(MMMeter)],
+                                ctypes.c_int),
+            "mm_meter_pcm": ([vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, P(MMJob), P(MMMeter)],
+                             ctypes.c_int),
+            "mm_last_meters": ([vp, ctypes.c_int, P(MMMeter)], ctypes.c_int),
+            "mm_op_true_peak": ([vp, ctypes.c_int, vp, ctypes.c_int64, ctypes.c_int, c_double_p], ctypes.c_int),
+            "mm_true_peak_host": ([P(ctypes.c_int16), ctypes.c_int64, ctypes.c_int, P(MMMeter)], ctypes.c_int),
+            "mm_meter_span": ([], ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             fn = getattr(lib, name)

@@ -36,7 +36,7 @@ from .engine import Job
 
 __all__ = ["audio_segment_to_float_array", "float_array_to_audio_segment", "apply_saturation",
            "apply_stereo_width", "apply_eq_to_samples", "apply_shelf_filter", "apply_peak_filter",
-           "apply_multiband_compressor", "normalize_to_lufs", "soft_limiter", "integrated_loudness"]
+           "apply_multiband_compressor", "normalize_to_lufs", "soft_limiter", "integrated_loudness", "true_peak"]
 
 _vp = ctypes.c_void_p
 
@@ -255,4 +255,22 @@ def normalize_to_lufs(samples, sample_rate, target_lufs=-14.0, device: int = 0):
     out = np.empty(x.shape, np.float64)
     ctx = _ctx(device)
     ctx.check(ctx.lib.mm_op_gain(ctx.ptr, dt, _ptr(x), x.size, float(gain_linear), _ptr(out)), "mm_op_gain")
+    return out
+
+
+# ------------------------------------------------------------------ true peak
+def true_peak(samples, device: int = 0) -> np.ndarray:
+    """Linear true peak per channel of float32/float64 samples [N] or [N, 2]: the
+    ITU-R BS.1770-4 Annex 2 4x interpolator (design.TRUE_PEAK_TAPS) over the full
+    convolution, accumulated in float64 (mm_op_true_peak).  No reference
+    counterpart.  Samples on the int16 grid give the integer meter's value / 2^28
+    exactly; int16 PCM itself goes through engine.meter_pcm."""
+    x, dt = _float_input(samples, "true_peak")
+    if x.ndim not in (1, 2) or (x.ndim == 2 and x.shape[1] != 2):
+        raise NotImplementedError("mono [N] or stereo [N, 2] samples only")
+    ch = 2 if x.ndim == 2 else 1
+    out = np.zeros(ch)
+    ctx = _ctx(device)
+    ctx.check(ctx.lib.mm_op_true_peak(ctx.ptr, dt, _ptr(x), x.shape[0], ch, out.ctypes.data_as(native.c_double_p)),
+              "mm_op_true_peak")
     return out

@@ -6,7 +6,9 @@ An object ``gs://<bucket>/<blob>`` lives at ``<root>/<bucket>/<blob>``; ``root``
 defaults to ``$MM_BUCKET_ROOT``.  Exactly like AME:92-107, the result is written to
 ``<bucket>/processed/mastered_<basename(blob)>`` (16-bit WAV) followed by an empty
 ``.complete`` marker next to it; the marker appears only after the WAV is fully
-written (renamed into place), so a poller never sees a partial file.
+written (renamed into place), so a poller never sees a partial file.  With a truthy
+``settings["report"]`` (no reference counterpart) the mastering report of the written
+file goes to ``<output>.report.json`` before the marker.
 
 ``wsgi_app`` is the handler as a plain WSGI callable (what gunicorn serves the
 reference's Flask app as), so no web framework is needed; ``handle_push`` is the
@@ -18,6 +20,7 @@ from __future__ import annotations
 
 import base64
 import json
+import math
 import os
 
 from . import engine
@@ -49,6 +52,17 @@ def object_path(uri: str, root: str | None = None) -> tuple[str, str, str]:
     return path, bucket_dir, blob
 
 
+def _json_safe(v):
+    """Report values as strict JSON: -inf dB (digital silence) becomes null."""
+    if isinstance(v, float) and not math.isfinite(v):
+        return None
+    if isinstance(v, list):
+        return [_json_safe(x) for x in v]
+    if isinstance(v, dict):
+        return {k: _json_safe(x) for k, x in v.items()}
+    return v
+
+
 def process_audio_from_gcs(gcs_uri: str, settings: dict, root: str | None = None, device: int = 0) -> dict:
     """AME:24-113 on the local object tree: master the object, write
     ``processed/mastered_<basename>`` and its ``.complete`` marker; re-raise any
@@ -68,6 +82,10 @@ def process_audio_from_gcs(gcs_uri: str, settings: dict, root: str | None = None
             if os.path.exists(tmp):
                 os.remove(tmp)
         print(f"Exporting and uploading processed audio to {out_name}...")
+        if isinstance(info, dict) and info.get("report"):
+            with open(dst + ".report.json.part", "w") as f:
+                json.dump(_json_safe(info["report"]), f, indent=1, sort_keys=True)
+            os.replace(dst + ".report.json.part", dst + ".report.json")
         with open(dst + ".complete", "wb"):
             pass
         print(f"Completion flag created at {out_name}.complete")
