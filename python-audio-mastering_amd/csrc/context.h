@@ -1,0 +1,183 @@
+// context.h — the library's context (mm_ctx: stream, device buffers, the chain's
+// control block and cached tables) and the helpers every host file uses: errors,
+// device buffers, the timed launch.  Included by mastering.hip after the kernels.
+#pragma once
+
+namespace {
+
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+};
+
+struct PendingEvent {
+    std::string name;
+    hipEvent_t a, b;
+};
+
+struct KStat {
+    double ms = 0.0;
+    int64_t n = 0;
+};
+
+}  // namespace
+
+struct mm_ctx {
+    int device = 0;
+    int n_cus = 256;  // compute units of the device (persistent launches)
+    hipStream_t stream = nullptr;
+    char err[512] = {0};
+    std::map<std::string, DevBuf> bufs;
+    // staged job geometry (mm_stage_chunks -> mm_hop_energies / mm_finalize)
+    bool staged = false;
+    mm_job job{};
+    int64_t G = 0;
+    short2 *mix = nullptr;
+    unsigned *lb_error = nullptr;
+    // per-chain control words, zeroed by ONE memset at the chain start: the three
+    // IIR stages' ticket/status regions and the compressor's sweep flags; a
+    // region is "fresh" until its first use (repeats zero their own words)
+    unsigned *ctl_lb[3] = {nullptr, nullptr, nullptr};
+    bool ctl_fresh[3] = {false, false, false};
+    bool comp_flags_fresh = false;
+    // compressor state kept across the queued launches (stage_front -> comp_sweeps/comp_back)
+    bool comp_on = false;
+    CompArgs ca{};
+    uint32_t comp_stamp = 0;  // stamp of the last queued fix-up sweep
+    unsigned *comp_changed = nullptr;
+    char *ctl = nullptr;                // the chain's control block (setup_control)
+    size_t ctl_bytes = 0, ctl_rba = 0;  // its size and readback area
+    size_t ctl_region = 0;              // bytes of each of its look-back regions (lb_prepare)
+    // the block is zero from ctl_clean_ptr up to ctl_clean_bytes: the last chain's
+    // tail (finalize) zeroed it, so the next setup_control queues no fill
+    bool ctl_clean = false;
+    char *ctl_clean_ptr = nullptr;
+    size_t ctl_clean_bytes = 0;
+    bool tail_readback = false;         // the last queued finalize hands the readback area over
+    uint32_t *ctl_claims = nullptr;     // its zeroed claim stamps
+    int comp_iters = 0, comp_pending = 0;
+    int comp_queue = 0;  // sweeps to queue with the next solve (0: COMP_SWEEPS; then the last solve's need + 1)
+    uint64_t comp_sig = 0;  // settings and geometry of the solve comp_queue was learnt on (comp_signature)
+    // loudness on the device
+    double *gate_out = nullptr;         // [2]: L, gain
+    std::vector<int64_t> geom_cache;    // loudness geometry already on the device (upload_geometry)
+    // exact block energies (kw_blocks_kernel): per block its first frame and program
+    int64_t *kb_lo = nullptr;
+    int32_t *kb_n = nullptr, *kb_prog_of = nullptr, *kb_prog = nullptr;
+    std::vector<int64_t> kb_cache;      // block geometry the programs on the device were built for
+    int kb_nvals = 0, kb_pints = 0;     // the largest program's values and ints (kw_blocks' LDS)
+    // timing
+    bool timing = false;
+    std::vector<PendingEvent> pending;
+    std::vector<hipEvent_t> free_events;
+    // pinned double-buffered staging for the WAV file path (mm_master_wav)
+    char *pin[2] = {nullptr, nullptr};
+    hipEvent_t pin_ev[2] = {nullptr, nullptr};
+    std::map<std::string, KStat> stats;
+    std::vector<std::string> stat_order;
+    // host tables already resident on the device
+    uint64_t lut_key[3] = {0, 0, 0};  // content keys of the band tables on the device (0: none)
+    uint64_t sat_key = 0;             // content key of the exciter table on the device (0: none)
+    bool sat_codes = false;           // its correction codes are complete (no entry needs the table)
+    std::map<std::string, std::vector<double>> mats_cache;
+    // pinned block the chain's results are copied into (one sync per chain)
+    char *rb = nullptr, *rb_dev = nullptr;  // (rb_dev: its device address)
+    size_t rb_cap = 0;
+    // batch execution (mm_master_batch): child contexts, one stream each
+    std::vector<mm_ctx *> children;
+    // mastering report of the last master call (mm_last_meters; empty: it did not meter)
+    std::vector<mm_meter> meters;
+    // rccl
+    ncclComm_t comm = nullptr;
+    int rank = 0, nranks = 1;
+};
+
+static int set_err(mm_ctx *c, int code, const char *fmt, ...) {
+    if (c) {
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(c->err, sizeof(c->err), fmt, ap);
+        va_end(ap);
+    }
+    return code;
+}
+
+#define HIPCHK(ctx, expr)                                                                    \
+    do {                                                                                     \
+        hipError_t e_ = (expr);                                                              \
+        if (e_ != hipSuccess)                                                                \
+            return set_err(ctx, MM_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
+                           __FILE__, __LINE__);                                              \
+    } while (0)
+
+template <typename T>
+static int get_buf(mm_ctx *c, const char *name, size_t count, T **out) {
+    DevBuf &b = c->bufs[name];
+    size_t bytes = std::max<size_t>(count * sizeof(T), 256);
+    if (b.cap < bytes) {
+        if (b.p) HIPCHK(c, hipFree(b.p));
+        b.p = nullptr;
+        b.cap = 0;
+        HIPCHK(c, hipMalloc(&b.p, bytes));
+        b.cap = bytes;
+    }
+    *out = reinterpret_cast<T *>(b.p);
+    return MM_OK;
+}
+
+static hipEvent_t take_event(mm_ctx *c) {
+    if (!c->free_events.empty()) {
+        hipEvent_t e = c->free_events.back();
+        c->free_events.pop_back();
+        return e;
+    }
+    hipEvent_t e;
+    if (hipEventCreate(&e) != hipSuccess) return nullptr;
+    return e;
+}
+
+// Launch helper: records HIP events around the kernel on the context stream
+// when timing is enabled.
+template <typename Kern, typename... Args>
+static int launch(mm_ctx *c, const char *name, Kern k, dim3 grid, dim3 block, size_t lds, Args... args) {
+    hipEvent_t a = nullptr, b = nullptr;
+    if (c->timing) {
+        a = take_event(c);
+        b = take_event(c);
+        if (a) hipEventRecord(a, c->stream);
+    }
+    hipLaunchKernelGGL(k, grid, block, lds, c->stream, args...);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_err(c, MM_ERR_HIP, "launch %s: %s", name, hipGetErrorString(e));
+    if (c->timing && a && b) {
+        hipEventRecord(b, c->stream);
+        c->pending.push_back({name, a, b});
+    }
+    return MM_OK;
+}
+
+static void resolve_events(mm_ctx *c) {
+    for (auto &p : c->pending) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
+            auto it = c->stats.find(p.name);
+            if (it == c->stats.end()) {
+                c->stat_order.push_back(p.name);
+                it = c->stats.emplace(p.name, KStat{}).first;
+            }
+            it->second.ms += ms;
+            it->second.n += 1;
+        }
+        c->free_events.push_back(p.a);
+        c->free_events.push_back(p.b);
+    }
+    c->pending.clear();
+}
+
+#define RET(expr)                  \
+    do {                           \
+        int r_ = (expr);           \
+        if (r_ != MM_OK) return r_; \
+    } while (0)
+
+static inline unsigned blocks_for(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }

@@ -1,5 +1,8 @@
-// mastering.hip — host side of the C-ABI (include/mastering.h): device buffers,
-// the launch sequence of the chain, loudness gating, event timing and RCCL.
+// mastering.hip — host side of the C-ABI (include/mastering.h), one translation
+// unit: the launch sequence of the chain (a unit of n >= 1 tracks between two
+// syncs), loudness gating, the batch scheduler and the staged / time-sharded entry
+// points.  The context is context.h; wav.hip, comm.hip, ops.hip and meter.hip are
+// included at the end.
 #include <rccl/rccl.h>
 
 #include <algorithm>
@@ -19,191 +22,7 @@
 
 using namespace mm;
 
-namespace {
-
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-};
-
-struct PendingEvent {
-    std::string name;
-    hipEvent_t a, b;
-};
-
-struct KStat {
-    double ms = 0.0;
-    int64_t n = 0;
-};
-
-}  // namespace
-
-struct mm_ctx {
-    int device = 0;
-    int n_cus = 256;  // compute units of the device (persistent launches)
-    hipStream_t stream = nullptr;
-    char err[512] = {0};
-    std::map<std::string, DevBuf> bufs;
-    // staged job geometry (mm_stage_chunks -> mm_hop_energies / mm_finalize)
-    bool staged = false;
-    mm_job job{};
-    int64_t G = 0;
-    short2 *mix = nullptr;
-    unsigned *lb_error = nullptr;
-    // per-chain control words, zeroed by ONE memset at the chain start: the three
-    // IIR stages' ticket/status regions and the compressor's sweep flags; a
-    // region is "fresh" until its first use (repeats zero their own words)
-    unsigned *ctl_lb[3] = {nullptr, nullptr, nullptr};
-    bool ctl_fresh[3] = {false, false, false};
-    bool comp_flags_fresh = false;
-    // compressor state kept across the queued launches (stage_front -> comp_sweeps/comp_back)
-    bool comp_on = false;
-    CompArgs ca{};
-    uint32_t comp_stamp = 0;  // stamp of the last queued fix-up sweep
-    unsigned *comp_changed = nullptr;
-    char *ctl = nullptr;                // the chain's control block (setup_control)
-    size_t ctl_bytes = 0, ctl_rba = 0;  // its size and readback area
-    // the block is zero from ctl_clean_ptr up to ctl_clean_bytes: the last chain's
-    // tail (finalize) zeroed it, so the next setup_control queues no fill
-    bool ctl_clean = false;
-    char *ctl_clean_ptr = nullptr;
-    size_t ctl_clean_bytes = 0;
-    bool tail_readback = false;         // the last queued finalize hands the readback area over
-    uint32_t *ctl_claims = nullptr;     // its zeroed claim stamps
-    int comp_iters = 0, comp_pending = 0;
-    int comp_queue = 0;  // sweeps to queue with the next solve (0: COMP_SWEEPS; then the last solve's need + 1)
-    uint64_t comp_sig = 0;  // settings and geometry of the solve comp_queue was learnt on (comp_signature)
-    // loudness on the device
-    double *gate_out = nullptr;         // [2]: L, gain
-    std::vector<int64_t> geom_cache;    // loudness geometry already on the device
-    int32_t *blk_s0 = nullptr, *blk_s1 = nullptr;
-    int64_t *seg_bounds_dev = nullptr;
-    // exact block energies (kw_blocks_kernel): per block its first frame and program
-    int64_t *kb_lo = nullptr;
-    int32_t *kb_n = nullptr, *kb_prog_of = nullptr, *kb_prog = nullptr;
-    std::vector<int64_t> kb_cache;      // block geometry the programs on the device were built for
-    int kb_nvals = 0, kb_pints = 0;     // the largest program's values and ints (kw_blocks' LDS)
-    // timing
-    bool timing = false;
-    std::vector<PendingEvent> pending;
-    std::vector<hipEvent_t> free_events;
-    // pinned double-buffered staging for the WAV file path (mm_master_wav)
-    char *pin[2] = {nullptr, nullptr};
-    hipEvent_t pin_ev[2] = {nullptr, nullptr};
-    std::map<std::string, KStat> stats;
-    std::vector<std::string> stat_order;
-    // host tables already resident on the device
-    uint64_t lut_key[3] = {0, 0, 0};  // content keys of the band tables on the device (0: none)
-    uint64_t sat_key = 0;             // content key of the exciter table on the device (0: none)
-    bool sat_codes = false;           // its correction codes are complete (no entry needs the table)
-    std::map<std::string, std::vector<double>> mats_cache;
-    // pinned block the chain's results are copied into (one sync per chain)
-    char *rb = nullptr, *rb_dev = nullptr;  // (rb_dev: its device address)
-    size_t rb_cap = 0;
-    // batch execution (mm_master_batch): child contexts, one stream each
-    std::vector<mm_ctx *> children;
-    // mastering report of the last master call (mm_last_meters; empty: it did not meter)
-    std::vector<mm_meter> meters;
-    // rccl
-    ncclComm_t comm = nullptr;
-    int rank = 0, nranks = 1;
-};
-
-static int set_err(mm_ctx *c, int code, const char *fmt, ...) {
-    if (c) {
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(c->err, sizeof(c->err), fmt, ap);
-        va_end(ap);
-    }
-    return code;
-}
-
-#define HIPCHK(ctx, expr)                                                                    \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return set_err(ctx, MM_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                           __FILE__, __LINE__);                                              \
-    } while (0)
-
-#define RET_EARLY(expr)             \
-    do {                            \
-        int r_ = (expr);            \
-        if (r_ != MM_OK) return r_; \
-    } while (0)
-
-template <typename T>
-static int get_buf(mm_ctx *c, const char *name, size_t count, T **out) {
-    DevBuf &b = c->bufs[name];
-    size_t bytes = std::max<size_t>(count * sizeof(T), 256);
-    if (b.cap < bytes) {
-        if (b.p) HIPCHK(c, hipFree(b.p));
-        b.p = nullptr;
-        b.cap = 0;
-        HIPCHK(c, hipMalloc(&b.p, bytes));
-        b.cap = bytes;
-    }
-    *out = reinterpret_cast<T *>(b.p);
-    return MM_OK;
-}
-
-static hipEvent_t take_event(mm_ctx *c) {
-    if (!c->free_events.empty()) {
-        hipEvent_t e = c->free_events.back();
-        c->free_events.pop_back();
-        return e;
-    }
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
-    return e;
-}
-
-// Launch helper: records HIP events around the kernel on the context stream
-// when timing is enabled.
-template <typename Kern, typename... Args>
-static int launch(mm_ctx *c, const char *name, Kern k, dim3 grid, dim3 block, size_t lds, Args... args) {
-    hipEvent_t a = nullptr, b = nullptr;
-    if (c->timing) {
-        a = take_event(c);
-        b = take_event(c);
-        if (a) hipEventRecord(a, c->stream);
-    }
-    hipLaunchKernelGGL(k, grid, block, lds, c->stream, args...);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_err(c, MM_ERR_HIP, "launch %s: %s", name, hipGetErrorString(e));
-    if (c->timing && a && b) {
-        hipEventRecord(b, c->stream);
-        c->pending.push_back({name, a, b});
-    }
-    return MM_OK;
-}
-
-static void resolve_events(mm_ctx *c) {
-    for (auto &p : c->pending) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
-            auto it = c->stats.find(p.name);
-            if (it == c->stats.end()) {
-                c->stat_order.push_back(p.name);
-                it = c->stats.emplace(p.name, KStat{}).first;
-            }
-            it->second.ms += ms;
-            it->second.n += 1;
-        }
-        c->free_events.push_back(p.a);
-        c->free_events.push_back(p.b);
-    }
-    c->pending.clear();
-}
-
-#define RET(expr)                  \
-    do {                           \
-        int r_ = (expr);           \
-        if (r_ != MM_OK) return r_; \
-    } while (0)
-
-static inline unsigned blocks_for(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
+#include "context.h"
 
 // meter.hip: meter track `slot` of `n` of the current master call into c->meters
 static int chain_meter(mm_ctx *c, const mm_job *j, const void *d_out, int slot, int n);
@@ -289,10 +108,11 @@ static int upload_zw(mm_ctx *c, const char *name, const mm_iir &f, int T, const 
 static size_t lb_flag_bytes(int64_t nblk) { return ((16 + (size_t)nblk * 4) + 15) / 16 * 16; }
 
 // region: the chain's pre-zeroed control region of this stage (0 eq, 1 crossover,
-// 2 K-weighting), used once; otherwise (or on a repeat) a private memset.
+// 2 K-weighting), used once and only by a launch it was sized for; otherwise (or
+// on a repeat) a private memset.
 static int lb_prepare(mm_ctx *c, int64_t nblk, int ch, LbArgs &lb, int region = -1) {
     char *flags;
-    if (region >= 0 && c->ctl_fresh[region]) {
+    if (region >= 0 && c->ctl_fresh[region] && lb_flag_bytes(nblk) <= c->ctl_region) {
         flags = reinterpret_cast<char *>(c->ctl_lb[region]);
         c->ctl_fresh[region] = false;
     } else {
@@ -452,8 +272,7 @@ static int attach_tail(mm_ctx *c, FinArgs &fa) {
 
 // Queue the D2H copy of everything the host checks after the chain (no sync): the
 // readback area of the control block, in ONE copy.
-static int queue_readback(mm_ctx *c, bool lufs) {
-    (void)lufs;
+static int queue_readback(mm_ctx *c) {
     const int64_t nch = comp_chunks(c);
     RET(ensure_rb(c, rb_bytes(nch) + 64));
     HIPCHK(c, hipMemcpyAsync(c->rb, c->ctl, rb_bytes(nch), hipMemcpyDeviceToHost, c->stream));
@@ -549,7 +368,7 @@ static void rb_finish(mm_ctx *c, const RbKeep &k) {
 }
 
 static int chain_check(mm_ctx *c, bool *converged) {
-    RET(queue_readback(c, false));
+    RET(queue_readback(c));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return evaluate_chain(c, converged);
 }
@@ -598,6 +417,7 @@ static int setup_control(mm_ctx *c, unsigned nblk, int64_t nch, int64_t claims) 
     c->ctl = ctl;
     c->ctl_bytes = bytes;
     c->ctl_rba = rba;
+    c->ctl_region = region;
     c->lb_error = reinterpret_cast<unsigned *>(ctl + RB_ERR);
     c->comp_changed = reinterpret_cast<unsigned *>(ctl + RB_FLAGS);
     c->gate_out = reinterpret_cast<double *>(ctl + RB_LG);
@@ -771,9 +591,15 @@ static int stage_compress(mm_ctx *c, const mm_job *j, short2 *const bands[3], co
     return MM_OK;
 }
 
+// Look-back blocks of the K-weighting stage over G tiles: one lane per sub-tile of
+// kweight.tile frames (design.kweight_sub).
+static unsigned kw_nblk(const mm_job *j, int64_t G) {
+    return blocks_for(std::max<int64_t>(G, 1) * (j->tile / std::max(1, j->kweight.tile)), LB_THREADS);
+}
+
 // ------------------------------------------------------------ chain A..C
-static int stage_front(mm_ctx *c, const mm_job *j, const void *d_in) {
-    RET(validate(c, j));
+// nblk_kw: the blocks of the K-weighting stage that will follow on this line (0: none)
+static int stage_front(mm_ctx *c, const mm_job *j, const void *d_in, unsigned nblk_kw) {
     const int T = j->tile, ch = j->channels, K = j->tiles_per_chunk;
     const int64_t N = j->frames_proc;
     const int64_t G = (N + T - 1) / T;
@@ -793,8 +619,6 @@ static int stage_front(mm_ctx *c, const mm_job *j, const void *d_in) {
         spc = sg.cols_per_chunk;
     }
     // (each look-back region also holds the K-weighting stage's blocks: sub-tile lanes)
-    const unsigned nblk_kw = j->lufs_on ? blocks_for(std::max<int64_t>(G, 1) * (T / std::max(1, j->kweight.tile)),
-                                                     LB_THREADS) : 0u;
     RET(setup_control(c, std::max(nblk, nblk_kw), nch, 3 * nch * spc + 3 * nch * spc / 64));  // claim stamps, column-block counts
 
     EqArgs ea{};
@@ -912,10 +736,18 @@ static int stage_front(mm_ctx *c, const mm_job *j, const void *d_in) {
 }
 
 // ------------------------------------------------------------ K-weighting
-// Loudness geometry on the device (segment bounds; per-block segment ranges),
-// uploaded only when the job's geometry changes.
-static int upload_geometry(mm_ctx *c) {
-    const mm_job *j = &c->job;
+// Loudness geometry of a line on the device: segment bounds, every gating block as a
+// segment range, and for a timeline of several tracks (n_trk > 0) each track's
+// first tile, the end of its real frames and its first gating block.
+struct LineGeom {
+    int n_trk = 0;
+    int64_t n_segs = 0, n_blocks = 0;
+    int64_t *bounds = nullptr, *trk_blk = nullptr, *trk_tile0 = nullptr, *trk_end = nullptr;
+    int32_t *s0 = nullptr, *s1 = nullptr;
+};
+
+// A single track's geometry (kept on the context, uploaded only when it changes).
+static int upload_geometry(mm_ctx *c, const mm_job *j, LineGeom *g) {
     std::vector<int64_t> key;
     key.reserve((size_t)(j->n_segs + 3 + 2 * j->n_blocks));
     key.push_back(j->n_segs);
@@ -923,9 +755,12 @@ static int upload_geometry(mm_ctx *c) {
     key.push_back(j->n_blocks);
     key.insert(key.end(), j->block_lo, j->block_lo + j->n_blocks);
     key.insert(key.end(), j->block_hi, j->block_hi + j->n_blocks);
-    RET(get_buf(c, "kw_bounds", (size_t)j->n_segs + 1, &c->seg_bounds_dev));
-    RET(get_buf(c, "gate_s0", (size_t)j->n_blocks, &c->blk_s0));
-    RET(get_buf(c, "gate_s1", (size_t)j->n_blocks, &c->blk_s1));
+    *g = LineGeom{};
+    g->n_segs = j->n_segs;
+    g->n_blocks = j->n_blocks;
+    RET(get_buf(c, "kw_bounds", (size_t)j->n_segs + 1, &g->bounds));
+    RET(get_buf(c, "gate_s0", (size_t)j->n_blocks, &g->s0));
+    RET(get_buf(c, "gate_s1", (size_t)j->n_blocks, &g->s1));
     if (key == c->geom_cache) return MM_OK;
     std::vector<int32_t> s0((size_t)j->n_blocks), s1((size_t)j->n_blocks);
     const int64_t *B = j->seg_bounds, S = j->n_segs;
@@ -933,10 +768,9 @@ static int upload_geometry(mm_ctx *c) {
         s0[b] = (int32_t)std::min<int64_t>(std::lower_bound(B, B + S + 1, j->block_lo[b]) - B, S);
         s1[b] = (int32_t)std::min<int64_t>(std::lower_bound(B, B + S + 1, j->block_hi[b]) - B, S);
     }
-    HIPCHK(c, hipMemcpyAsync(c->seg_bounds_dev, j->seg_bounds, (S + 1) * sizeof(int64_t), hipMemcpyHostToDevice,
-                             c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->blk_s0, s0.data(), s0.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->blk_s1, s1.data(), s1.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(g->bounds, j->seg_bounds, (S + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(g->s0, s0.data(), s0.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(g->s1, s1.data(), s1.size() * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));  // host vectors are transient
     c->geom_cache = key;
     return MM_OK;
@@ -1040,16 +874,20 @@ static float pw_eval(const int32_t *P, const float *x) {
     return root < 0 ? 0.0f : val[root];
 }
 
-// Per-block programs on the device: blocks [lo_b, lo_b + n_b) of the line; one
-// program per distinct length (the clamped last blocks of a track differ).
-static int kb_upload(mm_ctx *c, const std::vector<int64_t> &lo, const std::vector<int64_t> &n) {
-    std::vector<int64_t> key(lo);
-    key.insert(key.end(), n.begin(), n.end());
-    const size_t nb = lo.size();
+// Per-block programs on the device: blocks [lo_b, hi_b) of the line; one program
+// per distinct length (the clamped last blocks of a track differ).  The blocks the
+// device already holds are recognised without building anything: a unit calls this
+// before its first launch, on the step's critical path.
+static int kb_upload(mm_ctx *c, const int64_t *lo, const int64_t *hi, size_t nb) {
+    if (c->kb_prog && c->kb_cache.size() == 2 * nb && std::equal(lo, lo + nb, c->kb_cache.begin()) &&
+        std::equal(hi, hi + nb, c->kb_cache.begin() + nb))
+        return MM_OK;
+    std::vector<int64_t> key(lo, lo + nb), n(nb);
+    key.insert(key.end(), hi, hi + nb);
+    for (size_t b = 0; b < nb; ++b) n[b] = hi[b] - lo[b];
     RET(get_buf(c, "kb_lo", std::max<size_t>(nb, 1), &c->kb_lo));
     RET(get_buf(c, "kb_prog_of", std::max<size_t>(nb, 1), &c->kb_prog_of));
     RET(get_buf(c, "kb_n", std::max<size_t>(nb, 1), &c->kb_n));
-    if (key == c->kb_cache && c->kb_prog) return MM_OK;
     std::map<int64_t, int32_t> at;
     std::vector<int32_t> prog, of(nb), n32(nb);
     int nvals = 1, pints = 4;
@@ -1073,7 +911,7 @@ static int kb_upload(mm_ctx *c, const std::vector<int64_t> &lo, const std::vecto
     prog.resize(prog.size() + pints, 0);  // every block copies the largest program's length
     RET(get_buf(c, "kb_prog", prog.size(), &c->kb_prog));
     if (nb) {
-        HIPCHK(c, hipMemcpyAsync(c->kb_lo, lo.data(), nb * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->kb_lo, lo, nb * 8, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->kb_prog_of, of.data(), nb * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->kb_n, n32.data(), nb * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->kb_prog, prog.data(), prog.size() * 4, hipMemcpyHostToDevice, c->stream));
@@ -1085,24 +923,30 @@ static int kb_upload(mm_ctx *c, const std::vector<int64_t> &lo, const std::vecto
     return MM_OK;
 }
 
-// K-weighting + per-segment energies of the staged mix (device).  Returns the
-// device segment-energy vector; `line_end` receives the state after the last
-// frame when requested.
-static int kweight_launch(mm_ctx *c, const double *carry_in_host, double *line_end, double **seg_out) {
-    const mm_job *j = &c->job;
-    const int64_t G = c->G;
-    // one lane per sub-tile of kweight.tile frames (design.kweight_sub), `sub` per tile
-    const int sub = j->tile / j->kweight.tile;
-    const int64_t GS = G * sub;
-    double *part, *seg;
-    int64_t *part_seg;
-    RET(get_buf(c, "kw_part", (size_t)std::max<int64_t>(GS, 1) * 2, &part));
-    RET(get_buf(c, "kw_part_seg", (size_t)std::max<int64_t>(GS, 1), &part_seg));
-    RET(get_buf(c, "kw_seg", (size_t)j->n_segs, &seg));
-    RET(upload_geometry(c));
+// The K-weighting kernel's arguments for the staged mix of G tiles holding `frames`
+// frames: one lane per sub-tile of kweight.tile frames (design.kweight_sub), `sub`
+// per tile.  The caller adds its mode's outputs and, for a timeline, the track tables.
+static KwArgs kw_args(const mm_ctx *c, const mm_job *j, int64_t frames, int64_t G) {
+    KwArgs ka{};
+    ka.sub = j->tile / j->kweight.tile;
+    ka.N_proc = frames;
+    ka.G = G * ka.sub;
+    ka.T = j->kweight.tile;
+    ka.Gt = G;
+    ka.ch = j->channels;
+    for (int s_ = 0; s_ < 2; ++s_)
+        for (int k = 0; k < 5; ++k) ka.sos[s_][k] = j->kweight.sos[s_][k];
+    ka.mix = reinterpret_cast<const int16_t *>(c->mix);
+    return ka;
+}
+
+// Queue the K-weighting of the staged line (SQ: pass 2 writes the f32 squares, else
+// the segment partials); a time-sharded range starts from `carry_in_host`.
+template <bool SQ>
+static int kweight_run(mm_ctx *c, const mm_job *j, const KwArgs &ka, const double *carry_in_host = nullptr) {
     LbArgs lb{};
     RET(upload_tables(c, "kweight", j->kweight, lb));
-    const unsigned nblk = blocks_for(GS, LB_THREADS);
+    const unsigned nblk = blocks_for(ka.G, LB_THREADS);
     RET(lb_prepare(c, nblk, 1, lb, 2));
     if (carry_in_host) {
         double *init;
@@ -1111,63 +955,58 @@ static int kweight_launch(mm_ctx *c, const double *carry_in_host, double *line_e
         HIPCHK(c, hipStreamSynchronize(c->stream));  // pageable source
         lb.init = init;
     }
-    KwArgs ka{};
-    ka.N_proc = j->frames_proc;
-    ka.G = GS;
-    ka.T = j->kweight.tile;
-    ka.Gt = G;
-    ka.sub = sub;
-    ka.ch = j->channels;
-    for (int s_ = 0; s_ < 2; ++s_)
-        for (int k = 0; k < 5; ++k) ka.sos[s_][k] = j->kweight.sos[s_][k];
-    ka.mix = reinterpret_cast<const int16_t *>(c->mix);
-    ka.n_segs = j->n_segs;
-    ka.seg_bounds = c->seg_bounds_dev;
-    ka.part = part;
-    ka.part_seg = part_seg;
+    return launch(c, "kweight", kweight_kernel<SQ>, dim3(nblk), dim3(LB_THREADS), lb_lds_bytes<4, 1>(), ka, lb);
+}
+
+// Segment energies of a line (round 5's loudness, and the time-sharded ranks'):
+// K-weighting + f64 energies per segment of `g`.  Returns the device segment-energy
+// vector; `line_end` receives the state after the last frame when requested.
+static int kweight_segments(mm_ctx *c, const mm_job *j, int64_t frames, const LineGeom &g,
+                            const double *carry_in_host, double *line_end, double **seg_out) {
+    KwArgs ka = kw_args(c, j, frames, c->G);
+    double *seg;
+    RET(get_buf(c, "kw_part", (size_t)std::max<int64_t>(ka.G, 1) * 2, &ka.part));
+    RET(get_buf(c, "kw_part_seg", (size_t)std::max<int64_t>(ka.G, 1), &ka.part_seg));
+    RET(get_buf(c, "kw_seg", (size_t)g.n_segs, &seg));
+    ka.n_segs = g.n_segs;
+    ka.seg_bounds = g.bounds;
     ka.line_end = line_end;
-    RET(launch(c, "kweight", kweight_kernel<false>, dim3(nblk), dim3(LB_THREADS), lb_lds_bytes<4, 1>(), ka, lb));
-    RET(launch(c, "seg_reduce", seg_reduce_kernel, dim3(blocks_for(j->n_segs, 4)), dim3(256), 0, ka, seg));  // wave per segment
+    ka.n_trk = g.n_trk;
+    ka.trk_tile0 = g.trk_tile0;
+    ka.trk_end = g.trk_end;
+    RET(kweight_run<false>(c, j, ka, carry_in_host));
+    RET(launch(c, "seg_reduce", seg_reduce_kernel, dim3(blocks_for(g.n_segs, 4)), dim3(256), 0, ka, seg));  // wave per segment
     *seg_out = seg;
     return MM_OK;
+}
+
+// The staged job's segment energies (time-sharded ranks: carry-in state, range end state).
+static int kweight_staged(mm_ctx *c, const double *carry_in_host, double *line_end, double **seg_out) {
+    LineGeom g;
+    RET(upload_geometry(c, &c->job, &g));
+    return kweight_segments(c, &c->job, c->job.frames_proc, g, carry_in_host, line_end, seg_out);
 }
 
 // The exact loudness of a line (single track or fused timeline, AME:212-218): the
 // K-weighting in lfilter's order writing np.square's f32 values, then pyloudnorm's
 // block energies in numpy's reduction order (kw_blocks_kernel) into zl [2 nb].
 // The block programs must be on the device (kb_upload) before this is queued.
-static int kweight_exact(mm_ctx *c, const mm_job &j0, int64_t frames, int n_trk, const int64_t *trk_tile0,
-                         const int64_t *trk_end, int64_t nb, double **zl_out) {
-    const int64_t G = c->G;
-    const int sub = j0.tile / j0.kweight.tile;  // (design.kweight_sub)
-    const int64_t GS = G * sub;
+static int kweight_exact(mm_ctx *c, const mm_job *j, int64_t frames, const LineGeom &g, double **zl_out) {
+    const int64_t G = c->G, nb = g.n_blocks;
     float *sq;
     double *zl;
-    const int Tt = j0.tile, TP = (Tt + 3) / 4 * 4;  // padded tile stride (16-byte stores and loads)
+    const int Tt = j->tile, TP = (Tt + 3) / 4 * 4;  // padded tile stride (16-byte stores and loads)
     if (((KB_CHUNK - 1) / Tt + 2) * (TP / 4) > KB_LD * KB_THREADS)
         return set_err(c, MM_ERR_ARG, "tile of %d frames: the loudness block loads do not cover a chunk", Tt);
     RET(get_buf(c, "kw_sq", (size_t)(G * TP), &sq));
     RET(get_buf(c, "gate_zl", (size_t)std::max<int64_t>(2 * nb, 2), &zl));
-    LbArgs lb{};
-    RET(upload_tables(c, "kweight", j0.kweight, lb));
-    const unsigned nblk = blocks_for(GS, LB_THREADS);
-    RET(lb_prepare(c, nblk, 1, lb, 2));
-    KwArgs ka{};
-    ka.N_proc = frames;
-    ka.G = GS;
-    ka.T = j0.kweight.tile;
-    ka.Gt = G;
-    ka.sub = sub;
-    ka.ch = j0.channels;
-    for (int s_ = 0; s_ < 2; ++s_)
-        for (int k = 0; k < 5; ++k) ka.sos[s_][k] = j0.kweight.sos[s_][k];
-    ka.mix = reinterpret_cast<const int16_t *>(c->mix);
-    ka.n_trk = n_trk;
-    ka.trk_tile0 = trk_tile0;
-    ka.trk_end = trk_end;
+    KwArgs ka = kw_args(c, j, frames, G);
+    ka.n_trk = g.n_trk;
+    ka.trk_tile0 = g.trk_tile0;
+    ka.trk_end = g.trk_end;
     ka.sq = sq;
     ka.sq_tp = TP;
-    RET(launch(c, "kweight", kweight_kernel<true>, dim3(nblk), dim3(LB_THREADS), lb_lds_bytes<4, 1>(), ka, lb));
+    RET(kweight_run<true>(c, j, ka));
     if (nb > 0) {
         KbArgs kb{};
         kb.sq = sq;
@@ -1178,7 +1017,7 @@ static int kweight_exact(mm_ctx *c, const mm_job &j0, int64_t frames, int n_trk,
         kb.blk_prog = c->kb_prog_of;
         kb.blk_n = c->kb_n;
         kb.prog = c->kb_prog;
-        kb.scale = (float)j0.block_scale;  // Python float * np.float32: the constant rounded to f32 (NEP 50)
+        kb.scale = (float)j->block_scale;  // Python float * np.float32: the constant rounded to f32 (NEP 50)
         kb.zl = zl;
         kb.stage_floats = ((KB_CHUNK - 1) / Tt + 2) * TP;  // the padded tile runs a chunk can span
         kb.nvals = 2 * c->kb_nvals;  // (two value buffers)
@@ -1197,7 +1036,7 @@ static int kweight_exact(mm_ctx *c, const mm_job &j0, int64_t frames, int n_trk,
 static int kweight_energies(mm_ctx *c, const double *carry_in_host, double *seg_host, double *range_end_host) {
     double *lend, *seg;
     RET(get_buf(c, "kw_lend", 8, &lend));
-    RET(kweight_launch(c, carry_in_host, range_end_host ? lend : nullptr, &seg));
+    RET(kweight_staged(c, carry_in_host, range_end_host ? lend : nullptr, &seg));
     if (range_end_host)
         HIPCHK(c, hipMemcpyAsync(range_end_host, lend, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (seg_host)
@@ -1217,37 +1056,27 @@ static int gate_launch(mm_ctx *c, GateArgs ga, unsigned n_tracks) {
     return launch(c, "gate", gate_kernel, dim3(n_tracks), dim3(GATE_THREADS), 0, ga);
 }
 
-// Whole-track loudness and gain on the device (no host round trip), exactly
-// pyloudnorm's block energies.
-static int kweight_device(mm_ctx *c) {
-    const mm_job *j = &c->job;
-    if (getenv("MM_LOUDNESS_SEGMENTS")) {  // (A/B builds: round 5's f64 segment energies)
+// Loudness and gain of every track of the staged line on the device (no host round
+// trip) into out[2i] = L, out[2i+1] = gain: exactly pyloudnorm's block energies, or
+// with MM_LOUDNESS_SEGMENTS round 5's f64 segment energies (A/B builds).  The
+// line's geometry must be on the device (unit_geometry) before this is queued.
+static int line_loudness(mm_ctx *c, const mm_job *j, int64_t frames, const LineGeom &g, double *out) {
+    GateArgs ga{};
+    ga.n_blocks = g.n_blocks;
+    ga.target = j->lufs_target;
+    ga.out = out;
+    ga.trk_blk = g.trk_blk;
+    if (getenv("MM_LOUDNESS_SEGMENTS")) {
         double *seg;
-        RET(kweight_launch(c, nullptr, nullptr, &seg));
-        GateArgs ga{};
-        ga.n_blocks = j->n_blocks;
-        ga.blk_s0 = c->blk_s0;
-        ga.blk_s1 = c->blk_s1;
+        RET(kweight_segments(c, j, frames, g, nullptr, nullptr, &seg));
+        ga.blk_s0 = g.s0;
+        ga.blk_s1 = g.s1;
         ga.seg = seg;
         ga.scale = j->block_scale;
-        ga.target = j->lufs_target;
-        ga.out = c->gate_out;
-        return gate_launch(c, ga, 1);
+    } else {
+        RET(kweight_exact(c, j, frames, g, &ga.zl));
     }
-    {
-        std::vector<int64_t> lo(j->block_lo, j->block_lo + j->n_blocks), n((size_t)j->n_blocks);
-        for (int64_t b = 0; b < j->n_blocks; ++b) n[b] = j->block_hi[b] - j->block_lo[b];
-        RET(kb_upload(c, lo, n));
-    }
-    double *zl;
-    RET(kweight_exact(c, *j, j->frames_proc, 0, nullptr, nullptr, j->n_blocks, &zl));
-    // c->gate_out: in the control block's readback area (setup_control)
-    GateArgs ga{};
-    ga.n_blocks = j->n_blocks;
-    ga.target = j->lufs_target;
-    ga.out = c->gate_out;
-    ga.zl = zl;
-    return gate_launch(c, ga, 1);
+    return gate_launch(c, ga, (unsigned)std::max(g.n_trk, 1));
 }
 
 // numpy's float32 np.sum over x[0..n) evaluated on the host through the same
@@ -1296,15 +1125,17 @@ extern "C" int mm_gate_loudness(const mm_job *j, const double *seg_energy, doubl
     return MM_OK;
 }
 
-static int finalize(mm_ctx *c, double gain, const double *gain_dev, int use_gain, void *d_out, bool tail = false) {
-    const mm_job *j = &c->job;
+// One track of the staged mix to its output: G tiles from tile g_off on.  `tail`:
+// the chain's last finalize launch, which hands the readback area over.
+static int finalize(mm_ctx *c, const mm_job *j, int64_t G, int64_t g_off, double gain, const double *gain_dev,
+                    int use_gain, void *d_out, bool tail = false) {
     c->tail_readback = false;
-    if (c->G == 0) return MM_OK;
+    if (G == 0) return MM_OK;
     FinArgs fa{};
     fa.N_proc = j->frames_proc;
-    fa.G = c->G;
+    fa.G = G;
     fa.Gs = c->G;
-    fa.g_off = 0;
+    fa.g_off = g_off;
     fa.T = j->tile;
     fa.ch = j->channels;
     fa.out_kind = j->out_kind;
@@ -1316,64 +1147,14 @@ static int finalize(mm_ctx *c, double gain, const double *gain_dev, int use_gain
     if (tail) RET(attach_tail(c, fa));
     const size_t lds = (size_t)FIN_TILES * (j->tile + 1) * sizeof(short2);
     if (fa.ch == 2)
-        return launch(c, "finalize", finalize_kernel<2>, dim3(blocks_for(c->G, FIN_TILES)), dim3(256), lds, fa);
-    return launch(c, "finalize", finalize_kernel<1>, dim3(blocks_for(c->G, FIN_TILES)), dim3(256), lds, fa);
-}
-
-// The chain is queued without host round trips (enqueue_chain); one sync at the
-// end (complete_chain) checks the compressor's convergence (a rare unconverged
-// batch is extended and the dependent stages re-run) and reads the loudness.
-static int enqueue_tail(mm_ctx *c, const mm_job *j, void *d_out) {
-    const bool lufs = j->lufs_on && c->G > 0;
-    if (lufs) RET(kweight_device(c));
-    RET(finalize(c, 1.0, lufs ? c->gate_out + 1 : nullptr, j->lufs_on, d_out, true));
-    return c->tail_readback ? MM_OK : queue_readback(c, lufs);
-}
-
-static int enqueue_chain(mm_ctx *c, const mm_job *j, const void *d_in, void *d_out) {
-    RET(stage_front(c, j, d_in));
-    return enqueue_tail(c, j, d_out);
-}
-
-static int complete_chain(mm_ctx *c, const mm_job *j, void *d_out, mm_result *res) {
-    RbKeep keep;
-    for (;;) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        bool converged;
-        RET(evaluate_chain(c, &converged));
-        if (converged) break;
-        rb_keep(c, keep);
-        RET(comp_sweeps(c, 8));
-        RET(comp_back(c));
-        RET(enqueue_tail(c, j, d_out));
-    }
-    rb_finish(c, keep);
-    if (res) {
-        const bool lufs = j->lufs_on && c->G > 0;
-        const double *lg = reinterpret_cast<const double *>(c->rb + RB_LG);
-        res->loudness = j->lufs_on ? (lufs ? lg[0] : -INFINITY) : NAN;  // no frames: pyloudnorm raised earlier
-        res->gain_linear = j->lufs_on ? (lufs ? lg[1] : INFINITY) : 1.0;
-        res->frames_out = j->frames_proc;
-        res->comp_iters = c->comp_iters;
-        res->comp_active = 0;
-        const int32_t *tot = reinterpret_cast<const int32_t *>(c->rb + RB_TOTALS);
-        for (int64_t k = 0; k < 3 * comp_chunks(c); ++k) res->comp_active += tot[k];
-        res->comp_walked = c->comp_on ? (int64_t) * reinterpret_cast<const unsigned long long *>(c->rb + RB_WALKED) : 0;
-        res->comp_jumped = c->comp_on ? (int64_t) * reinterpret_cast<const unsigned long long *>(c->rb + RB_WALKED + 8) : 0;
-    }
-    return MM_OK;
-}
-
-static int master_device(mm_ctx *c, const mm_job *j, const void *d_in, void *d_out, mm_result *res) {
-    c->meters.clear();
-    RET(enqueue_chain(c, j, d_in, d_out));
-    RET(complete_chain(c, j, d_out, res));
-    return j->meter_on ? chain_meter(c, j, d_out, 0, 1) : MM_OK;
+        return launch(c, "finalize", finalize_kernel<2>, dim3(blocks_for(G, FIN_TILES)), dim3(256), lds, fa);
+    return launch(c, "finalize", finalize_kernel<1>, dim3(blocks_for(G, FIN_TILES)), dim3(256), lds, fa);
 }
 
 // Stage the chunk chain of a range (time-sharded ranks) to convergence.
 static int stage_chunks(mm_ctx *c, const mm_job *j, const void *d_in) {
-    RET(stage_front(c, j, d_in));
+    RET(validate(c, j));
+    RET(stage_front(c, j, d_in, j->lufs_on ? kw_nblk(j, (j->frames_proc + j->tile - 1) / j->tile) : 0u));
     for (;;) {
         bool converged;
         RET(chain_check(c, &converged));
@@ -1383,25 +1164,32 @@ static int stage_chunks(mm_ctx *c, const mm_job *j, const void *d_in) {
     }
 }
 
-// ------------------------------------------------------------ fused batch
-// Tracks with the same settings mastered as ONE timeline (BASELINE C3/C5 on one
-// GPU).  Track i occupies whole chunks [off_i, off_i + n_i * CF) of it, its last
-// chunk zero-padded; every per-chunk stage (EQ, crossover, compressor: AME:48-77
-// restarts them per chunk) then runs once over all tracks with the single-track
-// kernels, and the padding changes none of a track's frames because it follows
-// them and every stage is causal.  The K-weighting line restarts at each track
-// start and gives padding frames zero energy; the gating runs one block per
-// track; finalize writes every track to its own output.  One launch per stage
-// covers the whole batch (n times one track's lanes), which fills the GPU where a
-// single track's latency-bound launches leave most SIMDs idle.
-struct FusedPlan {
+// ------------------------------------------------------------------ units
+// What a context runs between two syncs: n >= 1 tracks with the same settings,
+// mastered as ONE line.  A single track (mm_master*, a batch's lone tracks) is a
+// unit of one and keeps its own geometry: its job goes to the chunk stages as it
+// is, the line is its ceil(frames / tile) tiles, and L and the gain arrive with the
+// tail's readback.  A fused unit (n > 1: a same-settings run of mm_master_batch,
+// BASELINE C3/C5 on one GPU) is a timeline: track i occupies whole chunks
+// [off_i, off_i + n_i * CF) of it, its last chunk zero-padded; every per-chunk
+// stage (EQ, crossover, compressor: AME:48-77 restarts them per chunk) then runs
+// once over all tracks with the single-track kernels, and the padding changes none
+// of a track's frames because it follows them and every stage is causal.  The
+// K-weighting line restarts at each track start and gives padding frames zero
+// energy; the gating runs one block per track; finalize writes every track to its
+// own output.  One launch per stage covers the whole batch (n times one track's
+// lanes), which fills the GPU where a single track's latency-bound launches leave
+// most SIMDs idle.
+struct Unit {
+    int n = 1;
+    const mm_job *J = nullptr;        // [n]
+    const void *const *in = nullptr;  // [n] device inputs
+    void *const *out = nullptr;       // [n] device outputs
+    // the timeline's layout (n > 1: unit_layout)
     std::vector<int64_t> off;  // [n + 1] first timeline frame of each track (and the end)
     std::vector<int64_t> nch;  // [n] chunks of each track
     int64_t P = 0;             // timeline frames
-    // loudness geometry on the device
-    int64_t n_segs = 0, n_blocks = 0;
-    int64_t *bounds = nullptr, *trk_blk = nullptr, *trk_tile0 = nullptr, *trk_end = nullptr;
-    int32_t *s0 = nullptr, *s1 = nullptr;
+    LineGeom geom;             // loudness geometry on the device (unit_geometry)
 };
 
 static bool same_iir(const mm_iir &a, const mm_iir &b) { return memcmp(&a, &b, sizeof a) == 0; }
@@ -1440,7 +1228,9 @@ static bool fusable(const mm_job *J, int n) {
     return true;
 }
 
-static bool fused_layout(const mm_job *J, int n, FusedPlan *p) {
+static bool unit_layout(Unit *p) {
+    const mm_job *J = p->J;
+    const int n = p->n;
     const int64_t CF = (int64_t)J[0].tile * J[0].tiles_per_chunk;
     p->off.assign((size_t)n + 1, 0);
     p->nch.assign((size_t)n, 0);
@@ -1452,12 +1242,22 @@ static bool fused_layout(const mm_job *J, int n, FusedPlan *p) {
     return p->P < ((int64_t)1 << 31);  // 32-bit frame indexing
 }
 
-// Loudness geometry of the timeline, uploaded before anything is queued (its one
-// sync then waits on nothing): every track's segment bounds shifted to its
-// offset (a bound shared with the previous track's end is not repeated; the gap
-// between a track's last bound and the next track start is a padding segment
-// no gating block reads), every track's blocks as segment ranges of that list.
-static int fused_geometry(mm_ctx *c, const mm_job *J, int n, FusedPlan *p) {
+// Loudness geometry of the unit's line, uploaded before anything is queued (its one
+// sync then waits on nothing).  A unit of one: the block programs of the track's
+// own blocks (or its segment tables), cached on the context.  A timeline: every
+// track's segment bounds shifted to its offset (a bound shared with the previous
+// track's end is not repeated; the gap between a track's last bound and the next
+// track start is a padding segment no gating block reads), every track's blocks as
+// segment ranges of that list, and the block programs at the timeline offsets.
+static int unit_geometry(mm_ctx *c, Unit *p) {
+    const mm_job *J = p->J;
+    const int n = p->n;
+    if (n == 1) {
+        if (getenv("MM_LOUDNESS_SEGMENTS")) return upload_geometry(c, J, &p->geom);
+        p->geom = LineGeom{};
+        p->geom.n_blocks = J->n_blocks;
+        return kb_upload(c, J->block_lo, J->block_hi, (size_t)J->n_blocks);
+    }
     const int T = J[0].tile;
     std::vector<int64_t> bounds, tblk((size_t)n + 1), tt0((size_t)n), tend((size_t)n);
     std::vector<int32_t> s0, s1;
@@ -1483,160 +1283,95 @@ static int fused_geometry(mm_ctx *c, const mm_job *J, int n, FusedPlan *p) {
     }
     tblk[n] = (int64_t)s0.size();
     {  // the exact path's blocks: every track's own blocks at its timeline offset
-        std::vector<int64_t> lo, len;
+        std::vector<int64_t> lo, hi;
         for (int i = 0; i < n; ++i)
             for (int64_t b = 0; b < J[i].n_blocks; ++b) {
                 lo.push_back(p->off[i] + J[i].block_lo[b]);
-                len.push_back(J[i].block_hi[b] - J[i].block_lo[b]);
+                hi.push_back(p->off[i] + J[i].block_hi[b]);
             }
-        RET(kb_upload(c, lo, len));
+        RET(kb_upload(c, lo.data(), hi.data(), lo.size()));
     }
     if (bounds.back() < p->P) bounds.push_back(p->P);  // the last track's padding
-    p->n_segs = (int64_t)bounds.size() - 1;
-    p->n_blocks = (int64_t)s0.size();
-    RET(get_buf(c, "fz_bounds", bounds.size(), &p->bounds));
-    RET(get_buf(c, "fz_trk_blk", tblk.size(), &p->trk_blk));
-    RET(get_buf(c, "fz_trk_tile0", tt0.size(), &p->trk_tile0));
-    RET(get_buf(c, "fz_trk_end", tend.size(), &p->trk_end));
-    RET(get_buf(c, "fz_s0", std::max<size_t>(s0.size(), 1), &p->s0));
-    RET(get_buf(c, "fz_s1", std::max<size_t>(s1.size(), 1), &p->s1));
-    HIPCHK(c, hipMemcpyAsync(p->bounds, bounds.data(), bounds.size() * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(p->trk_blk, tblk.data(), tblk.size() * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(p->trk_tile0, tt0.data(), tt0.size() * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(p->trk_end, tend.data(), tend.size() * 8, hipMemcpyHostToDevice, c->stream));
+    p->geom.n_segs = (int64_t)bounds.size() - 1;
+    p->geom.n_blocks = (int64_t)s0.size();
+    p->geom.n_trk = n;
+    RET(get_buf(c, "fz_bounds", bounds.size(), &p->geom.bounds));
+    RET(get_buf(c, "fz_trk_blk", tblk.size(), &p->geom.trk_blk));
+    RET(get_buf(c, "fz_trk_tile0", tt0.size(), &p->geom.trk_tile0));
+    RET(get_buf(c, "fz_trk_end", tend.size(), &p->geom.trk_end));
+    RET(get_buf(c, "fz_s0", std::max<size_t>(s0.size(), 1), &p->geom.s0));
+    RET(get_buf(c, "fz_s1", std::max<size_t>(s1.size(), 1), &p->geom.s1));
+    HIPCHK(c, hipMemcpyAsync(p->geom.bounds, bounds.data(), bounds.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(p->geom.trk_blk, tblk.data(), tblk.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(p->geom.trk_tile0, tt0.data(), tt0.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(p->geom.trk_end, tend.data(), tend.size() * 8, hipMemcpyHostToDevice, c->stream));
     if (!s0.empty()) {
-        HIPCHK(c, hipMemcpyAsync(p->s0, s0.data(), s0.size() * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(p->s1, s1.data(), s1.size() * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(p->geom.s0, s0.data(), s0.size() * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(p->geom.s1, s1.data(), s1.size() * 4, hipMemcpyHostToDevice, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));  // host vectors are transient
     return MM_OK;
 }
 
-// K-weighting (a line per track), segment energies and per-track gating into
-// lg[2i] = L, lg[2i+1] = gain.
-static int fused_loudness(mm_ctx *c, const mm_job &j0, int n, const FusedPlan &p, double *lg) {
-    if (!getenv("MM_LOUDNESS_SEGMENTS")) {  // exact block energies (the programs: fused_geometry)
-        double *zl;
-        RET(kweight_exact(c, j0, p.P, n, p.trk_tile0, p.trk_end, p.n_blocks, &zl));
-        GateArgs ga{};
-        ga.n_blocks = p.n_blocks;
-        ga.target = j0.lufs_target;
-        ga.out = lg;
-        ga.trk_blk = p.trk_blk;
-        ga.zl = zl;
-        return gate_launch(c, ga, (unsigned)n);
-    }
-    const int64_t G = c->G;
-    const int sub = j0.tile / j0.kweight.tile;  // (design.kweight_sub)
-    const int64_t GS = G * sub;
-    double *part, *seg;
-    int64_t *part_seg;
-    RET(get_buf(c, "kw_part", (size_t)GS * 2, &part));
-    RET(get_buf(c, "kw_part_seg", (size_t)GS, &part_seg));
-    RET(get_buf(c, "kw_seg", (size_t)p.n_segs, &seg));
-    LbArgs lb{};
-    RET(upload_tables(c, "kweight", j0.kweight, lb));
-    const unsigned nblk = blocks_for(GS, LB_THREADS);
-    RET(lb_prepare(c, nblk, 1, lb, 2));
-    KwArgs ka{};
-    ka.N_proc = p.P;
-    ka.G = GS;
-    ka.T = j0.kweight.tile;
-    ka.Gt = G;
-    ka.sub = sub;
-    ka.ch = j0.channels;
-    for (int s_ = 0; s_ < 2; ++s_)
-        for (int k = 0; k < 5; ++k) ka.sos[s_][k] = j0.kweight.sos[s_][k];
-    ka.mix = reinterpret_cast<const int16_t *>(c->mix);
-    ka.n_segs = p.n_segs;
-    ka.seg_bounds = p.bounds;
-    ka.part = part;
-    ka.part_seg = part_seg;
-    ka.n_trk = n;
-    ka.trk_tile0 = p.trk_tile0;
-    ka.trk_end = p.trk_end;
-    RET(launch(c, "kweight", kweight_kernel<false>, dim3(nblk), dim3(LB_THREADS), lb_lds_bytes<4, 1>(), ka, lb));
-    RET(launch(c, "seg_reduce", seg_reduce_kernel, dim3(blocks_for(p.n_segs, 4)), dim3(256), 0, ka, seg));
-    GateArgs ga{};
-    ga.n_blocks = p.n_blocks;
-    ga.blk_s0 = p.s0;
-    ga.blk_s1 = p.s1;
-    ga.seg = seg;
-    ga.scale = j0.block_scale;
-    ga.target = j0.lufs_target;
-    ga.out = lg;
-    ga.trk_blk = p.trk_blk;
-    return gate_launch(c, ga, (unsigned)n);
+// Loudness of the staged line, every track's finalize (the last launch hands the
+// readback area over), and the readback: what follows the chunk stages, and again
+// an extended solve.
+static int unit_tail(mm_ctx *c, const Unit &u) {
+    const mm_job &j0 = u.J[0];
+    const bool fused = u.n > 1, lufs = j0.lufs_on && c->G > 0;
+    // lg[2i] = L, lg[2i+1] = gain: a single track's in the readback area (setup_control)
+    double *lg = c->gate_out;
+    if (fused) RET(get_buf(c, "fz_lg", (size_t)2 * u.n, &lg));
+    if (lufs) RET(line_loudness(c, &j0, fused ? u.P : j0.frames_proc, u.geom, lg));
+    for (int i = 0; i < u.n; ++i)
+        RET(finalize(c, &u.J[i], fused ? u.nch[i] * j0.tiles_per_chunk : c->G, fused ? u.off[i] / j0.tile : 0, 1.0,
+                     lufs ? lg + 2 * i + 1 : nullptr, j0.lufs_on, u.out[i], i == u.n - 1));
+    return c->tail_readback ? MM_OK : queue_readback(c);
 }
 
-static int fused_finalize(mm_ctx *c, const mm_job *J, int n, const FusedPlan &p, const double *lg, void *const *d_out) {
-    const mm_job &j0 = J[0];
-    const int T = j0.tile;
-    const size_t lds = (size_t)FIN_TILES * (T + 1) * sizeof(short2);
-    c->tail_readback = false;
-    for (int i = 0; i < n; ++i) {
-        FinArgs fa{};
-        fa.N_proc = J[i].frames_proc;
-        fa.G = p.nch[i] * j0.tiles_per_chunk;
-        fa.Gs = c->G;
-        fa.g_off = p.off[i] / T;
-        fa.T = T;
-        fa.ch = j0.channels;
-        fa.out_kind = j0.out_kind;
-        fa.use_gain = j0.lufs_on;
-        fa.gain = 1.0;
-        fa.gain_dev = j0.lufs_on ? lg + 2 * i + 1 : nullptr;
-        fa.mix = c->mix;
-        fa.out = d_out[i];
-        if (i == n - 1 && fa.G > 0) RET(attach_tail(c, fa));
-        const dim3 grid(blocks_for(fa.G, FIN_TILES));
-        if (fa.ch == 2) RET(launch(c, "finalize", finalize_kernel<2>, grid, dim3(256), lds, fa));
-        else RET(launch(c, "finalize", finalize_kernel<1>, grid, dim3(256), lds, fa));
-    }
-    return MM_OK;
-}
-
-// Queue a fused unit: loudness geometry (uploaded first: its sync waits on an
-// idle stream), the input timeline (in place when the tracks already lie back to
-// back on whole chunks, else gathered with the padding zeroed), the chunk stages,
-// loudness and the per-track finalize.
-static int fused_enqueue(mm_ctx *c, int n, const mm_job *J, const void *const *d_in, void *const *d_out, FusedPlan &p) {
-    const mm_job &j0 = J[0];
-    const bool lufs = j0.lufs_on != 0;
-    if (lufs) RET(fused_geometry(c, J, n, &p));
-    const size_t fb = (size_t)j0.channels * (j0.in_kind == MM_IN_I16 ? 2 : 4);
-    bool in_place = true;
-    for (int i = 0; i < n && in_place; ++i)
-        in_place = J[i].frames_in == p.off[i + 1] - p.off[i] &&
-                   static_cast<const char *>(d_in[i]) == static_cast<const char *>(d_in[0]) + p.off[i] * fb;
-    const void *tin = d_in[0];
-    if (!in_place) {
-        char *buf;
-        RET(get_buf(c, "fz_in", (size_t)p.P * fb, &buf));
-        for (int i = 0; i < n; ++i) {
-            const int64_t len = p.off[i + 1] - p.off[i], nin = std::min(J[i].frames_in, len);
-            if (nin > 0)
-                HIPCHK(c, hipMemcpyAsync(buf + p.off[i] * fb, d_in[i], nin * fb, hipMemcpyDeviceToDevice, c->stream));
-            if (len > nin) HIPCHK(c, hipMemsetAsync(buf + (p.off[i] + nin) * fb, 0, (len - nin) * fb, c->stream));
+// Queue a unit without host round trips: loudness geometry (uploaded first: its
+// sync waits on an idle stream), for a timeline its input (in place when the tracks
+// already lie back to back on whole chunks, else gathered with the padding zeroed),
+// the chunk stages, then the tail.
+static int unit_enqueue(mm_ctx *c, Unit &u) {
+    RET(validate(c, u.J));
+    const mm_job &j0 = u.J[0];
+    const bool fused = u.n > 1;
+    const int64_t G = ((fused ? u.P : j0.frames_proc) + j0.tile - 1) / j0.tile;
+    const bool lufs = j0.lufs_on && G > 0;  // (G == 0: a single empty track; fusable tracks have frames)
+    if (lufs) RET(unit_geometry(c, &u));
+    const mm_job *line = &j0;
+    const void *tin = u.in[0];
+    mm_job tj;
+    if (fused) {
+        const size_t fb = (size_t)j0.channels * (j0.in_kind == MM_IN_I16 ? 2 : 4);
+        bool in_place = true;
+        for (int i = 0; i < u.n && in_place; ++i)
+            in_place = u.J[i].frames_in == u.off[i + 1] - u.off[i] &&
+                       static_cast<const char *>(u.in[i]) == static_cast<const char *>(u.in[0]) + u.off[i] * fb;
+        if (!in_place) {
+            char *buf;
+            RET(get_buf(c, "fz_in", (size_t)u.P * fb, &buf));
+            for (int i = 0; i < u.n; ++i) {
+                const int64_t len = u.off[i + 1] - u.off[i], nin = std::min(u.J[i].frames_in, len);
+                if (nin > 0)
+                    HIPCHK(c, hipMemcpyAsync(buf + u.off[i] * fb, u.in[i], nin * fb, hipMemcpyDeviceToDevice, c->stream));
+                if (len > nin) HIPCHK(c, hipMemsetAsync(buf + (u.off[i] + nin) * fb, 0, (len - nin) * fb, c->stream));
+            }
+            tin = buf;
         }
-        tin = buf;
+        tj = j0;  // the timeline as one job (loudness is per track)
+        tj.frames_in = tj.frames_proc = u.P;
+        tj.lufs_on = 0;
+        line = &tj;
     }
-    mm_job tj = j0;  // the timeline as one job (loudness is per track)
-    tj.frames_in = tj.frames_proc = p.P;
-    tj.lufs_on = 0;
-    RET(stage_front(c, &tj, tin));
-    double *lg;
-    RET(get_buf(c, "fz_lg", (size_t)2 * n, &lg));
-    if (lufs) RET(fused_loudness(c, j0, n, p, lg));
-    RET(fused_finalize(c, J, n, p, lg, d_out));
-    return c->tail_readback ? MM_OK : queue_readback(c, lufs);
+    RET(stage_front(c, line, tin, lufs ? kw_nblk(&j0, G) : 0u));
+    return unit_tail(c, u);
 }
 
-static int fused_complete(mm_ctx *c, int n, const mm_job *J, void *const *d_out, mm_result *res, const FusedPlan &p) {
-    const mm_job &j0 = J[0];
-    const bool lufs = j0.lufs_on != 0;
-    double *lg;
-    RET(get_buf(c, "fz_lg", (size_t)2 * n, &lg));
+// The unit's one sync: checks the compressor's convergence (a rare unconverged
+// solve is extended and the tail re-run) and reads the results.
+static int unit_complete(mm_ctx *c, const Unit &u, mm_result *res) {
     RbKeep keep;
     for (;;) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1646,27 +1381,35 @@ static int fused_complete(mm_ctx *c, int n, const mm_job *J, void *const *d_out,
         rb_keep(c, keep);
         RET(comp_sweeps(c, 8));
         RET(comp_back(c));
-        if (lufs) RET(fused_loudness(c, j0, n, p, lg));
-        RET(fused_finalize(c, J, n, p, lg, d_out));
-        if (!c->tail_readback) RET(queue_readback(c, lufs));
+        RET(unit_tail(c, u));
     }
     rb_finish(c, keep);
     if (!res) return MM_OK;
-    std::vector<double> l2((size_t)2 * n, 0.0);
-    if (lufs) HIPCHK(c, hipMemcpy(l2.data(), lg, l2.size() * sizeof(double), hipMemcpyDeviceToHost));
+    const mm_job &j0 = u.J[0];
+    const bool fused = u.n > 1, lufs = j0.lufs_on && c->G > 0;
+    const double *lg = reinterpret_cast<const double *>(c->rb + RB_LG);
+    std::vector<double> l2;
+    if (fused && lufs) {  // (only a timeline's L and gains lie outside the readback area)
+        double *d;
+        RET(get_buf(c, "fz_lg", (size_t)2 * u.n, &d));
+        l2.resize((size_t)2 * u.n);
+        HIPCHK(c, hipMemcpy(l2.data(), d, l2.size() * sizeof(double), hipMemcpyDeviceToHost));
+        lg = l2.data();
+    }
     const int64_t nchk = comp_chunks(c), CF = (int64_t)j0.tile * j0.tiles_per_chunk;
     const int32_t *tot = reinterpret_cast<const int32_t *>(c->rb + RB_TOTALS);
     const int64_t walked = c->comp_on ? (int64_t) * reinterpret_cast<const unsigned long long *>(c->rb + RB_WALKED) : 0;
     const int64_t jumped = c->comp_on ? (int64_t) * reinterpret_cast<const unsigned long long *>(c->rb + RB_WALKED + 8) : 0;
-    for (int i = 0; i < n; ++i) {
+    for (int i = 0; i < u.n; ++i) {
         mm_result &r = res[i];
-        r.loudness = lufs ? l2[2 * i] : NAN;
-        r.gain_linear = lufs ? l2[2 * i + 1] : 1.0;
-        r.frames_out = J[i].frames_proc;
+        r.loudness = j0.lufs_on ? (lufs ? lg[2 * i] : -INFINITY) : NAN;  // no frames: pyloudnorm raised earlier
+        r.gain_linear = j0.lufs_on ? (lufs ? lg[2 * i + 1] : INFINITY) : 1.0;
+        r.frames_out = u.J[i].frames_proc;
         r.comp_iters = c->comp_iters;  // one solve for the whole unit
-        r.comp_active = 0;
+        r.comp_active = 0;             // summed over the track's own chunks (no compressor: no counts)
         for (int b = 0; b < 3 && c->comp_on; ++b)
-            for (int64_t k = p.off[i] / CF; k < p.off[i + 1] / CF; ++k) r.comp_active += tot[b * nchk + k];
+            for (int64_t k = fused ? u.off[i] / CF : 0; k < (fused ? u.off[i + 1] / CF : nchk); ++k)
+                r.comp_active += tot[b * nchk + k];
         // the unit's solve statistics are reported once, on its first track (sums over
         // a batch's results then count every unit once)
         r.comp_walked = i == 0 ? walked : 0;
@@ -1675,19 +1418,25 @@ static int fused_complete(mm_ctx *c, int n, const mm_job *J, void *const *d_out,
     return MM_OK;
 }
 
-// A unit of a batch: one track, or consecutive same-settings tracks fused into one
+static int master_device(mm_ctx *c, const mm_job *j, const void *d_in, void *d_out, mm_result *res) {
+    c->meters.clear();
+    Unit u;
+    u.J = j;
+    u.in = &d_in;
+    u.out = &d_out;
+    RET(unit_enqueue(c, u));
+    RET(unit_complete(c, u, res));
+    return j->meter_on ? chain_meter(c, j, d_out, 0, 1) : MM_OK;
+}
+
+// The units of a batch: one track, or consecutive same-settings tracks fused into one
 // timeline.  A run of such tracks is split into max(2, ceil(frames / cap)) units of
 // about equal length (cap MM_FUSE_MAX_FRAMES, default 150 M frames): two units in
 // flight on two streams overlap one unit's latency-bound tail with the other's
 // front (C3 8 x 3 min: 14.5 G frames/s as 2 units, 14.2 as 1, 13.7 as 4; C5 16 x 3
 // min at 96 kHz: 12.6 as 2, 12.3 as 4, 12.0 as 1, 11.0 unfused), and the cap
 // keeps a unit's compacted envelope arrays to a few GB.
-struct BatchUnit {
-    int first = 0, count = 1;
-    FusedPlan plan;
-};
-
-static std::vector<BatchUnit> batch_units(const mm_job *J, int n) {
+static std::vector<Unit> batch_units(const mm_job *J, const void *const *d_in, void *const *d_out, int n) {
     int64_t cap = 150000000;
     if (const char *e = getenv("MM_FUSE_MAX_FRAMES")) cap = std::max<int64_t>(1, atoll(e));
     const bool fuse = !getenv("MM_BATCH_STREAMS_ONLY");
@@ -1695,7 +1444,15 @@ static std::vector<BatchUnit> batch_units(const mm_job *J, int n) {
         const int64_t CF = (int64_t)J[i].tile * J[i].tiles_per_chunk;
         return (J[i].frames_proc + CF - 1) / CF * CF;
     };
-    std::vector<BatchUnit> units;
+    auto unit = [&](int first, int count) {
+        Unit u;
+        u.n = count;
+        u.J = J + first;
+        u.in = d_in + first;
+        u.out = d_out + first;
+        return u;
+    };
+    std::vector<Unit> units;
     for (int i = 0; i < n;) {
         int run = 1;  // maximal run of tracks fusable with track i
         int64_t total = padded(i);
@@ -1709,8 +1466,7 @@ static std::vector<BatchUnit> batch_units(const mm_job *J, int n) {
         int64_t acc = 0;
         int k = i;
         for (int q = 0; q < parts; ++q) {  // close unit q once it holds about (q+1)/parts of the run
-            BatchUnit u;
-            u.first = k;
+            const int first = k;
             if (q + 1 == parts) {
                 k = i + run;
             } else {
@@ -1718,13 +1474,9 @@ static std::vector<BatchUnit> batch_units(const mm_job *J, int n) {
                 acc += padded(k++);
                 while (k < i + run - (parts - q - 1) && acc + padded(k) / 2 <= goal) acc += padded(k++);
             }
-            u.count = k - u.first;
-            if (u.count > 1 && !fused_layout(J + u.first, u.count, &u.plan)) {  // over 2^31 frames: one by one
-                for (int t = u.first; t < k; ++t) {
-                    BatchUnit v;
-                    v.first = t;
-                    units.push_back(std::move(v));
-                }
+            Unit u = unit(first, k - first);
+            if (u.n > 1 && !unit_layout(&u)) {  // over 2^31 frames: one by one
+                for (int t = first; t < k; ++t) units.push_back(unit(t, 1));
                 continue;
             }
             units.push_back(std::move(u));
@@ -1805,7 +1557,7 @@ int mm_master_device(mm_ctx *c, const mm_job *j, const void *d_in, void *d_out, 
 }
 
 // A batch of independent tracks (BASELINE C3/C5 on one GPU), cut into units
-// (batch_units: same-settings runs fused into one timeline, else single tracks);
+// (batch_units: same-settings runs fused into one timeline, else units of one);
 // unit u runs on child context u % S (own stream and buffers, S = min(units,
 // MM_BATCH_STREAMS)), so up to S units are in flight at once and their
 // latency-bound kernels fill each other's idle SIMDs.  Units are completed in
@@ -1817,7 +1569,7 @@ int mm_master_batch(mm_ctx *c, int n, const mm_job *jobs, const void *const *d_i
     HIPCHK(c, hipSetDevice(c->device));
     for (int i = 0; i < n; ++i) RET(validate(c, &jobs[i]));
     c->meters.clear();
-    std::vector<BatchUnit> units = batch_units(jobs, n);
+    std::vector<Unit> units = batch_units(jobs, d_in, d_out, n);
     const int nu = (int)units.size();
     const int S = std::min(nu, MM_BATCH_STREAMS);
     while ((int)c->children.size() < S) {
@@ -1828,16 +1580,7 @@ int mm_master_batch(mm_ctx *c, int n, const mm_job *jobs, const void *const *d_i
     for (int s = 0; s < S; ++s) {
         c->children[s]->timing = c->timing;
     }
-    auto enqueue = [&](mm_ctx *k, BatchUnit &u) {
-        const int f = u.first;
-        if (u.count == 1) return enqueue_chain(k, &jobs[f], d_in[f], d_out[f]);
-        return fused_enqueue(k, u.count, jobs + f, d_in + f, d_out + f, u.plan);
-    };
-    auto complete = [&](mm_ctx *k, BatchUnit &u) {
-        const int f = u.first;
-        if (u.count == 1) return complete_chain(k, &jobs[f], d_out[f], res ? &res[f] : nullptr);
-        return fused_complete(k, u.count, jobs + f, d_out + f, res ? res + f : nullptr, u.plan);
-    };
+    auto complete = [&](mm_ctx *k, const Unit &u) { return unit_complete(k, u, res ? res + (u.J - jobs) : nullptr); };
     std::vector<int> cur((size_t)S, -1);
     int next = 0;
     auto fail = [&](mm_ctx *k) {
@@ -1847,7 +1590,7 @@ int mm_master_batch(mm_ctx *c, int n, const mm_job *jobs, const void *const *d_i
     };
     for (int s = 0; s < S && next < nu; ++s, ++next) {
         cur[s] = next;
-        if (enqueue(c->children[s], units[next]) != MM_OK) return fail(c->children[s]);
+        if (unit_enqueue(c->children[s], units[next]) != MM_OK) return fail(c->children[s]);
     }
     for (int done = 0; done < nu;) {
         for (int s = 0; s < S; ++s) {
@@ -1858,7 +1601,7 @@ int mm_master_batch(mm_ctx *c, int n, const mm_job *jobs, const void *const *d_i
             cur[s] = -1;
             if (next < nu) {
                 cur[s] = next;
-                if (enqueue(k, units[next]) != MM_OK) return fail(k);
+                if (unit_enqueue(k, units[next]) != MM_OK) return fail(k);
                 ++next;
             }
         }
@@ -1899,166 +1642,6 @@ int mm_master(mm_ctx *c, const mm_job *j, const void *in, void *out, mm_result *
     if (in_bytes) HIPCHK(c, hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, c->stream));
     RET(master_device(c, j, d_in, d_out, res));
     if (out_bytes) HIPCHK(c, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    resolve_events(c);
-    return MM_OK;
-}
-
-// ------------------------------------------------------------ WAV files
-// RIFF/WAVE codec of the file path (replaces pydub/ffmpeg decode, AME:43, and the
-// stdlib `wave` export, AME:98), mirroring mastering_amd/wavio.py: PCM16 or
-// IEEE float32 (WAVE_FORMAT_EXTENSIBLE resolved through its subformat), the
-// last fmt/data chunk wins, a data chunk running past the end of the file is
-// truncated to whole frames.
-static uint32_t le32(const unsigned char *p) { return p[0] | p[1] << 8 | p[2] << 16 | (uint32_t)p[3] << 24; }
-static uint16_t le16(const unsigned char *p) { return (uint16_t)(p[0] | p[1] << 8); }
-
-static int wav_parse(mm_ctx *c, FILE *f, const char *path, mm_wav_info *info) {
-    unsigned char h[40];
-    if (fseeko(f, 0, SEEK_END) != 0) return set_err(c, MM_ERR_ARG, "%s: cannot seek", path);
-    const int64_t fsize = (int64_t)ftello(f);
-    if (fseeko(f, 0, SEEK_SET) != 0 || fread(h, 1, 12, f) != 12 || memcmp(h, "RIFF", 4) || memcmp(h + 8, "WAVE", 4))
-        return set_err(c, MM_ERR_ARG, "%s: not a RIFF/WAVE file", path);
-    int64_t pos = 12, data_off = -1, data_size = 0;
-    int tag = -1, ch = 0, rate = 0, bits = 0;
-    while (pos + 8 <= fsize) {
-        if (fseeko(f, pos, SEEK_SET) != 0 || fread(h, 1, 8, f) != 8) break;
-        const int64_t size = le32(h + 4);
-        if (!memcmp(h, "fmt ", 4)) {
-            const size_t nb = (size_t)std::min<int64_t>(std::min<int64_t>(size, 40), fsize - pos - 8);
-            unsigned char b[40] = {0};
-            if (nb < 16 || fread(b, 1, nb, f) != nb) return set_err(c, MM_ERR_ARG, "%s: short fmt chunk", path);
-            tag = le16(b);
-            ch = le16(b + 2);
-            rate = (int)le32(b + 4);
-            bits = le16(b + 14);
-            if (tag == 0xFFFE && nb >= 26) tag = le16(b + 24);
-        } else if (!memcmp(h, "data", 4)) {
-            data_off = pos + 8;
-            data_size = std::min<int64_t>(size, fsize - data_off);
-        }
-        pos += 8 + size + (size & 1);
-    }
-    if (tag < 0 || data_off < 0) return set_err(c, MM_ERR_ARG, "%s: missing fmt or data chunk", path);
-    if (!((tag == 1 && bits == 16) || (tag == 3 && bits == 32)))
-        return set_err(c, MM_ERR_ARG, "%s: unsupported WAV format tag=%d bits=%d", path, tag, bits);
-    if (ch < 1 || rate < 1) return set_err(c, MM_ERR_ARG, "%s: bad fmt chunk (channels %d, rate %d)", path, ch, rate);
-    info->frames = data_size / (ch * bits / 8);
-    info->data_offset = data_off;
-    info->rate = rate;
-    info->channels = ch;
-    info->format = tag;
-    info->bits = bits;
-    return MM_OK;
-}
-
-int mm_wav_probe(mm_ctx *c, const char *path, mm_wav_info *info) {
-    if (!path || !info) return set_err(c, MM_ERR_ARG, "null argument");
-    FILE *f = fopen(path, "rb");
-    if (!f) return set_err(c, MM_ERR_ARG, "%s: cannot open", path);
-    const int rc = wav_parse(c, f, path, info);
-    fclose(f);
-    return rc;
-}
-
-constexpr size_t PIN_CHUNK = (size_t)8 << 20;  // bytes per staging buffer
-
-static int ensure_pinned(mm_ctx *c) {
-    for (int b = 0; b < 2; ++b) {
-        if (!c->pin[b]) HIPCHK(c, hipHostMalloc((void **)&c->pin[b], PIN_CHUNK, hipHostMallocDefault));
-        if (!c->pin_ev[b]) HIPCHK(c, hipEventCreateWithFlags(&c->pin_ev[b], hipEventDisableTiming));
-    }
-    return MM_OK;
-}
-
-namespace {
-struct FileCloser {
-    FILE *f;
-    ~FileCloser() {
-        if (f) fclose(f);
-    }
-};
-}  // namespace
-
-int mm_master_wav(mm_ctx *c, const mm_job *jin, const char *in_path, const char *out_path, mm_result *res) {
-    if (!c) return MM_ERR_ARG;
-    if (!jin || !in_path || !out_path) return set_err(c, MM_ERR_ARG, "null argument");
-    HIPCHK(c, hipSetDevice(c->device));
-    FileCloser in{fopen(in_path, "rb")};
-    if (!in.f) return set_err(c, MM_ERR_ARG, "%s: cannot open", in_path);
-    mm_wav_info wi;
-    RET(wav_parse(c, in.f, in_path, &wi));
-    mm_job j = *jin;
-    j.in_kind = wi.format == 1 ? MM_IN_I16 : MM_IN_F32;
-    if (j.frames_in != wi.frames || j.channels != wi.channels || j.rate != wi.rate)
-        return set_err(c, MM_ERR_ARG, "%s: job built for %lld frames x %d ch @ %d Hz, file has %lld x %d @ %d", in_path,
-                       (long long)j.frames_in, j.channels, j.rate, (long long)wi.frames, wi.channels, wi.rate);
-    RET(validate(c, &j));
-    const size_t in_bytes = (size_t)wi.frames * wi.channels * (wi.bits / 8);
-    const size_t out_bytes = (size_t)j.frames_proc * j.channels * (j.out_kind == MM_OUT_I16 ? 2 : 4);
-    if (out_bytes > 0xFFFFFFFFull - 36) return set_err(c, MM_ERR_ARG, "output larger than a RIFF file can hold");
-    char *d_in, *d_out;
-    RET(get_buf(c, "host_in", std::max<size_t>(in_bytes, 1), &d_in));
-    RET(get_buf(c, "host_out", std::max<size_t>(out_bytes, 1), &d_out));
-    RET(ensure_pinned(c));
-    // file -> pinned -> HBM: chunk k is read while chunk k-1 is in flight
-    if (fseeko(in.f, wi.data_offset, SEEK_SET) != 0) return set_err(c, MM_ERR_ARG, "%s: cannot seek", in_path);
-    size_t k = 0;
-    for (size_t off = 0; off < in_bytes; ++k) {
-        const int b = (int)(k & 1);
-        const size_t n = std::min(PIN_CHUNK, in_bytes - off);
-        if (k >= 2) HIPCHK(c, hipEventSynchronize(c->pin_ev[b]));
-        if (fread(c->pin[b], 1, n, in.f) != n) return set_err(c, MM_ERR_ARG, "%s: short read", in_path);
-        HIPCHK(c, hipMemcpyAsync(d_in + off, c->pin[b], n, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipEventRecord(c->pin_ev[b], c->stream));
-        off += n;
-    }
-    RET(master_device(c, &j, d_in, d_out, res));
-    // HBM -> pinned -> file: chunk k is written while chunk k+1 is copied back
-    FileCloser out{fopen(out_path, "wb")};
-    if (!out.f) return set_err(c, MM_ERR_ARG, "%s: cannot create", out_path);
-    const int tag = j.out_kind == MM_OUT_I16 ? 1 : 3, bits = j.out_kind == MM_OUT_I16 ? 16 : 32;
-    const int ba = j.channels * bits / 8;
-    unsigned char hdr[44];
-    auto put32 = [&](int at, uint32_t v) {
-        for (int i = 0; i < 4; ++i) hdr[at + i] = (unsigned char)(v >> (8 * i));
-    };
-    auto put16 = [&](int at, uint32_t v) {
-        hdr[at] = (unsigned char)v;
-        hdr[at + 1] = (unsigned char)(v >> 8);
-    };
-    memcpy(hdr, "RIFF", 4);
-    put32(4, (uint32_t)(36 + out_bytes));
-    memcpy(hdr + 8, "WAVEfmt ", 8);
-    put32(16, 16);
-    put16(20, tag);
-    put16(22, j.channels);
-    put32(24, j.rate);
-    put32(28, (uint32_t)j.rate * ba);
-    put16(32, ba);
-    put16(34, bits);
-    memcpy(hdr + 36, "data", 4);
-    put32(40, (uint32_t)out_bytes);
-    if (fwrite(hdr, 1, 44, out.f) != 44) return set_err(c, MM_ERR_ARG, "%s: write failed", out_path);
-    size_t prev_n = 0;
-    k = 0;
-    for (size_t off = 0; off < out_bytes; ++k) {
-        const int b = (int)(k & 1);
-        const size_t n = std::min(PIN_CHUNK, out_bytes - off);
-        HIPCHK(c, hipMemcpyAsync(c->pin[b], d_out + off, n, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipEventRecord(c->pin_ev[b], c->stream));
-        if (k >= 1) {
-            HIPCHK(c, hipEventSynchronize(c->pin_ev[b ^ 1]));
-            if (fwrite(c->pin[b ^ 1], 1, prev_n, out.f) != prev_n) return set_err(c, MM_ERR_ARG, "%s: write failed", out_path);
-        }
-        prev_n = n;
-        off += n;
-    }
-    if (k >= 1) {
-        const int b = (int)((k - 1) & 1);
-        HIPCHK(c, hipEventSynchronize(c->pin_ev[b]));
-        if (fwrite(c->pin[b], 1, prev_n, out.f) != prev_n) return set_err(c, MM_ERR_ARG, "%s: write failed", out_path);
-    }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     resolve_events(c);
     return MM_OK;
@@ -2116,7 +1699,7 @@ int mm_shard_energies_device(mm_ctx *c, const double *carry_in_host, int64_t n_g
     HIPCHK(c, hipMemsetAsync(d_full, 0, (size_t)n_global_segs * sizeof(double), c->stream));
     if (c->G > 0 && nl > 0) {
         double *seg;
-        RET(kweight_launch(c, carry_in_host, nullptr, &seg));
+        RET(kweight_staged(c, carry_in_host, nullptr, &seg));
         HIPCHK(c, hipMemcpyAsync(d_full + seg_offset, seg, (size_t)nl * sizeof(double), hipMemcpyDeviceToDevice,
                                  c->stream));
     }
@@ -2151,7 +1734,7 @@ int mm_gate_finalize_device(mm_ctx *c, const double *d_full, int64_t n_global_se
     ga.target = target;
     ga.out = gout;
     RET(gate_launch(c, ga, 1));
-    RET(finalize(c, 1.0, gout + 1, 1, d_out));
+    RET(finalize(c, &c->job, c->G, 0, 1.0, gout + 1, 1, d_out));
     // L and the gain finalize applied (gate.hip's device expression, not a host recomputation)
     HIPCHK(c, hipMemcpyAsync(loudness_gain_host, gout, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2181,7 +1764,7 @@ int mm_shard_loudness_device(mm_ctx *c, const double *carry_in_host, int64_t n_g
 
 int mm_finalize(mm_ctx *c, double gain_linear, int use_gain, void *d_out) {
     if (!c || !c->staged) return set_err(c, MM_ERR_STATE, "no staged job");
-    return finalize(c, gain_linear, nullptr, use_gain, d_out);
+    return finalize(c, &c->job, c->G, 0, gain_linear, nullptr, use_gain, d_out);
 }
 
 int mm_read_mix(mm_ctx *c, int16_t *host_mix) {
@@ -2230,86 +1813,10 @@ int mm_kernel_stats(mm_ctx *c, char *names, int names_cap, double *total_ms, int
     return n;
 }
 
-int mm_comm_unique_id(char id_out[128]) {
-    ncclUniqueId id;
-    if (ncclGetUniqueId(&id) != ncclSuccess) return MM_ERR_RCCL;
-    static_assert(sizeof(id) == 128, "nccl unique id size");
-    memcpy(id_out, &id, 128);
-    return MM_OK;
-}
-
-int mm_comm_init(mm_ctx *c, int rank, int nranks, const char id[128]) {
-    if (!c) return MM_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    ncclUniqueId uid;
-    memcpy(&uid, id, 128);
-    ncclResult_t r = ncclCommInitRank(&c->comm, nranks, uid, rank);
-    if (r != ncclSuccess) return set_err(c, MM_ERR_RCCL, "ncclCommInitRank: %s", ncclGetErrorString(r));
-    c->rank = rank;
-    c->nranks = nranks;
-    return MM_OK;
-}
-
-int mm_comm_destroy(mm_ctx *c) {
-    if (!c) return MM_ERR_ARG;
-    if (c->comm) ncclCommDestroy(c->comm);
-    c->comm = nullptr;
-    return MM_OK;
-}
-
-int mm_allreduce_sum_f64(mm_ctx *c, double *host_buf, int64_t n) {
-    if (!c || !c->comm) return set_err(c, MM_ERR_STATE, "communicator not initialised");
-    double *d;
-    RET(get_buf(c, "coll", (size_t)std::max<int64_t>(n, 1), &d));
-    HIPCHK(c, hipMemcpyAsync(d, host_buf, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    ncclResult_t r = ncclAllReduce(d, d, (size_t)n, ncclDouble, ncclSum, c->comm, c->stream);
-    if (r != ncclSuccess) return set_err(c, MM_ERR_RCCL, "ncclAllReduce: %s", ncclGetErrorString(r));
-    HIPCHK(c, hipMemcpyAsync(host_buf, d, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return MM_OK;
-}
-
-// Device-pointer collectives on the context's stream: no host
-// staging; the buffers must live on this context's device.  Synchronous on return.
-int mm_allreduce_sum_f64_device(mm_ctx *c, double *d_buf, int64_t n) {
-    if (!c) return MM_ERR_ARG;
-    if (n < 0 || (n > 0 && !d_buf)) return set_err(c, MM_ERR_ARG, "all-reduce: bad buffer");
-    if (!c->comm) return set_err(c, MM_ERR_STATE, "communicator not initialised");
-    if (n > 0) {
-        ncclResult_t r = ncclAllReduce(d_buf, d_buf, (size_t)n, ncclDouble, ncclSum, c->comm, c->stream);
-        if (r != ncclSuccess) return set_err(c, MM_ERR_RCCL, "ncclAllReduce: %s", ncclGetErrorString(r));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return MM_OK;
-}
-
-int mm_allgather_f64_device(mm_ctx *c, const double *d_in, double *d_out, int64_t n) {
-    if (!c) return MM_ERR_ARG;
-    if (n < 0 || (n > 0 && (!d_in || !d_out))) return set_err(c, MM_ERR_ARG, "all-gather: bad buffers");
-    if (!c->comm) return set_err(c, MM_ERR_STATE, "communicator not initialised");
-    if (n > 0) {
-        ncclResult_t r = ncclAllGather(d_in, d_out, (size_t)n, ncclDouble, c->comm, c->stream);
-        if (r != ncclSuccess) return set_err(c, MM_ERR_RCCL, "ncclAllGather: %s", ncclGetErrorString(r));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return MM_OK;
-}
-
-int mm_allgather_f64(mm_ctx *c, const double *host_in, double *host_out, int64_t n) {
-    if (!c || !c->comm) return set_err(c, MM_ERR_STATE, "communicator not initialised");
-    double *d;
-    RET(get_buf(c, "coll_ag", (size_t)std::max<int64_t>(n * (c->nranks + 1), 1), &d));
-    double *dout = d + n;
-    HIPCHK(c, hipMemcpyAsync(d, host_in, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    ncclResult_t r = ncclAllGather(d, dout, (size_t)n, ncclDouble, c->comm, c->stream);
-    if (r != ncclSuccess) return set_err(c, MM_ERR_RCCL, "ncclAllGather: %s", ncclGetErrorString(r));
-    HIPCHK(c, hipMemcpyAsync(host_out, dout, n * c->nranks * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return MM_OK;
-}
-
 }  // extern "C"
 
-// per-stage operators (AME:117-227 one at a time)
+// the WAV file path, the collectives, per-stage operators (AME:117-227 one at a time), metering
+#include "wav.hip"
+#include "comm.hip"
 #include "ops.hip"
 #include "meter.hip"

@@ -706,28 +706,24 @@ int loudness_device(mm_ctx *c, const mm_job *j, int dtype, const void *din, doub
     RET(get_buf(c, "op_part_seg", (size_t)G, &part_seg));
     RET(get_buf(c, "op_seg", (size_t)j->n_segs, &seg));
     RET(get_buf(c, "op_gate", 2, &gout));
-    mm_job saved = c->job;  // upload_geometry reads the context's job
-    c->job = *j;
-    const int rc = upload_geometry(c);
-    c->job = saved;
-    RET(rc);
-    KwArgs ka{};
-    ka.N_proc = N;
-    ka.G = G;
-    ka.T = T;
-    ka.Gt = G;
+    LineGeom lg;
+    RET(upload_geometry(c, j, &lg));
+    KwArgs ka = kw_args(c, j, N, G);
+    // the line is already mono f64 and tiled by the K-weighting tile itself (one lane per
+    // tile); tile_energy / seg_reduce read neither kw_args' mix nor its sos
+    ka.G = ka.Gt = G;
     ka.sub = 1;
     ka.ch = 1;
     ka.n_segs = j->n_segs;
-    ka.seg_bounds = c->seg_bounds_dev;
+    ka.seg_bounds = lg.bounds;
     ka.part = part;
     ka.part_seg = part_seg;
     RET(launch(c, "op_tile_energy", tile_energy_kernel, dim3(blocks_for(G, 256)), dim3(256), 0, ka, (const double *)tm));
     RET(launch(c, "op_seg_reduce", seg_reduce_kernel, dim3(blocks_for(j->n_segs, 4)), dim3(256), 0, ka, seg));
     GateArgs ga{};
     ga.n_blocks = j->n_blocks;
-    ga.blk_s0 = c->blk_s0;
-    ga.blk_s1 = c->blk_s1;
+    ga.blk_s0 = lg.s0;
+    ga.blk_s1 = lg.s1;
     ga.seg = seg;
     ga.scale = j->block_scale;
     ga.target = j->lufs_target;

@@ -229,6 +229,143 @@ def test_compressor_resume_path(oracle, monkeypatch, warmup):
     assert info["comp_active"] == info2["comp_active"] > 0, (info["comp_active"], info2["comp_active"])
 
 
+def _batch_on_fresh_context(pcms, rate, params, timing=False):
+    """Same-settings stereo f32 tracks through mm_master_batch on a fresh context:
+    (outputs, results, per-kernel launch counts when `timing`)."""
+    import torch
+
+    from mastering_amd import Job, master_batch, native
+    jobs = [Job(p.shape[0], rate, 2, params) for p in pcms]
+    xs = [torch.from_numpy(p.astype(np.float32) / 32768).cuda() for p in pcms]
+    outs = [torch.full((j.frames_proc, 2), 12345, dtype=torch.int16, device="cuda") for j in jobs]
+    torch.cuda.synchronize()
+    ctx = native.Context(0)
+    ctx.timing(timing)
+    res = master_batch(ctx, jobs, [x.data_ptr() for x in xs], [o.data_ptr() for o in outs])
+    launches = {name: n for name, (_, n) in ctx.kernel_stats().items()} if timing else None
+    ctx.close()
+    return [o.cpu().numpy() for o in outs], res, launches
+
+
+def test_fused_unit_resume_path(oracle, monkeypatch):
+    """The resume loop on a fused unit: with ONE queued fix-up sweep the 40 s track
+    (the input test_compressor_resume_path resumes on) and a 3.2 s track, fused into
+    one timeline, need more sweeps after the unit's sync; both stay exact against the
+    oracle, and the active band-frames kept on the host over the resume (rb_keep /
+    rb_finish) land on the right track.  (A run of two tracks is always cut into two
+    units of one, so a third 31 s track follows: the scheduler then fuses the first
+    two and runs the third as the second unit; two `eq` launches show that split.)"""
+    from mastering_amd.synth import pink_noise_pcm16
+    rate = 44100
+    pcms = [pink_noise_pcm16(40 * rate, rate, 2, 11), pink_noise_pcm16(int(3.2 * rate), rate, 2, 12),
+            pink_noise_pcm16(31 * rate, rate, 2, 13)]
+    monkeypatch.setenv("MM_COMP_SWEEPS", "1")
+    outs, res, launches = _batch_on_fresh_context(pcms, rate, P_HOT, timing=True)
+    assert launches["eq"] == 2, launches  # units {40 s, 3.2 s} and {31 s}
+    assert res[0].comp_iters == res[1].comp_iters >= 1, (res[0].comp_iters, res[1].comp_iters)
+    for t in range(3):
+        ref, L = oracle.master(pcms[t], rate, P_HOT, return_loudness=True)
+        _check(outs[t], {"loudness": res[t].loudness}, ref, L)
+    monkeypatch.delenv("MM_COMP_SWEEPS")
+    _, res2, _ = _batch_on_fresh_context(pcms, rate, P_HOT)
+    for t in (0, 1):
+        assert res[t].comp_active == res2[t].comp_active > 0, (t, res[t].comp_active, res2[t].comp_active)
+
+
+@pytest.mark.parametrize("channels,params,in_i16,seconds",
+                         [(2, P_HOT, False, 0.7), (2, P_HOT, False, 30.0), (2, P_HOT, False, 31.7),
+                          (1, P_FULL, True, 31.7), (2, dict(P_HOT, lufs=None), False, 31.7)],
+                         ids=["stereo_hot_0.7s", "stereo_hot_30s", "stereo_hot_31.7s", "mono_full_i16_31.7s",
+                              "stereo_hot_nolufs_31.7s"])
+def test_unit_of_one_equals_direct_call(oracle, channels, params, in_i16, seconds):
+    """A single track is a unit of one: mm_master_device and mm_master_batch with
+    n = 1, each on a fresh context, give the same bytes and the same result fields
+    (sub-chunk, one whole chunk, a ragged last chunk: where a padded timeline and the
+    track's own geometry would differ), and both are right against the oracle."""
+    import torch
+
+    from mastering_amd import Job, master_batch, master_device, native
+    from mastering_amd.synth import pink_noise_pcm16
+    rate = 44100
+    n = int(round(seconds * rate))
+    pcm = pink_noise_pcm16(n, rate, channels, 950)
+    x = torch.from_numpy(pcm.copy() if in_i16 else pcm.astype(np.float32) / 32768).cuda()
+
+    def run(batch):
+        job = Job(n, rate, channels, params)
+        job.job.in_kind = native.MM_IN_I16 if in_i16 else native.MM_IN_F32
+        out = torch.full((job.frames_proc, channels), 12345, dtype=torch.int16, device="cuda")
+        torch.cuda.synchronize()
+        ctx = native.Context(0)
+        if batch:
+            res = master_batch(ctx, [job], [x.data_ptr()], [out.data_ptr()])[0]
+        else:
+            res = master_device(ctx, job, x.data_ptr(), out.data_ptr(), native.MMResult())
+        ctx.close()
+        return out.cpu().numpy(), res
+
+    (a, ra), (b, rb) = run(False), run(True)
+    assert a.tobytes() == b.tobytes()
+    fields = ("loudness", "gain_linear", "comp_iters", "comp_active", "comp_walked", "comp_jumped")
+    np.testing.assert_array_equal([getattr(ra, f) for f in fields], [getattr(rb, f) for f in fields])  # (NaN == NaN)
+    ref, L = oracle.master(pcm, rate, params, return_loudness=True)
+    for out, r in ((a, ra), (b, rb)):
+        _check(out.reshape(ref.shape), {"loudness": r.loudness}, ref, L)
+
+
+def test_fused_unit_without_multiband_after_one_with(oracle):
+    """A fused unit with the compressor off reports no active band-frames: the
+    readback block then holds no per-chunk counts, and what an earlier multiband
+    unit on the same contexts left there (or what lies past it: 20 chunks per unit
+    here) is not read.  Every track against the oracle."""
+    import torch
+
+    from mastering_amd import Job, master_batch, native
+    from mastering_amd.synth import pink_noise_pcm16
+    rate = 44100
+    plain = dict(P_FULL, multiband=False)
+    pcms = [pink_noise_pcm16(int(s * rate), rate, 2, 960 + t) for t, s in enumerate((3.2, 31.7, 0.7, 30.0))]
+    xs = [torch.from_numpy(p.astype(np.float32) / 32768).cuda() for p in pcms]
+    ctx = native.Context(0)
+
+    def run(params):
+        # the plain batch repeats the tracks: two units of 20 chunks, more than their readback block spans
+        k = 1 if params["multiband"] else 8
+        jobs = [Job(p.shape[0], rate, 2, params) for p in pcms] * k
+        outs = [torch.full((j.frames_proc, 2), 12345, dtype=torch.int16, device="cuda") for j in jobs]
+        torch.cuda.synchronize()
+        res = master_batch(ctx, jobs, [x.data_ptr() for x in xs] * k, [o.data_ptr() for o in outs])
+        return [o.cpu().numpy() for o in outs], res
+
+    _, res = run(P_FULL)
+    assert sum(r.comp_active for r in res) > 0  # (the contexts now hold a multiband unit's counts)
+    outs, res = run(plain)
+    assert [r.comp_active for r in res] == [0] * len(res), [r.comp_active for r in res]
+    assert [(r.comp_walked, r.comp_jumped) for r in res] == [(0, 0)] * len(res)
+    for t, pcm in enumerate(pcms):
+        ref, L = oracle.master(pcm, rate, plain, return_loudness=True)
+        for rep in range(8):
+            _check(outs[rep * len(pcms) + t], {"loudness": res[rep * len(pcms) + t].loudness}, ref, L)
+    ctx.close()
+
+
+def test_fused_unit_kweight_sub_tiles(oracle, monkeypatch):
+    """MM_KW_SUB=3 (three K-weighting lanes per 225-frame tile) on a fused unit: the
+    K-weighting stage then has more look-back blocks than the stereo chunk stages, and
+    the control block's regions are sized for them (the unit tells stage_front its
+    K-weighting block count).  Ragged stereo tracks against the oracle."""
+    from mastering_amd import design
+    from mastering_amd.synth import pink_noise_pcm16
+    rate = 44100
+    monkeypatch.setenv("MM_KW_SUB", "3")
+    assert design.kweight_sub(design.choose_tile(30 * rate)) == 3
+    pcms = [pink_noise_pcm16(int(s * rate), rate, 2, 900 + t) for t, s in enumerate((3.2, 31.7, 0.7))]
+    outs, res, _ = _batch_on_fresh_context(pcms, rate, P_FULL)
+    for t, pcm in enumerate(pcms):
+        ref, L = oracle.master(pcm, rate, P_FULL, return_loudness=True)
+        _check(outs[t], {"loudness": res[t].loudness}, ref, L)
+
+
 @pytest.mark.parametrize("channels,params,in_i16,rate", [(2, P_FULL, False, 44100), (1, P_HOT, True, 44100),
                                                           (2, dict(P_FULL, lufs=None), False, 44100),
                                                           (2, P_HOT, True, 48000)],
