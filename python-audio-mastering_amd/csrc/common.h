@@ -76,58 +76,6 @@ __device__ __forceinline__ void stream(int len, LD &&ld, PROC &&proc) {
             if (k * B + j < rem) proc(buf[k][j]);
 }
 
-// Two-stage variant for dependent gathers: ld1(i) is streamed NB blocks ahead,
-// ld2(v1) (e.g. a table lookup indexed by the loaded value) is issued one block
-// ahead of its use, so both latencies hide behind the consumer proc(v1, v2).
-// ld2 must be safe for any v1 that ld1 can return.
-template <int B, int NB, typename V1, typename V2, typename LD1, typename LD2, typename PROC>
-__device__ __forceinline__ void stream2(int len, LD1 &&ld1, LD2 &&ld2, PROC &&proc) {
-    constexpr int R = B * NB;
-    if (len <= 0) return;
-    V1 a[NB][B];
-    V2 m[B];
-#pragma unroll
-    for (int k = 0; k < NB; ++k) {
-#pragma unroll
-        for (int j = 0; j < B; ++j) a[k][j] = ld1(k * B + j);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int j = 0; j < B; ++j) m[j] = ld2(a[0][j]);
-    __builtin_amdgcn_sched_barrier(0);
-    const int nfull = len / R;
-    int base = 0;
-    for (int r = 0; r < nfull; ++r, base += R) {
-#pragma unroll
-        for (int k = 0; k < NB; ++k) {
-            V2 mn[B];
-#pragma unroll
-            for (int j = 0; j < B; ++j) mn[j] = ld2(a[(k + 1) % NB][j]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int j = 0; j < B; ++j) proc(a[k][j], m[j]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int j = 0; j < B; ++j) a[k][j] = ld1(base + R + k * B + j);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int j = 0; j < B; ++j) m[j] = mn[j];
-        }
-    }
-    const int rem = len - base;
-#pragma unroll
-    for (int k = 0; k < NB; ++k) {
-        V2 mn[B];
-#pragma unroll
-        for (int j = 0; j < B; ++j) mn[j] = ld2(a[(k + 1) % NB][j]);
-#pragma unroll
-        for (int j = 0; j < B; ++j)
-            if (k * B + j < rem) proc(a[k][j], m[j]);
-#pragma unroll
-        for (int j = 0; j < B; ++j) m[j] = mn[j];
-    }
-}
-
 struct SatArgs {
     float keep, mix, drive;
     int on;
@@ -169,9 +117,9 @@ struct CompArgs {
     const double *E[3], *tail[3];  // per tile: sum of L^2+R^2, and over its last look % T frames
     int32_t *cnt[3];           // per tile: active frames
     double *mmax[3];           // per tile: largest M
-    double *ced[3];            // per tile: (max,+) release summary {c, D} (double2; comp_rms)
+    double *ced[3];            // per tile: (max,+) release summary {c, D} (double2; comp_rms_t)
     int32_t *total[3];         // per chunk: active frames (statistics)
-    int32_t *cbtot[3];         // per column block: active tiles (comp_rms; zeroed per chain)
+    int32_t *cbtot[3];         // per column block: active tiles (comp_rms_t; zeroed per chain)
     int32_t *rank[3];          // per tile: active tiles before it in its chunk (comp_describe)
     int32_t *nact[3];          // per chunk: active tiles
     // per active tile at compact index ci = chunk * K + rank:
@@ -189,8 +137,7 @@ struct CompArgs {
     int32_t *se0[3];           // per super-tile: binade of its largest M (SJ_NONE: no record)
     uint32_t stamp;            // this sweep's stamp (> every earlier one of the chain)
     int heads;                 // 0: Jacobi sweep (every stale super-tile walks); 1: run heads only
-    int jacobi_stop;           // a Jacobi walker stops at its super-tile's end (MM_JACOBI_STOP=1: experiments)
-    int e_tiles;               // active tiles of a pass-0 guess's (max,+) fold (MM_E_TILES; E_TILES)
+    int e_tiles;               // active tiles of a pass-0 guess's (max,+) fold (E_TILES)
     unsigned int *changed;
     unsigned long long *walked;  // [0] frames re-walked, [1] frames jumped by the fix-up sweeps (statistics)
     uint32_t *trace;           // diagnostics (MM_FIX_TRACE): per sweep, band, super-tile {10 ns ticks, walked, jumped, visited}

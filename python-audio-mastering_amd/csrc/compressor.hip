@@ -23,7 +23,7 @@
 //                bytes per step), plus per tile its active count, largest M and
 //                (max,+) release summary `ce`, per column block its active-tile count.
 //                Consumers gate every read of M on the tile's count: rows of tiles
-//                with no active frame are never stored (comp_rms's quiet-tile skip).
+//                with no active frame are never stored (the quiet-tile skip).
 //  2. comp_describe per column block: ranks and lists the chunk's active tiles in
 //                compact order and records per active tile the exact effect of its T
 //                release steps on any state of the EIGHT binades above its largest M
@@ -50,15 +50,10 @@
 
 namespace mm {
 
-// x^2 + y^2 of one frame: at most 2 * 32768^2 = 2^31, exact in uint32
 template <bool V>
 struct BoolTag {
     static constexpr bool value = V;
 };
-
-__device__ __forceinline__ uint32_t frame_energy(short2 v) {
-    return (uint32_t)((int32_t)v.x * v.x) + (uint32_t)((int32_t)v.y * v.y);
-}
 
 // correctly rounded m / d given rd = RN(1/d) (Markstein; tests/test_oracle.py)
 __device__ __forceinline__ double div_cr(double m, double d, double rd) {
@@ -70,7 +65,7 @@ __device__ __forceinline__ double div_cr(double m, double d, double rd) {
 #ifndef MM_RMS_NB
 #define MM_RMS_NB 3
 #endif
-constexpr int RMS_B = 8;  // frames per load block of comp_rms
+constexpr int RMS_B = 8;  // frames per load block of comp_rms_t
 constexpr int RMS_TPS = 4;  // tiles per super-tile comp_rms_t is written for (its four waves)
 
 // Super-tile-major M plane of a band: frame n of tile g — the k-th tile of
@@ -98,17 +93,13 @@ __device__ __forceinline__ double *chunk_plane(const CompArgs &a, int b, int64_t
     return a.Ms[b] + c * a.chunk_elems;
 }
 
-// 1. rms and M per frame.  grid: (GS * TPS / 256, 3 bands) of 256-thread blocks,
-// one wave per (column block, position k): wave v handles tile k = v % TPS of the 64
-// super-tiles (columns) of column block v / TPS, lane l the one of column 64 (v /
-// TPS) + l.  SPC is a multiple of 64, so a column block lies in one chunk and the
-// wave's 64 lanes store row k*T + n of 64 consecutive columns: every M store is
-// one 512-byte run (round 3 mapped lanes to consecutive tiles: 8 runs of 64 B per
-// store).  The band loads are TPS tiles apart across the lanes (the block's TPS
-// waves share those lines).  The window [max(chunk0, f-look), f) slides one frame
-// per step: + frame f-1 (this lane's own previous frame), - frame f-1-look (up to
-// ~4 tiles back: another tile's data).  The window sum is an exact integer held in
-// a double.  M = lut[r] is gathered ONCE here (a block of RMS_B frames' gathers is
+// 1. rms and M per frame (comp_rms_t_kernel below).  grid: (GS / 64, 3 bands) of
+// 256-thread blocks, one per column block: 64 super-tiles (columns) x TPS = 4 tiles,
+// 256 consecutive tiles of one chunk (SPC is a multiple of 64, so a column block
+// lies in one chunk).  The window [max(chunk0, f-look), f) slides one frame per
+// step: + frame f-1 (this lane's own previous frame), - frame f-1-look (up to ~4
+// tiles back: another tile's data).  The window sum is an exact integer held in a
+// double.  M = lut[r] is gathered ONCE here (a block of RMS_B frames' gathers is
 // stored one block later) and written to the super-tile-major plane that the
 // walkers and comp_apply read; rows past the end of a partial last tile get M = 0
 // (identity steps).  Also the tile's active count and largest M (the table is
@@ -117,7 +108,7 @@ __device__ __forceinline__ double *chunk_plane(const CompArgs &a, int b, int64_t
 #ifndef MM_RMS_MINB
 #define MM_RMS_MINB 1
 #endif
-// rms_exact with one correction: the f32 estimate of sqrt(S * (1/n)) taken with
+// The exact integer rms isqrt(S div n) with one correction: the f32 estimate of sqrt(S * (1/n)) taken with
 // the reciprocal scaled by (1 - 2^-18) (inv_b) lies in sqrt(S/n) * [1 - 2^-19 -
 // 2^-22, 1 - 2^-19 + 2^-22] (rcp, product and sqrt each within a few ulp), so
 // below sqrt(S/n) and above it minus 0.07 at r <= 32768: its truncation is r or
@@ -145,17 +136,17 @@ __device__ __forceinline__ double vmax(double x, double y) {
     return r;
 }
 
-// ---- comp_rms with the table gathers and M stores transposed through LDS -------
-// (TPS == 4: a workgroup = one column block = 256 consecutive tiles of a chunk.)
-// The per-frame rms runs as in comp_rms (lane = tile, coalesced band rows); per
-// block of RMS_B frames three phases exchange through LDS:
+// ---- the table gathers and M stores transposed through LDS --------------------
+// The per-frame rms runs with lane = tile (coalesced band rows); per block of
+// RMS_B frames three phases exchange through LDS:
 //   A  lane = tile: the exact rms r of RMS_B frames -> R[j][tile];
 //   B  each wave gathers M = lut[r] for its own 64 tiles x RMS_B frames with lanes
 //      over (8 tiles x 8 CONSECUTIVE frames): a lane group of one tile reads
 //      nearly the same r, so a gather touches ~8 table lines instead of 64 (the
-//      round-5 profile had comp_rms TA-bound: L1 address stalls 55 % of its time);
+//      round-5 profile had this kernel TA-bound: L1 address stalls 55 % of its time);
 //   C  lane = column, wave = tile position: M rows of 64 consecutive columns are
-//      stored as one 512-byte run, and the lane keeps its tile's (max,+) release
+//      stored as one 512-byte run (round 3 mapped lanes to consecutive tiles: 8 runs
+//      of 64 B per store), and the lane keeps its tile's (max,+) release
 //      summary (frames in order).
 // Gathers of block q are in flight while block q+1's rms runs; one workgroup
 // barrier per block (double-buffered R and M stages).
@@ -254,7 +245,6 @@ __global__ void __launch_bounds__(256, MM_RMS_MINB) comp_rms_t_kernel(CompArgs a
     const int tlC = lane * 4 + w;
     const int64_t jtC = jt0 + tlC, gC = cc * a.K + jtC;
     const bool vC = jtC < a.K && gC < a.G;
-    const int lenC = vC ? (int)min((int64_t)T, a.N_proc - gC * T) : 0;
     double *Mo = chunk_plane(a, b, cc);
     uint32_t eC = col_elem(a, cc * a.SPC + jtC / 4) + (uint32_t)(w * a.TP) * 64u;  // row w*TP of its column
     double ce = 0.0, De = 0.0;
@@ -272,11 +262,7 @@ __global__ void __launch_bounds__(256, MM_RMS_MINB) comp_rms_t_kernel(CompArgs a
 #pragma unroll
         for (int r8 = 0; r8 < B; ++r8) {
             const int tl = w * 64 + r8 * 8 + (lane >> 3);
-#ifdef MM_RMS_NOGATHER  // (ablation builds: timing only)
-            gm[r8] = (double)Rs[q & 1][jB][tl];
-#else
             gm[r8] = lut[Rs[q & 1][jB][tl]];
-#endif
         }
     };
     auto finish_gathers = [&](int q) __attribute__((always_inline)) {
@@ -302,10 +288,8 @@ __global__ void __launch_bounds__(256, MM_RMS_MINB) comp_rms_t_kernel(CompArgs a
         for (int j = 0; j < B; ++j) m[j] = Mst[q & 1][j][slotC];
 #pragma unroll
         for (int j = 0; j < B; ++j) {
-#ifndef MM_RMS_NOSTORE  // (ablation builds: timing only)
             const uint32_t off = (vC && j < nv) ? (eC + (uint32_t)j * 64u) * 8u : DROP;
             __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, m[j]), Mr, off, 0, 0);
-#endif
         }
         eC += (uint32_t)nv * 64u;
 #pragma unroll
@@ -359,7 +343,6 @@ __global__ void __launch_bounds__(256, MM_RMS_MINB) comp_rms_t_kernel(CompArgs a
     if (vC)
         for (int i = T; i < a.TP; ++i, eC += 64u) Mo[eC] = 0.0;
     if (vC) reinterpret_cast<double2 *>(a.ced[b])[gC] = make_double2(ce, De);
-    (void)lenC;
     if (vA) {
         a.cnt[b][gA] = active;
         a.mmax[b][gA] = lut[rmx];
@@ -393,16 +376,8 @@ __device__ __forceinline__ int binade(double x) { return (int)((uint64_t)__doubl
 //   if rms > thr and att <= M: att = min(att + M/A, M)
 //   else:                      att = max(att - M/R, 0)
 // M == 0 (rms <= thr) leaves att unchanged (inc = dec = 0); M != 0 implies
-// rms > thr, so the rms test folds away.  min/max are v_min_f64/v_max_f64
-// (equal operands and signed zeros give the same observable att); the
-// divisions are correctly rounded and off the att chain.
-__device__ __forceinline__ double comp_step(double att, double M, const BandStep &bs) {
-    const double inc = div_cr(M, bs.A, bs.rA);
-    const double dec = div_cr(M, bs.R, bs.rR);
-    const double up = fmin(att + inc, M);
-    const double dn = fmax(att - dec, 0.0);
-    return att <= M ? up : dn;
-}
+// rms > thr, so the rms test folds away.  The divisions are correctly rounded
+// (div_cr) and off the att chain: lean_step below takes them precomputed.
 
 // v_min_f64 without the operand canonicalisation fmin adds
 // (operands here are never NaN; equal operands and signed zeros give the same
@@ -668,10 +643,11 @@ struct Describer {
 
 // 2. links + describers, ONE launch.  grid: (column blocks, 3), a block of
 // 64 * TPS threads = one column block (64 super-tiles x TPS tiles = 64 TPS
-// consecutive tiles of one chunk), lanes mapped to tiles as in comp_rms (wave k:
-// tile position k of the 64 columns), so the describers' M loads are 512-byte runs.
+// consecutive tiles of one chunk), lanes mapped to tiles as in comp_rms_t's phase
+// C (wave k: tile position k of the 64 columns), so the describers' M loads are
+// 512-byte runs.
 //  * links: ranks the chunk's active tiles (rank[g] = active tiles before g in its
-//    chunk: the counts comp_rms left per column block for the blocks before this
+//    chunk: the counts comp_rms_t left per column block for the blocks before this
 //    one, plus a scan over the block's tiles in tile order), lists them at compact
 //    index ci = chunk * K + rank (tl = the tile, mmaxc = its largest M, cedc = its
 //    (max,+) summary) and counts them (nact[c], by the chunk's last block);
@@ -700,7 +676,7 @@ __global__ void __launch_bounds__(64 * DESC_MAX_TPS) comp_describe_kernel(CompAr
     const bool live = valid && a.cnt[b][g] != 0;
     // tile order within the block: tile jt = (column block base) + l * TPS + kc
     flag[l * TPS + kc] = live ? 1 : 0;
-    if (threadIdx.x < 64) {  // active tiles of the chunk's earlier column blocks (comp_rms counts), wave 0
+    if (threadIdx.x < 64) {  // active tiles of the chunk's earlier column blocks (comp_rms_t counts), wave 0
         int32_t acc = 0;
         const int32_t *ct = a.cbtot[b] + cc * (a.SPC >> 6);
         for (int64_t q = threadIdx.x; q < cbl; q += 64) acc += ct[q];
@@ -817,7 +793,7 @@ __device__ void compose_super(const CompArgs &a, int b, int64_t s, int64_t ci0) 
 // The pass-0 guess across one tile: the exit of the per-frame (max,+) walk E <-
 // max(M, E - M/R) from entry E, bit for bit (tests/test_envelope_jumps.py) when the
 // tile's release-jump record covers E: E = 0 or below the tile's largest M clamps
-// in the tile and ends on ct (the walk from 0, comp_rms); above it the pure release
+// in the tile and ends on ct (the walk from 0, comp_rms_t); above it the pure release
 // E - q (exact while it stays in E's binade: the offsets do not depend on M), max'ed
 // with ct (a walk that clamps ends on ct's values: the steps are monotone).  An
 // uncovered E takes E - Dt (a guess; exactness never depends on it).
@@ -844,7 +820,7 @@ __device__ __forceinline__ double e_fold_tile(double E, double ct, double Dt, do
 // active tiles before it (with `warmup` = 1, before a walk of the previous
 // super-tile).  Exactness never depends on the guess (the fix-up sweeps).
 constexpr int PASS0_BLOCK = 64, P0_MAXL = 64;  // lanes; tiles per walker (warm-up included)
-constexpr int E_TILES = 32;  // active tiles folded into a pass-0 guess by default (~4000 frames of release history)
+constexpr int E_TILES = 32;  // active tiles folded into a pass-0 guess (~4000 frames of release history)
 
 constexpr int EW_MAX = 64 * SJ_TPS + 64;  // tiles a pass-0 block stages for its guesses (TPS <= 4, window <= 64)
 constexpr int P0_SMEM = (EW_MAX * (3 + 2 * JF) * 8 > P0_MAXL * PASS0_BLOCK * 4) ? EW_MAX * (3 + 2 * JF) * 8
@@ -1081,9 +1057,8 @@ __global__ void __launch_bounds__(64) comp_fix_kernel(CompArgs a, const unsigned
         if (st.last) return false;  // the chunk's last super-tile
         // continue into the successor if it could be claimed (else its owner read an
         // older end of cur: it is stale next sweep, which this walk's own `changed`
-        // flag queues); with jacobi_stop the Jacobi sweep's walkers stop here instead
-        // (C2: 5 sweeps, fix 0.295 ms against 3 and 0.269 continuing)
-        if (!a.heads && a.jacobi_stop) return false;
+        // flag queues).  (Stopping the Jacobi sweep's walkers here instead measured
+        // worse on C2: 5 sweeps, fix 0.295 ms against 3 and 0.269 continuing.)
         if (!a.heads) nx_claimed = comp_claim(a, b, cur + 1);
         if (!nx_claimed) return false;
         ++cur;
@@ -1281,7 +1256,7 @@ __device__ __forceinline__ double exp10_tab(double y, const double2 *tab) {
 
 // Verification of the compressor's two hand-made elementary functions on the
 // device (mm_check_compressor_math, tests/test_compressor_math.py): what 0: out =
-// exp10_tab(a) (10^a); what 1: out = rms_exact1(a, b) with comp_rms's biased
+// exp10_tab(a) (10^a); what 1: out = rms_exact1(a, b) with comp_rms_t's biased
 // reciprocal (isqrt(floor(a / b)) for integers a < 2^53, b >= 1).
 __global__ void __launch_bounds__(256) comp_math_kernel(int what, const double *xa, const double *xb, int64_t n,
                                                        double *out) {
@@ -1296,11 +1271,6 @@ __global__ void __launch_bounds__(256) comp_math_kernel(int what, const double *
 
 #ifndef MM_APPLY_MINB
 #define MM_APPLY_MINB 1
-#endif
-#ifdef MM_APPLY_OCML  // (A/B builds: OCML's exp10)
-#define MM_GAIN(att) exp10(neg_div20(att))
-#else
-#define MM_GAIN(att) exp10_tab(neg_div20(att), etab)
 #endif
 __global__ void __launch_bounds__(192, MM_APPLY_MINB) comp_apply_kernel(CompArgs a) {
     constexpr int S = APPLY_STEP;
@@ -1342,16 +1312,16 @@ __global__ void __launch_bounds__(192, MM_APPLY_MINB) comp_apply_kernel(CompArgs
     // M loads or steps
     const bool quiet = __all(!valid || a.cnt[b][g] == 0);
     if (quiet) {
-        gain = MM_GAIN(att);
+        gain = exp10_tab(neg_div20(att), etab);
         gain_att = att;
     }
     const uint32_t G32 = (uint32_t)G, gl = valid ? (uint32_t)g : 0u;
     const uint32_t last = (uint32_t)max(len - 1, 0);
     const short2 *Xl = X + gl;       // this lane's tile, row 0
     const double *Ml = Mp + e0;      // this lane's column, its tile's row 0
-    // rows past the tile's frames hold M = 0 (comp_rms): identity steps whose
+    // rows past the tile's frames hold M = 0 (comp_rms_t): identity steps whose
     // output is unused; samples are clamped to the tile
-    // a tile without active frames has M = 0 throughout: comp_rms may not have
+    // a tile without active frames has M = 0 throughout: comp_rms_t may not have
     // stored its rows (quiet tiles), so it takes 0 instead of loading them
     const bool act = valid && a.cnt[b][g] != 0;
     // the overlay's fast path: the block's 64 tiles all whole (every block but a
@@ -1389,11 +1359,7 @@ __global__ void __launch_bounds__(192, MM_APPLY_MINB) comp_apply_kernel(CompArgs
             } else {
 #pragma unroll
                 for (int j = 0; j < S; ++j)
-#ifdef MM_APPLY_NOEXP  // timing experiment only (wrong gains)
-                    gj[j] = 1.0 + neg_div20(at[j]);
-#else
-                    gj[j] = MM_GAIN(at[j]);  // db_to_float(-att); exactly 1 at att == 0
-#endif
+                    gj[j] = exp10_tab(neg_div20(at[j]), etab);  // db_to_float(-att); exactly 1 at att == 0
                 gain = gj[S - 1];
                 gain_att = at[S - 1];
             }

@@ -14,8 +14,6 @@
 // segment energies (f64) on the time-sharded and per-stage paths (gate_blocks).
 // The reductions over blocks are tree-ordered (the result differs from numpy's
 // pairwise mean in the last bits only: ~1e-16 of the gain).
-#include <type_traits>
-
 #include "common.h"
 
 namespace mm {
@@ -82,16 +80,12 @@ __host__ __device__ constexpr int kb_lds_bytes(int stage_floats, int nvals, int 
 // x per + w/8, + grid/8, ... of its XCD's contiguous range (neighbouring blocks'
 // windows overlap 3/4: the re-reads hit that XCD's L2).  The blocks' chunks
 // (8192 frames, numpy's buffers) form one stream over all the workgroup's blocks
-// with KB_RING chunks' 16-byte loads in flight (a ring of register buffers).  Per
-// chunk the tiles' padded runs are copied to LDS as they lie in memory (a plain
-// 16-byte copy); eight lanes per leaf run numpy's eight accumulators, walking the
-// frames' word addresses; per block the
-// program's levels combine the leaves in numpy's order.  A block's program (one
-// per block length) stays in LDS while the next block has the same.
-#ifndef MM_KB_RING
-#define MM_KB_RING 1
-#endif
-constexpr int KB_RING = MM_KB_RING;  // chunks in flight per workgroup (1-3)
+// with one chunk's 16-byte loads in flight in a register buffer (the next chunk
+// loads while this one is summed).  Per chunk the tiles' padded runs are copied to
+// LDS as they lie in memory (a plain 16-byte copy); eight lanes per leaf run numpy's
+// eight accumulators, walking the frames' word addresses; per block the program's
+// levels combine the leaves in numpy's order.  A block's program (one per block
+// length) stays in LDS while the next block has the same.
 __global__ void __launch_bounds__(KB_THREADS) kw_blocks_kernel(KbArgs a) {
     extern __shared__ __attribute__((aligned(16))) float kb_smem[];
     __shared__ int kb_prog_cur;
@@ -108,8 +102,8 @@ __global__ void __launch_bounds__(KB_THREADS) kw_blocks_kernel(KbArgs a) {
     const float4 *sq4 = reinterpret_cast<const float4 *>(a.sq);
     float4 *el4 = reinterpret_cast<float4 *>(el);
     if (tid == 0) kb_prog_cur = -1;
-    float4 buf[KB_RING][KB_LD];
-    int g_nld[KB_RING], g_fb[KB_RING];  // per buffer: quads loaded; the chunk's first frame's row in its tile
+    float4 buf[KB_LD];
+    int g_nld, g_fb;  // of the buffered chunk: quads loaded; its first frame's row in its tile
     // the stream's next chunk: (block lj, chunk lc)
     int64_t lj = jb;
     int lc = 0;
@@ -122,18 +116,17 @@ __global__ void __launch_bounds__(KB_THREADS) kw_blocks_kernel(KbArgs a) {
     // the chunk's padded tile runs [tA, tB] land in LDS as they lie in memory: quad
     // L of the run is LDS quad L (a plain 16-byte copy); frame u of the run (u = row
     // + T * tile) is LDS word (u / T) TP + u % T
-    auto issue = [&](auto B) __attribute__((always_inline)) {  // the stream's next chunk into buffer B
-        constexpr int b = decltype(B)::value;
+    auto issue = [&]() __attribute__((always_inline)) {  // the stream's next chunk into the buffer
         if (lj >= je) return;
         const int m = min(KB_CHUNK, ln - lc * KB_CHUNK);
         const int64_t F0 = lF0 + (int64_t)lc * KB_CHUNK;
         const int64_t tA = F0 / T;
         const int nld = (int)((F0 + m - 1) / T - tA + 1) * Q4;
-        g_nld[b] = nld;
-        g_fb[b] = (int)(F0 - tA * T);
+        g_nld = nld;
+        g_fb = (int)(F0 - tA * T);
         const float4 *base = sq4 + tA * Q4;
 #pragma unroll
-        for (int r = 0; r < KB_LD; ++r) buf[b][r] = base[min(tid + r * KB_THREADS, nld - 1)];
+        for (int r = 0; r < KB_LD; ++r) buf[r] = base[min(tid + r * KB_THREADS, nld - 1)];
         if (++lc * KB_CHUNK >= ln) {  // advance (blocks without frames have no chunks)
             lc = 0;
             for (lj += nslot; lj < je; lj += nslot) {
@@ -143,19 +136,15 @@ __global__ void __launch_bounds__(KB_THREADS) kw_blocks_kernel(KbArgs a) {
             }
         }
     };
-    auto copy = [&](auto B) __attribute__((always_inline)) {  // buffer B -> LDS
-        constexpr int b = decltype(B)::value;
+    auto copy = [&]() __attribute__((always_inline)) {  // the buffer -> LDS
 #pragma unroll
         for (int r = 0; r < KB_LD; ++r) {
-            const float4 v = buf[b][r];
-            float *d = el + 4 * min(tid + r * KB_THREADS, g_nld[b] - 1);
-            if (tid + r * KB_THREADS < g_nld[b]) d[0] = v.x, d[1] = v.y, d[2] = v.z, d[3] = v.w;
+            const float4 v = buf[r];
+            float *d = el + 4 * min(tid + r * KB_THREADS, g_nld - 1);
+            if (tid + r * KB_THREADS < g_nld) d[0] = v.x, d[1] = v.y, d[2] = v.z, d[3] = v.w;
         }
     };
-    issue(std::integral_constant<int, 0>{});
-    if constexpr (KB_RING > 1) issue(std::integral_constant<int, 1 % KB_RING>{});
-    if constexpr (KB_RING > 2) issue(std::integral_constant<int, 2 % KB_RING>{});
-    int ring = 0;  // the buffer holding the next chunk to sum
+    issue();
     int vb = 0;    // val double buffer: the levels of block j read val[vb] while block j+1 fills the other
     for (int64_t j = jb; j < je; j += nslot, vb ^= 1) {
         const int pj = a.blk_prog[j];
@@ -173,28 +162,16 @@ __global__ void __launch_bounds__(KB_THREADS) kw_blocks_kernel(KbArgs a) {
         float *V = val + vb * ((a.nvals + 1) / 2);  // (nvals counts both buffers)
         for (int c = 0; c < nch; ++c) {
             const int l0 = chunk_leaf[c], l1 = chunk_leaf[c + 1];
-            int fb;
-#ifndef MM_KB_NOCOPY  // (ablation builds: timing only)
-            if (KB_RING == 1 || ring == 0) copy(std::integral_constant<int, 0>{}), fb = g_fb[0];
-            else if (KB_RING == 2 || ring == 1) copy(std::integral_constant<int, 1 % KB_RING>{}), fb = g_fb[1 % KB_RING];
-            else copy(std::integral_constant<int, 2 % KB_RING>{}), fb = g_fb[2 % KB_RING];
-#else
-            fb = g_fb[0];
-#endif
+            copy();
+            const int fb = g_fb;  // (issue below overwrites it)
             __syncthreads();
-            if (KB_RING == 1 || ring == 0) issue(std::integral_constant<int, 0>{});
-            else if (KB_RING == 2 || ring == 1) issue(std::integral_constant<int, 1 % KB_RING>{});
-            else issue(std::integral_constant<int, 2 % KB_RING>{});
-            ring = ring == KB_RING - 1 ? 0 : ring + 1;
+            issue();
             // chunk frame i -> LDS word
             auto word = [&](int i) __attribute__((always_inline)) {
                 const int u = i + fb, t = u / T;
                 return t * TP + (u - t * T);
             };
             const int q = tid & 7;  // accumulator q of the leaf (eight lanes per leaf)
-#ifdef MM_KB_NOLEAF  // (ablation builds: timing only)
-            if (l1 < 0)
-#endif
             for (int li = l0 + (tid >> 3); li < l1; li += KB_THREADS / 8) {
                 const int off = loff[li] - c * KB_CHUNK, len = llen[li];
                 float res;
@@ -247,12 +224,10 @@ __global__ void __launch_bounds__(KB_THREADS) kw_blocks_kernel(KbArgs a) {
             }
             __syncthreads();  // (the next chunk overwrites el; the levels read V)
         }
-#ifndef MM_KB_NOLEVEL  // (ablation builds: timing only)
         for (int L = 0; L < nlev; ++L) {
             for (int k = lvl[L] + tid; k < lvl[L + 1]; k += KB_THREADS) V[nl + k] = __fadd_rn(V[na[k]], V[nb[k]]);
             __syncthreads();
         }
-#endif
         if (tid == 0) {
             const float sm = root < 0 ? 0.0f : V[root];
             const double z = (double)__fmul_rn(a.scale, sm);

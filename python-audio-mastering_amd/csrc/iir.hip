@@ -14,8 +14,9 @@
 //   xover_kernel   AME:196-206 q1/32768 -> LP4 250 Hz + HP4 4 kHz (f64),
 //                              mid = x - lo - hi -> three int16 band planes
 //   kweight_kernel AME:213-218 mix -> mono f32 -> pyloudnorm high shelf + high
-//                              pass (f64, f32 between) -> per-tile energies of
-//                              the 0.1 s loudness segments
+//                              pass (f64, f32 between) -> the f32 square of every
+//                              frame for the exact block sums (gate.hip), or per-tile
+//                              partial energies of the 0.1 s loudness segments
 #include "lookback.h"
 
 namespace mm {
@@ -33,39 +34,13 @@ __device__ __forceinline__ int32_t quantize_i32(double v) {
 }
 __device__ __forceinline__ int16_t quantize(double v) { return (int16_t)quantize_i32(v); }
 
-// tanhf without a branch: OCML's __ocml_tanh_f32 (ROCm 7.2 ocml.bc) operation for
-// operation — |x| < 0.625: the odd polynomial |x| + x^2 |x| P(x^2) (FMAs), else
-// 1 - 2 / (exp(2|x|) + 1) with OCML's expf and v_rcp_f32 — both evaluated and one
-// selected, then copysign.  Bit-identical to tanhf (whose divergent if/else runs
-// both paths in most waves anyway, behind exec-mask branches that keep the
-// scheduler from overlapping a frame's tanh with the previous frame's f64 chain).
-__device__ __forceinline__ float tanh_sel(float x) {
-    const float ax = fabsf(x);
-    const float x2 = __fmul_rn(x, x);
-    float p = fmaf(x2, -0x1.758e7ap-8f, 0x1.521192p-6f);
-    p = fmaf(x2, p, -0x1.b8389cp-5f);
-    p = fmaf(x2, p, 0x1.110704p-3f);
-    p = fmaf(x2, p, -0x1.555532p-2f);
-    const float small = fmaf(x2, __fmul_rn(ax, p), ax);
-    const float e = expf(__fmul_rn(ax, 2.0f));
-    const float big = fmaf(-2.0f, __builtin_amdgcn_rcpf(__fadd_rn(e, 1.0f)), 1.0f);
-    return copysignf(ax < 0.625f ? small : big, x);
-}
-
 // apply_saturation (AME:128-134), f32 throughout; no FMA contraction so the
 // rounding sequence matches numpy: keep*x + mix*tanh(x*drive).  Inputs on the
 // int16 grid (every decoded PCM16 sample, AME:121) read the host's table of the
 // reference's own numpy evaluation (bit-identical); only off-grid inputs (f32
 // WAV) evaluate tanhf here (within 2 ulp of numpy's float32 tanh).
-// The device's own evaluation (tanhf: within 2 ulp of numpy's float32 tanh).
 __device__ __forceinline__ float saturate_dev(float x, const SatArgs &s) {
-#ifdef MM_ABLATE_TANH  // timing-only builds (tools/ablate.sh): the exciter without its tanh
-    float t = __fmul_rn(x, s.drive);
-#elif defined(MM_TANH_SEL)
-    float t = tanh_sel(__fmul_rn(x, s.drive));
-#else
     float t = tanhf(__fmul_rn(x, s.drive));
-#endif
     return __fadd_rn(__fmul_rn(s.keep, x), __fmul_rn(s.mix, t));
 }
 // With the correction codes: the device value, then the signed 2-bit code of its
@@ -220,7 +195,7 @@ constexpr int eq_lds_bytes() {
 // cooperatively loads EQ_STAGE frames of each of its tiles (16 consecutive
 // threads read one tile's 128 contiguous bytes), double-buffered so the next
 // stage's loads are in flight while lanes run the recurrence.
-template <int NS, int CH, bool P2, bool I16>
+template <int NS, int CH, bool I16>
 __device__ void eq_pass(const EqArgs &a, int64_t g0, int t, int c, int len, double (&z)[NS][2], float *stage,
                         const uint32_t *codes) {
     constexpr int TPB = LB_THREADS / CH;
@@ -258,8 +233,6 @@ __device__ void eq_pass(const EqArgs &a, int64_t g0, int t, int c, int len, doub
             }
         }
     };
-    // The exciter runs here, on the staged values, once per sample (its codes are LDS
-    // reads: no vector-memory wait in the per-frame loop below)
     // The exciter runs in the per-frame loop below: tanhf fills the issue slots the
     // f64 chain leaves, and its correction codes are LDS reads, so no vector-memory
     // wait sits in that loop (one would drain the staging prefetch at every frame).
@@ -278,7 +251,6 @@ __device__ void eq_pass(const EqArgs &a, int64_t g0, int t, int c, int len, doub
     load(0);
     store(0);
     lds_barrier();
-    const int64_t g = g0 + t;
     for (int step = 0; step < nsteps; ++step) {
         const int cur = step & 1;
         if (step + 1 < nsteps) load(step + 1);
@@ -291,16 +263,10 @@ __device__ void eq_pass(const EqArgs &a, int64_t g0, int t, int c, int len, doub
             // (no global load may sit in this loop, even unexecuted: the compiler's waits
             // would drain the staging prefetch; the full-table case runs as a pre-pass)
             if (a.sat.on) x = codes ? saturate_corr(x, a.sat, codes) : saturate_dev(x, a.sat);
-            if (!P2) a.xs[((int64_t)n * a.G + g0 + t) * CH + c] = x;  // pass 2 reads it back coalesced
+            a.xs[((int64_t)n * a.G + g0 + t) * CH + c] = x;  // pass 2 reads it back coalesced
             double y = (double)x;
 #pragma unroll
-            for (int s = 0; s < NS; ++s) y = df2t<P2>(y, z[s][0], z[s][1], sos[s]);
-            if (P2) {
-                if (CH == 2 && a.width_on) y = widen_pair(y, a.width * 0.5);  // AME:136-144, f64
-                const int64_t o = ((int64_t)n * a.G + g) * 2;
-                if (CH == 2) a.q_out[o + c] = quantize(y);
-                else *reinterpret_cast<short2 *>(a.q_out + o) = make_short2(quantize(y), 0);  // mono: R = 0
-            }
+            for (int s = 0; s < NS; ++s) y = df2t<false>(y, z[s][0], z[s][1], sos[s]);
         }
         if (step + 1 < nsteps) store(cur ^ 1);
         lds_barrier();
@@ -392,14 +358,14 @@ __global__ void __launch_bounds__(LB_THREADS, 4) eq_kernel(EqArgs a, LbArgs lb, 
     // with the exciter switch as a template argument measured slower: eq 0.152 ->
     // 0.166 ms); pass 2 takes the uniform-row path on full blocks.
     const bool full = (g0 + TPB) * a.T <= a.N_proc;
-#ifndef MM_ABL_EQ_NOP1  // (ablation builds: timing only)
     // the exciter's correction codes into LDS (ordered before their reads by eq_pass's
     // first barrier)
     const bool codes_on = a.sat.on && a.sat.corr;
     if (codes_on)
         for (int i = tid; i < SAT_CORR_WORDS; i += LB_THREADS) codes_lds[i] = a.sat.corr[i];
-    eq_pass<NS, CH, false, I16>(a, g0, t, c, len, zs, stage, codes_on ? codes_lds : nullptr);
-#endif
+    eq_pass<NS, CH, I16>(a, g0, t, c, len, zs, stage, codes_on ? codes_lds : nullptr);
+    // (packed by hand here and in xover_kernel: through lb_carry_sections the
+    // compiler schedules these two kernels' pass-2 loops differently)
     double z[DIM], s[DIM], rst[DIM];
 #pragma unroll
     for (int s_ = 0; s_ < NS; ++s_) {
@@ -408,26 +374,14 @@ __global__ void __launch_bounds__(LB_THREADS, 4) eq_kernel(EqArgs a, LbArgs lb, 
     }
 #pragma unroll
     for (int d = 0; d < DIM; ++d) rst[d] = 0.0;
-#ifndef MM_ABL_EQ_NOLB  // (ablation builds: timing only)
     lb_carry<DIM, CH>(lb, blk, t, c, valid, valid && (g % line_tiles) == 0, rst, z, s, lds);
-#else
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) s[d] = z[d] + rst[d];
-#endif
     __syncthreads();  // every lane has read the look-back scratch before pass 2 stages into it
 #pragma unroll
     for (int s_ = 0; s_ < NS; ++s_) {
         zs[s_][0] = s[2 * s_];
         zs[s_][1] = s[2 * s_ + 1];
     }
-#ifdef MM_ABL_EQ_NOP2  // (ablation builds: timing only)
-    return;
-#endif
-#ifdef MM_EQ_P2_GENERIC  // (ablation builds)
-    if (false) {
-#else
     if (full) {
-#endif
         if (CH == 2 && a.width_on) eq_pass2_full<NS, CH, true>(a, g0, zs);
         else eq_pass2_full<NS, CH, false>(a, g0, zs);
     } else if (valid) {
@@ -786,41 +740,24 @@ __global__ void __launch_bounds__(LB_THREADS, 2) kweight_kernel(KwArgs a, LbArgs
         e_end = a.trk_end[lo];
     }
     if (valid) kw_pass<false>(a, g, len, zs, 0, e_end, e0, e1);
-    double z[4] = {zs[0][0], zs[0][1], zs[1][0], zs[1][1]}, s[4], rst[4];
-#pragma unroll
-    for (int d = 0; d < 4; ++d) rst[d] = lb.init ? lb.init[d] : 0.0;
-    lb_carry<4, 1>(lb, blk, t, 0, valid, valid && g == line0, rst, z, s, smem);
+    lb_carry_sections<2, 1>(lb, blk, t, 0, valid, valid && g == line0, zs, smem, lb.init);
     if (!valid) return;
     if constexpr (SQ) {
-        zs[0][0] = s[0];
-        zs[0][1] = s[1];
-        zs[1][0] = s[2];
-        zs[1][1] = s[3];
         kw_pass<true, true>(a, g, len, zs, 0, e_end, e0, e1);
-        if (a.line_end && g == a.G - 1) {
-            a.line_end[0] = zs[0][0];
-            a.line_end[1] = zs[0][1];
-            a.line_end[2] = zs[1][0];
-            a.line_end[3] = zs[1][1];
+    } else {
+        // loudness segment of the tile's first frame (largest s with bounds[s] <= f0)
+        const int64_t f0 = g * a.T;
+        int64_t lo = 0, hi = a.n_segs;
+        while (hi - lo > 1) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (a.seg_bounds[mid] <= f0) lo = mid;
+            else hi = mid;
         }
-        return;
+        kw_pass<true>(a, g, len, zs, a.seg_bounds[lo + 1], e_end, e0, e1);
+        a.part[2 * g] = e0;
+        a.part[2 * g + 1] = e1;
+        a.part_seg[g] = lo;
     }
-    // loudness segment of the tile's first frame (largest s with bounds[s] <= f0)
-    const int64_t f0 = g * a.T;
-    int64_t lo = 0, hi = a.n_segs;
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (a.seg_bounds[mid] <= f0) lo = mid;
-        else hi = mid;
-    }
-    zs[0][0] = s[0];
-    zs[0][1] = s[1];
-    zs[1][0] = s[2];
-    zs[1][1] = s[3];
-    kw_pass<true>(a, g, len, zs, a.seg_bounds[lo + 1], e_end, e0, e1);
-    a.part[2 * g] = e0;
-    a.part[2 * g + 1] = e1;
-    a.part_seg[g] = lo;
     if (a.line_end && g == a.G - 1) {
         a.line_end[0] = zs[0][0];
         a.line_end[1] = zs[0][1];

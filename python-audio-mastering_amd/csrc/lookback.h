@@ -181,11 +181,7 @@ __device__ void lb_carry(const LbArgs &a, int blk, int t, int c, bool valid, boo
         for (int d = 0; d < DIM; ++d) sp[d] = 0.0;
     }
     const bool blk_reset = flg[0 * TPB + TPB - 1] != 0;  // same line structure for every channel
-#ifndef MM_ABL_NOLOOK  // (ablation builds: timing only)
     const bool need_carry = !flg[0 * TPB + 0];           // tile 0 of the block is not a line start
-#else
-    const bool need_carry = false;
-#endif
     // 2. publish the aggregate
     if (t == TPB - 1) {
         double *ag = a.agg + ((int64_t)blk * CH + c) * 8;
@@ -310,6 +306,28 @@ __device__ void lb_carry(const LbArgs &a, int blk, int t, int c, bool valid, boo
         }
 #pragma unroll
         for (int d = 0; d < DIM; ++d) s[d] = sp[d] + cv[d];
+    }
+}
+
+// lb_carry on a filter's section state: zs[k] = (z0, z1) of DF2T section k holds the
+// tile's zero-state end state on entry and its carry-in state on return.  init: the
+// state at a line start ([2 NS]; null = zero).
+template <int NS, int CH, int NB0 = NS>
+__device__ __forceinline__ void lb_carry_sections(const LbArgs &a, int blk, int t, int c, bool valid, bool reset,
+                                                  double (&zs)[NS][2], double *lds, const double *init = nullptr) {
+    double z[2 * NS], s[2 * NS], rst[2 * NS];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        z[2 * k] = zs[k][0];
+        z[2 * k + 1] = zs[k][1];
+    }
+#pragma unroll
+    for (int d = 0; d < 2 * NS; ++d) rst[d] = init ? init[d] : 0.0;
+    lb_carry<2 * NS, CH, NB0>(a, blk, t, c, valid, reset, rst, z, s, lds);
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        zs[k][0] = s[2 * k];
+        zs[k][1] = s[2 * k + 1];
     }
 }
 

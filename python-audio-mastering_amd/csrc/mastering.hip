@@ -79,11 +79,11 @@ static void zs_weights(const mm_iir &f, int T, std::vector<double> &W) {
 }
 
 // The stage's zero-state weights on the device (rebuilt only when its sections or
-// the tile change); null with MM_ZS_RECUR (A/B: pass 1 as the recurrence).
+// the tile change); null for a section count outside 1..4 (pass 1 then runs the
+// recurrence).
 static int upload_zw(mm_ctx *c, const char *name, const mm_iir &f, int T, const double **out) {
-    static const bool recur = getenv("MM_ZS_RECUR") != nullptr;
     *out = nullptr;
-    if (recur || f.nsec < 1 || f.nsec > 4) return MM_OK;
+    if (f.nsec < 1 || f.nsec > 4) return MM_OK;
     std::vector<double> key(f.sos[0], f.sos[0] + 20);
     key.push_back((double)T);
     key.push_back((double)f.nsec);
@@ -255,9 +255,8 @@ static int ensure_rb(mm_ctx *c, size_t bytes) {
 // Hand the readback area over in the chain's last finalize launch (FinArgs::ctl),
 // instead of a copy after it.
 static int attach_tail(mm_ctx *c, FinArgs &fa) {
-    static const bool off = getenv("MM_CTL_FILL") != nullptr;  // (A/B: the round-5 fill + copy)
     c->tail_readback = false;
-    if (off || !c->ctl) return MM_OK;
+    if (!c->ctl) return MM_OK;
     const size_t rbb = rb_bytes(comp_chunks(c));
     RET(ensure_rb(c, rbb + 64));
     fa.ctl = c->ctl;
@@ -283,10 +282,6 @@ static int queue_readback(mm_ctx *c) {
 // block only waits on blocks that started before it) and whether the queued
 // sweeps converged.
 static int evaluate_chain(mm_ctx *c, bool *converged) {
-    static const bool debug_walked = getenv("MM_DEBUG_WALKED") != nullptr;
-    if (debug_walked)
-        fprintf(stderr, "walked=%llu jumped=%llu\n", *reinterpret_cast<const unsigned long long *>(c->rb + RB_WALKED),
-                *reinterpret_cast<const unsigned long long *>(c->rb + RB_WALKED + 8));
     if (*reinterpret_cast<const unsigned *>(c->rb + RB_ERR)) return set_err(c, MM_ERR_STATE, "IIR look-back timed out");
     if (c->comp_on && c->ca.trace) {  // MM_FIX_TRACE: the three slowest walkers of every sweep
         const int64_t NS = c->ca.GS;
@@ -410,8 +405,7 @@ static int setup_control(mm_ctx *c, unsigned nblk, int64_t nch, int64_t claims) 
     const size_t bytes = rba + FIN_DONE_BYTES + cla + 3 * region;
     char *ctl;
     RET(get_buf(c, "ctl", bytes, &ctl));
-    static const bool always_fill = getenv("MM_CTL_FILL") != nullptr;  // (A/B: round 5's fill per chain)
-    if (always_fill || !c->ctl_clean || ctl != c->ctl_clean_ptr || bytes > c->ctl_clean_bytes)
+    if (!c->ctl_clean || ctl != c->ctl_clean_ptr || bytes > c->ctl_clean_bytes)
         HIPCHK(c, hipMemsetAsync(ctl, 0, bytes, c->stream));
     c->ctl_clean = false;
     c->ctl = ctl;
@@ -500,9 +494,7 @@ static int stage_compress(mm_ctx *c, const mm_job *j, short2 *const bands[3], co
     RET(get_buf(c, "comp_nact", (size_t)3 * nchunks, &nacts));
     ca.jumps = getenv("MM_COMP_NOJUMP") ? 0 : 1;  // diagnostics: results must not change
     ca.sjump = ca.jumps && !getenv("MM_COMP_NOSJUMP") && ca.TPS == SJ_TPS ? 1 : 0;
-    ca.jacobi_stop = getenv("MM_JACOBI_STOP") ? 1 : 0;  // (tuning experiments)
     ca.e_tiles = E_TILES;
-    if (const char *e = getenv("MM_E_TILES")) ca.e_tiles = std::max(0, atoi(e));  // (tuning experiments)
     double *sdesc;
     int32_t *se0s;
     RET(get_buf(c, "comp_sdesc", ca.sjump ? (size_t)3 * NS * SREC : 1, &sdesc));
@@ -655,7 +647,6 @@ static int stage_front(mm_ctx *c, const mm_job *j, const void *d_in, unsigned nb
         }
         // codes when complete (else, and for A/B: a full-table gather per sample)
         if (c->sat_codes && !getenv("MM_SAT_GATHER")) ea.sat.corr = corr;
-        if (getenv("MM_SAT_TANHF")) ea.sat.tab = nullptr, ea.sat.corr = nullptr;  // (A/B: round 5's tanhf alone)
         if (ea.sat.tab && !ea.sat.corr && j->eq.nsec > 0 && N > 0) {
             // the EQ kernel takes the exciter only as tanhf + codes: the table case runs
             // as a pointwise pre-pass into a decoded f32 input, and the EQ without it
@@ -1024,7 +1015,7 @@ static int kweight_exact(mm_ctx *c, const mm_job *j, int64_t frames, const LineG
         kb.pints = c->kb_pints;
         const size_t lds = (size_t)kb_lds_bytes(kb.stage_floats, kb.nvals, kb.pints);
         // persistent: as many workgroups as fit at once (a multiple of 8: the XCD-aware block mapping)
-        const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(KB_RING == 1 ? 4 : 2, (160 * 1024) / (int64_t)(lds + 64)));  // (and VGPRs)
+        const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(4, (160 * 1024) / (int64_t)(lds + 64)));  // (and VGPRs)
         const unsigned grid = (unsigned)std::min<int64_t>((nb + 7) / 8 * 8, (int64_t)c->n_cus * per_cu / 8 * 8);
         RET(launch(c, "kw_blocks", kw_blocks_kernel, dim3(std::max(grid, 8u)), dim3(KB_THREADS), lds, kb));
     }

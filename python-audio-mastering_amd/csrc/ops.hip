@@ -212,7 +212,6 @@ template <int NS, int CH, bool R32>
 __global__ void __launch_bounds__(LB_THREADS, 2) iir_op_kernel(IirOpArgs a, LbArgs lb) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int TPB = LB_THREADS / CH;
-    constexpr int DIM = 2 * NS;
     __shared__ int ticket_slot;
     const int blk = lb_ticket(lb, &ticket_slot);
     const int tid = threadIdx.x;
@@ -225,19 +224,7 @@ __global__ void __launch_bounds__(LB_THREADS, 2) iir_op_kernel(IirOpArgs a, LbAr
 #pragma unroll
     for (int s = 0; s < NS; ++s) zs[s][0] = zs[s][1] = 0.0;
     if (valid) iir_op_pass<NS, R32, false>(a, g, c, CH, len, zs);
-    double z[DIM], s[DIM], rst[DIM];
-#pragma unroll
-    for (int s_ = 0; s_ < NS; ++s_) {
-        z[2 * s_] = zs[s_][0];
-        z[2 * s_ + 1] = zs[s_][1];
-        rst[2 * s_] = rst[2 * s_ + 1] = 0.0;
-    }
-    lb_carry<DIM, CH>(lb, blk, t, c, valid, valid && g == 0, rst, z, s, smem);
-#pragma unroll
-    for (int s_ = 0; s_ < NS; ++s_) {
-        zs[s_][0] = s[2 * s_];
-        zs[s_][1] = s[2 * s_ + 1];
-    }
+    lb_carry_sections<NS, CH>(lb, blk, t, c, valid, valid && g == 0, zs, smem);
     if (valid) iir_op_pass<NS, R32, true>(a, g, c, CH, len, zs);
 }
 

@@ -1,6 +1,6 @@
 #!/bin/bash
-# Bench one workload under several environment settings (tuning knobs such as
-# MM_COMP_LAYOUT, MM_PASS0_OWN), printing step time and the top kernels.
+# Bench one workload under several environment settings (switches such as
+# MM_COMP_SWEEPS, MM_SAT_GATHER), printing step time and the top kernels.
 # Usage: bash tools/env_sweep.sh <tag> <workload|C2hot> "ENV=a ENV2=b" "ENV=c" ...
 cd "$GRAFT_REPO_ROOT" || exit 1
 tag=$1; w=$2; shift 2

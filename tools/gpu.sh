@@ -5,7 +5,7 @@
 #   bash tools/gpu.sh test [pytest selection...]      GPU parity suite (+ smoke)
 #   bash tools/gpu.sh iter [variants...]              C2 / C2 P_HOT bench lines with the
 #        per-kernel split; a variant is "ENV=x" (library env knob), "tune:NAME=V"
-#        (bench tune) or "lib:<path.so>" (an ablation build from tools/build_var.sh)
+#        (bench tune) or "lib:<path.so>" (a variant build from tools/build_var.sh: build/ab/<name>.so)
 #   bash tools/gpu.sh c2 [variants...]                C2 lines only (variants as in iter)
 #   bash tools/gpu.sh configs [C3 C4 C5 C1 ...]       bench lines of the other workloads
 #   bash tools/gpu.sh measure <round> [notest] [workloads...]  end-of-round measurement: tests, smoke,
