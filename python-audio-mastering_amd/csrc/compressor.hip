@@ -356,6 +356,37 @@ __global__ void __launch_bounds__(256, MM_RMS_MINB) comp_rms_t_kernel(CompArgs a
     if (lane == 0 && v) atomicAdd(a.total[b] + cc, v);
 }
 
+// 1b. A fused timeline (mm_master_batch) pads every track to whole chunks with zero
+// input, and the IIR stages ring on into that padding: band frames there can stay
+// above the threshold, and comp_rms_t counts them (the solve ranks their tiles like
+// any other: the per-tile counts stay).  They are not the track's frames, so they
+// leave the per-chunk statistics again and a track reports the same active
+// band-frames in a timeline as on its own.  grid: (tracks, 3 bands) of one wave;
+// pad[2 i] is track i's end on the timeline, pad[2 i + 1] the end of its last chunk.
+// (active <=> M != 0: r0 is the table's first nonzero row, the table nondecreasing;
+// a tile with a nonzero count has its M rows stored.)
+__global__ void __launch_bounds__(64) comp_trim_kernel(CompArgs a, const int64_t *pad) {
+    const int b = blockIdx.y, lane = threadIdx.x, T = a.T;
+    const int64_t e = pad[2 * blockIdx.x], nx = pad[2 * blockIdx.x + 1];
+    int v = 0;
+    for (int64_t g = e / T + lane; g < nx / T; g += 64) {
+        const int c = a.cnt[b][g];
+        const int first = (int)max((int64_t)0, e - g * T);  // (> 0 only in the tile the track ends in)
+        if (c == 0) continue;
+        if (first == 0) {
+            v += c;
+            continue;
+        }
+        int64_t s;
+        int k;
+        tile_col(a, g, &s, &k);
+        const double *M = chunk_plane(a, b, g / a.K) + col_elem(a, s) + (uint32_t)(k * a.TP) * 64u;
+        for (int n = first; n < T; ++n) v += M[(uint32_t)n * 64u] != 0.0 ? 1 : 0;
+    }
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if (lane == 0 && v) atomicSub(a.total[b] + (nx / ((int64_t)T * a.K) - 1), v);
+}
+
 struct BandStep {
     double A, R, rA, rR;
 };

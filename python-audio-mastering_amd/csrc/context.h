@@ -56,6 +56,10 @@ struct mm_ctx {
     bool tail_readback = false;         // the last queued finalize hands the readback area over
     uint32_t *ctl_claims = nullptr;     // its zeroed claim stamps
     int comp_iters = 0, comp_pending = 0;
+    // a fused timeline's tracks with padding: {end, end of the last chunk} pairs on the
+    // device for comp_trim_kernel (unit_enqueue sets them around stage_front; 0: none)
+    const int64_t *comp_pad = nullptr;
+    int comp_pad_n = 0;
     int comp_queue = 0;  // sweeps to queue with the next solve (0: COMP_SWEEPS; then the last solve's need + 1)
     uint64_t comp_sig = 0;  // settings and geometry of the solve comp_queue was learnt on (comp_signature)
     // loudness on the device

@@ -558,6 +558,8 @@ static int stage_compress(mm_ctx *c, const mm_job *j, short2 *const bands[3], co
     }
     // column block = one workgroup (RMS_TPS x 64 tiles): gathers / stores through LDS
     RET(launch(c, "comp_rms", comp_rms_t_kernel, dim3((unsigned)(NS / 64), 3), dim3(256), 0, ca));
+    if (c->comp_pad_n > 0)  // a timeline: the padding's frames leave the per-chunk statistics
+        RET(launch(c, "comp_trim", comp_trim_kernel, dim3((unsigned)c->comp_pad_n, 3), dim3(64), 0, ca, c->comp_pad));
     RET(launch(c, "comp_describe", comp_describe_kernel, dim3((unsigned)(NS / 64), 3), dim3(64 * ca.TPS), 0, ca));
     RET(launch(c, "comp_pass0", comp_pass0_kernel, dim3(blocks_for(NS, PASS0_BLOCK), 3), dim3(PASS0_BLOCK), 0, ca));
     c->comp_on = true;
@@ -1181,6 +1183,7 @@ struct Unit {
     std::vector<int64_t> nch;  // [n] chunks of each track
     int64_t P = 0;             // timeline frames
     LineGeom geom;             // loudness geometry on the device (unit_geometry)
+    std::vector<int64_t> pad;  // {track end, end of its last chunk} of the tracks that end inside a chunk
 };
 
 static bool same_iir(const mm_iir &a, const mm_iir &b) { return memcmp(&a, &b, sizeof a) == 0; }
@@ -1355,8 +1358,23 @@ static int unit_enqueue(mm_ctx *c, Unit &u) {
         tj.frames_in = tj.frames_proc = u.P;
         tj.lufs_on = 0;
         line = &tj;
+        u.pad.clear();  // (the unit outlives the copy: unit_complete syncs)
+        for (int i = 0; i < u.n && j0.multiband_on; ++i)
+            if (u.off[i] + u.J[i].frames_proc < u.off[i + 1]) {
+                u.pad.push_back(u.off[i] + u.J[i].frames_proc);
+                u.pad.push_back(u.off[i + 1]);
+            }
+        if (!u.pad.empty()) {
+            int64_t *d;
+            RET(get_buf(c, "fz_pad", u.pad.size(), &d));
+            HIPCHK(c, hipMemcpyAsync(d, u.pad.data(), u.pad.size() * 8, hipMemcpyHostToDevice, c->stream));
+            c->comp_pad = d;
+            c->comp_pad_n = (int)(u.pad.size() / 2);
+        }
     }
-    RET(stage_front(c, line, tin, lufs ? kw_nblk(&j0, G) : 0u));
+    const int rc = stage_front(c, line, tin, lufs ? kw_nblk(&j0, G) : 0u);
+    c->comp_pad_n = 0;
+    RET(rc);
     return unit_tail(c, u);
 }
 

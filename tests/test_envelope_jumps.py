@@ -7,7 +7,11 @@ The per-frame M sequences (inactive frames M = 0 included: the solve runs in
 frame space, one descriptor per 125-frame tile) come from the oracle's own band
 split of a pink-noise track at P_HOT thresholds (every envelope branch fires), so
 the check covers long release stretches, parity ties and binade crossings of real
-trajectories."""
+trajectories.  Pink noise is stationary, so the same checks also run on the M
+sequences of three structured signals (tests/signals.py): a level step with a long
+release over quiet frames, sparse bursts, and a staircase around the table's first
+nonzero row whose state sits some 15 binades above M (outside a record's JB binades:
+no jump may be taken there, and none that is taken may be wrong)."""
 import math
 import struct
 
@@ -96,10 +100,50 @@ def _band_M(seconds=20):
     return out
 
 
+STRUCTURED = ("step_down", "bursts", "staircase")
+
+
+def _structured_M(name):
+    """[(M, attack frames, release frames)] per band of a 3 s structured signal."""
+    import signals as S
+    if name == "staircase":
+        hold = int(S.SECONDS * S.RATE) // 8
+        return [(b["M"], b["attack_frames"], b["release_frames"])
+                for b in (S.band_structure(x, S.RATE, *st, SEG)
+                          for x, st in zip(S.staircase_bands(1, hold=hold)[:2], S.band_settings()))]
+    st = S.structure(S.CATALOGUE[name](), S.RATE, S.P_HOT)
+    return [(b["M"], b["attack_frames"], b["release_frames"]) for b in st["chunks"][0]]
+
+
+def _sources(source):
+    return [("pink", _band_M())] if source == "pink" else [(n, _structured_M(n)) for n in STRUCTURED]
+
+
+def _floor(source, what, shares, floor):
+    """Pink noise keeps its floor on the share of jumps taken; over the structured
+    sources every taken jump was asserted exact, at least one must be taken over the
+    three together, and each source's share is printed."""
+    for name, (taken, of) in shares.items():
+        print(f"{what}: {name}: {taken} of {of} taken ({taken / max(of, 1):.3f})")
+    taken, of = (sum(v[k] for v in shares.values()) for k in (0, 1))
+    if source == "pink":
+        assert taken > floor * of, (taken, of)
+    else:
+        assert taken > 0, shares
+
+
 @pytest.mark.timeout(300)
-def test_release_jumps_are_exact():
+@pytest.mark.parametrize("source", ["pink", "structured"])
+def test_release_jumps_are_exact(source):
+    shares = {}
+    for name, bands in _sources(source):
+        shares[name] = _release_jumps(bands)
+    _floor(source, "release jumps", shares, 0.3)  # the jump conditions are not vacuous
+
+
+def _release_jumps(bands):
     jumps = checked = 0
-    for M, A, R in _band_M():
+    for M, A, R in bands:
         traj = [0.0]
         for m in M:
             traj.append(_step(traj[-1], m, A, R))
@@ -122,7 +166,7 @@ def test_release_jumps_are_exact():
                 for m in seg:
                     y = _step(y, m, A, R)
                 assert x == y, (s0, att, x, y)
-    assert jumps > 0.3 * checked, (jumps, checked)  # the jump conditions are not vacuous
+    return jumps, checked
 
 
 SJ_TPS = 4  # tiles per super-tile with a composed record (== csrc/compressor.hip SJ_TPS)
@@ -174,12 +218,20 @@ def _super_jump(rec, att):
 
 
 @pytest.mark.timeout(300)
-def test_super_tile_jumps_are_exact():
+@pytest.mark.parametrize("source", ["pink", "structured"])
+def test_super_tile_jumps_are_exact(source):
     """Records composed from SJ_TPS consecutive active tiles' descriptors: a super
     jump lands on the state the step-by-step loop reaches, and every tile's entry
     state it writes equals the loop's."""
+    shares = {}
+    for name, bands in _sources(source):
+        shares[name] = _super_jumps(bands)
+    _floor(source, "super jumps", shares, 0.2)
+
+
+def _super_jumps(bands):
     jumps = checked = 0
-    for M, A, R in _band_M():
+    for M, A, R in bands:
         Ma = [float(v) for v in M if v != 0.0]  # the solve's compact (active) frames
         traj = [0.0]
         for m in Ma:
@@ -203,7 +255,7 @@ def test_super_tile_jumps_are_exact():
                     for m in sg:
                         y = _step(y, m, A, R)
                 assert x == y, (s0, att, x, y)
-    assert jumps > 0.2 * checked, (jumps, checked)
+    return jumps, checked
 
 
 def _e_walk(E, M, R):
@@ -238,12 +290,20 @@ def _e_tile(E, ct, desc):
 
 
 @pytest.mark.timeout(300)
-def test_e_fold_by_tiles_is_exact():
+@pytest.mark.parametrize("source", ["pink", "structured"])
+def test_e_fold_by_tiles_is_exact(source):
     """The pass-0 guess folded tile by tile equals the per-frame (max,+) walk bit for
     bit whenever the tile records cover the state (so a guess coincides with a
     speculative walk's release values, as tools/study/envelope_model.c assumes)."""
+    shares = {}
+    for name, bands in _sources(source):
+        shares[name] = _e_fold(bands)
+    _floor(source, "e fold (tiles covered by their records)", shares, 0.9)
+
+
+def _e_fold(bands):
     total = covered = 0
-    for M, A, R in _band_M():
+    for M, A, R in bands:
         Ma = [float(v) for v in M if v != 0.0]
         segs = [Ma[s0:s0 + SEG] for s0 in range(0, len(Ma) - SEG + 1, SEG)]
         E_frame = E_tile = 0.0
@@ -258,5 +318,4 @@ def test_e_fold_by_tiles_is_exact():
             covered += 1
             assert nxt == E_frame
             E_tile = nxt
-    print(f"e fold: {covered} of {total} tiles covered by their records")
-    assert covered > 0.9 * total
+    return covered, total
