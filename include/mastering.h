@@ -131,7 +131,12 @@ typedef struct mm_job {
        when the job carries loudness geometry (kweight, blocks, segments), whether or
        not lufs_on is set.  0: the chain queues exactly what it queued before. */
     int32_t meter_on;
-    int32_t _pad;
+    /* true-peak ceiling (ABI 5, the former trailing pad): 0 = off, the chain queues exactly
+       what it queued before; else the ceiling C as linear * 2^28, 2^24 <= C <= 2^28
+       (-24.08 .. 0 dBTP; design.ceiling_q28).  The delivered output of the track is then
+       rewritten in place (mm_ceiling, window of 5 ms) after the chain and before the
+       report, so that its true peak, measured as mm_meter measures it, is at most C. */
+    int32_t ceiling_q28;
 } mm_job;
 
 typedef struct mm_result {
@@ -166,6 +171,34 @@ typedef struct mm_meter {
                                    NaN when not requested or shorter than 0.4 s      */
 } mm_meter;
 
+/* The true-peak ceiling (no reference counterpart), all integers.  Notation of
+ * mm_meter; ONE = 2^16; C = ceiling_q28; W = window (frames); C_t = C - 8286 (8286 >
+ * 16571 / 2, the largest sum of |taps| of a phase: requantising a scaled signal moves a
+ * sample by at most 1/2, hence |Y| by at most 8285.5).
+ *   1. P[m] = max over channels and phases of |Y_c[m][p]|, TP0 = max P.  If TP0 <= C
+ *      the signal is not touched (no byte is written).
+ *   2. r[m] = ONE if P[m] <= C_t, else floor(C_t * 2^16 / P[m])      (in [1900, 65535])
+ *   3. R[n] = min r[n .. n+11] for n in [0, frames) (the m that sample n feeds); ONE outside
+ *   4. h[k] = min R[k-W .. k+W] for k in [-W, frames + W)
+ *   5. g[n] = floor(sum h[n-W .. n+W] / (2W + 1))   (every window holds n: g[n] <= R[n])
+ *   6. s'[c][n] = s[c][n] if g[n] == ONE, else (s[c][n] * g[n] + 2^15) >> 16 (arithmetic)
+ *   7. TP1 = true peak of s'.  If TP1 <= C: done.
+ *   8. Else every sample once more by g_t = floor(C_t * 2^16 / TP1), same rounding:
+ *      |Y''| <= g_t * TP1 / 2^16 + 8285.5 <= C_t + 8285.5 < C.
+ * Channels are linked: one gain per frame. */
+typedef struct mm_ceiling {
+    int64_t frames;          /* 0: this track had no ceiling (mm_last_ceilings)     */
+    int32_t channels;
+    int32_t window;          /* W                                                   */
+    int32_t ceiling_q28;     /* C                                                   */
+    int32_t tp_in_q28;       /* TP0: linked true peak of the input                  */
+    int32_t tp_limited_q28;  /* TP1: after the limiter (== TP0 when not touched)    */
+    int32_t tp_out_q28;      /* of the delivered samples; <= C whenever TP0 > C     */
+    int32_t min_gain_q16;    /* min g (ONE when not touched)                        */
+    int32_t trim_q16;        /* g_t, ONE when no trim was needed                    */
+    int64_t limited_frames;  /* frames with g < ONE                                 */
+} mm_ceiling;
+
 /* Geometry of the compressor's envelope solve for a job (mm_solve_geometry: the
    planning arithmetic stage C runs on, computed on the host without a GPU). */
 typedef struct mm_solve_geom {
@@ -195,7 +228,10 @@ int mm_sync(mm_ctx *ctx);
    mm_op_saturation_table, mm_np_sum_f32, mm_check_compressor_math,
    mm_solve_geom.col_block / rms_group_tiles (round 6); 5 = mm_job.meter_on, mm_meter and
    the metering entry points (mm_meter_device, mm_meter_pcm, mm_last_meters,
-   mm_op_true_peak, mm_true_peak_host, mm_meter_span).  A caller built against an older header must
+   mm_op_true_peak, mm_true_peak_host, mm_meter_span); also under 5, in the place of
+   mm_job's trailing pad (a caller that zeroed it gets what it got): mm_job.ceiling_q28,
+   mm_ceiling and the ceiling entry points (mm_ceiling_device, mm_ceiling_pcm,
+   mm_ceiling_host, mm_last_ceilings, mm_ceiling_span, mm_ceiling_max_window).  A caller built against an older header must
    refuse a library whose version differs from its own MM_ABI_VERSION. */
 #define MM_ABI_VERSION 5
 int mm_version(void);
@@ -245,6 +281,31 @@ int mm_last_meters(mm_ctx *ctx, int cap, mm_meter *out);
 int mm_true_peak_host(const int16_t *pcm, int64_t frames, int channels, mm_meter *out);
 /* Frames of m per workgroup of the meter kernel (where its seams lie). */
 int mm_meter_span(void);
+
+/* ---- true-peak ceiling ----------------------------------------------------- */
+/* Hold a device-resident signal, interleaved [frames][channels] of `kind` (MM_OUT_I16,
+ * or MM_OUT_F32 = the same PCM / 32768), under the true-peak ceiling ceiling_q28 with a
+ * look-ahead window of `window` frames (1 .. mm_ceiling_max_window()), in place, as
+ * mm_ceiling defines.  MM_ERR_ARG for a ceiling or window out of range or frames beyond
+ * the meter's limit.  Synchronous on return. */
+int mm_ceiling_device(mm_ctx *ctx, void *d_pcm, int kind, int64_t frames, int channels, int32_t ceiling_q28,
+                      int32_t window, mm_ceiling *out);
+/* The same on a host buffer, in place. */
+int mm_ceiling_pcm(mm_ctx *ctx, void *pcm, int kind, int64_t frames, int channels, int32_t ceiling_q28,
+                   int32_t window, mm_ceiling *out);
+/* The definition restated in plain C++ on the host (no context, no GPU), in place on
+ * interleaved int16: a CPU check of what the ceiling kernels compute. */
+int mm_ceiling_host(int16_t *pcm, int64_t frames, int channels, int32_t ceiling_q28, int32_t window,
+                    mm_ceiling *out);
+/* The ceilings of the last mm_master / mm_master_device / mm_master_wav (1) or
+ * mm_master_batch (n, in job order; tracks whose job had ceiling_q28 == 0 report
+ * frames 0) call on this context: copies min(cap, n) of them and returns n.
+ * MM_ERR_STATE if that call set no ceiling. */
+int mm_last_ceilings(mm_ctx *ctx, int cap, mm_ceiling *out);
+/* Frames per workgroup of the kernel that applies the gains (where its seams lie). */
+int mm_ceiling_span(void);
+/* The largest look-ahead window, in frames (1024). */
+int mm_ceiling_max_window(void);
 
 /* ---- WAV files (AME:43 decode, AME:98 export) ------------------------------ */
 typedef struct mm_wav_info {

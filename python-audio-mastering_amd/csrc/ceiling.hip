@@ -1,0 +1,525 @@
+// ceiling.hip — the true-peak ceiling: an exact look-ahead limiter on the delivered
+// int16 output, and one static trim when the limiter leaves a residue.  No reference
+// counterpart.  Everything is defined in integers (include/mastering.h, mm_ceiling):
+//   P[m]  = max over channels and phases of |Y_c[m][p]|          (the meter's Y)
+//   r[m]  = 2^16 if P[m] <= C_t, else floor(C_t * 2^16 / P[m]),  C_t = C - 8286
+//   R[n]  = min r[n .. n+11]                (the m that sample n feeds), 2^16 outside
+//   h[k]  = min R[k-W .. k+W],   g[n] = floor(sum h[n-W .. n+W] / (2W+1))   (<= R[n])
+//   s'[n] = s[n] if g[n] == 2^16, else (s[n] * g[n] + 2^15) >> 16
+// and, if the true peak TP1 of s' is still above C, every sample once more by
+// g_t = floor(C_t * 2^16 / TP1): requantising moves |Y| by at most 8285.5 < 8286, so
+// the trimmed peak is at most C_t + 8285.5 < C.
+//
+// Three kernels.  ceil_need has the meter's structure (LDS int16 lines, 24 packed dot
+// products per frame and channel) and writes r - 1 as uint16 to a plane; ceil_apply
+// stages the plane with its halo in LDS, forms both window minima by log-step doubling
+// and the box sums from one LDS scan, and rewrites the samples in place; ceil_trim is
+// pointwise.  The true peak after the limiter is the meter's own kernel.  All results
+// are integers combined with min / max / add: nothing depends on the launch geometry.
+//
+// Included at the end of mastering.hip after meter.hip (its taps, dot product, wave
+// reductions and meter_launch).
+
+namespace mm {
+
+constexpr int CEIL_ONE = 1 << 16;
+constexpr int CEIL_GUARD = 8286;     // > 16571 / 2: what requantising can add to |Y|
+constexpr int CEIL_MAX_W = 1024;     // mm_ceiling_max_window
+constexpr int CEIL_THREADS = 256;
+constexpr int CEIL_SPAN = 4096;      // frames per ceil_apply workgroup (mm_ceiling_span)
+constexpr int CEIL_RLEN = CEIL_SPAN + 4 * CEIL_MAX_W + 11;  // staged r of a span at the widest window
+constexpr int CEIL_BUF = (CEIL_RLEN + 5 + 7) / 8 * 8;     // + what a packed pass may touch past a line's end
+constexpr int CEIL_HLEN = CEIL_SPAN + 2 * CEIL_MAX_W;       // h of a span at the widest window
+
+// device result block of one ceiling (zeroed on the stream before ceil_need)
+struct CeilDev {
+    unsigned tp0;                // max P (TP0)
+    unsigned max_red;            // max (2^16 - g): the minimum gain, as a maximum of zero-initialised words
+    unsigned long long limited;  // frames with g < 2^16
+};
+
+// floor(Ct * 2^16 / P) for 0 < Ct < P < 2^30.  The numerator is below 2^44 and exact in
+// f64; a non-integer quotient lies at least 1/P > 2^-30 from an integer while the
+// correctly rounded f64 quotient is within 2^-37 of it, so truncation already gives the
+// floor.  The integer remainder check makes that independent of how the division rounds.
+__device__ __forceinline__ int ceil_ratio(int Ct, int P) {
+    const long long num = (long long)Ct << 16;
+    int q = (int)((double)num / (double)P);
+    const long long rem = num - (long long)q * P;
+    q += rem < 0 ? -1 : (rem >= P ? 1 : 0);
+    return q;
+}
+
+// One workgroup per span of METER_SPAN frames m; a thread owns METER_FPT consecutive m
+// (the meter's window layout).  It writes r[m] - 1 for all its m as one 16-byte store:
+// the plane holds whole spans, so every entry up to the plane's end is written (2^16 - 1
+// beyond N + 11, where P = 0).  TP0 is folded into st->tp0 with one atomic per workgroup.
+template <int CH, typename T>
+__global__ void __launch_bounds__(METER_THREADS) ceil_need_kernel(const T *__restrict__ in, int64_t N, int Ct,
+                                                                  uint16_t *__restrict__ plane, CeilDev *st) {
+    __shared__ __attribute__((aligned(16))) int16_t line[CH][METER_LINE];
+    __shared__ int red[METER_THREADS / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t base = (int64_t)blockIdx.x * METER_SPAN;
+    const int64_t f0 = base - METER_HALO;  // frame of LDS index 0
+    for (int i = threadIdx.x; i < METER_LINE; i += METER_THREADS) {
+        const int64_t f = f0 + i;
+        const bool ok = f >= 0 && f < N;
+        if constexpr (CH == 2) {
+            int l = 0, r = 0;
+            if (ok) {
+                if constexpr (sizeof(T) == 2) {
+                    const uint32_t d = reinterpret_cast<const uint32_t *>(in)[f];
+                    l = (int16_t)(d & 0xFFFFu);
+                    r = (int16_t)(d >> 16);
+                } else {
+                    const float2 d = reinterpret_cast<const float2 *>(in)[f];
+                    l = meter_sample<float>(d.x);
+                    r = meter_sample<float>(d.y);
+                }
+            }
+            line[0][i] = (int16_t)l;
+            line[1][i] = (int16_t)r;
+        } else {
+            line[0][i] = ok ? (int16_t)meter_sample<T>(in[f]) : (int16_t)0;
+        }
+    }
+    __syncthreads();
+    int pm[METER_FPT];
+#pragma unroll
+    for (int j = 0; j < METER_FPT; ++j) pm[j] = 0;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+        // window w[i] = s[m0 - 12 + i], i < 20, as dwords D[i] = (w[2i], w[2i+1])
+        const uint4 *src = reinterpret_cast<const uint4 *>(&line[c][threadIdx.x * METER_FPT]);
+        const uint4 a = src[0], b = src[1];
+        const uint2 e = *reinterpret_cast<const uint2 *>(src + 2);
+        const uint32_t D[10] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, e.x, e.y};
+        uint32_t P[19];  // P[i] = (w[i], w[i+1])
+#pragma unroll
+        for (int i = 0; i < 19; ++i) P[i] = (i & 1) ? ((D[i / 2] >> 16) | (D[i / 2 + 1] << 16)) : D[i / 2];
+#pragma unroll
+        for (int j = 0; j < METER_FPT; ++j) {
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                int acc = 0;
+#pragma unroll
+                for (int q = 0; q < 6; ++q) acc = tp_dot2(P[j + 11 - 2 * q], tp_pair(p, q), acc);
+                pm[j] = max(pm[j], acc < 0 ? -acc : acc);
+            }
+        }
+    }
+    int best = 0;
+    uint32_t r1[METER_FPT];  // r - 1
+#pragma unroll
+    for (int j = 0; j < METER_FPT; ++j) {
+        best = max(best, pm[j]);
+        r1[j] = pm[j] > Ct ? (uint32_t)(ceil_ratio(Ct, pm[j]) - 1) : (uint32_t)(CEIL_ONE - 1);
+    }
+    uint4 o;
+    o.x = r1[0] | (r1[1] << 16);
+    o.y = r1[2] | (r1[3] << 16);
+    o.z = r1[4] | (r1[5] << 16);
+    o.w = r1[6] | (r1[7] << 16);
+    static_assert(METER_FPT == 8, "one 16-byte store of eight uint16 per thread");
+    *reinterpret_cast<uint4 *>(plane + base + (int64_t)threadIdx.x * METER_FPT) = o;
+    best = wave_max_i32(best);
+    if (lane == 0) red[wave] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < METER_THREADS / 64; ++w) best = max(best, red[w]);
+        if (best) atomicMax(&st->tp0, (unsigned)best);
+    }
+}
+
+typedef unsigned short ceil_u16x2 __attribute__((ext_vector_type(2)));
+
+// both uint16 halves of a dword at once (v_pk_min_u16)
+__device__ __forceinline__ uint32_t ceil_min2(uint32_t a, uint32_t b) {
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(ceil_u16x2, a),
+                                                                  __builtin_bit_cast(ceil_u16x2, b)));
+}
+
+// nxt[e] = min(cur[e], cur[e + off]) for e < n, two entries per dword: the partner pair is
+// a dword for even off and a funnel shift of two neighbours for odd off.  The last dword
+// may cover one entry past n, and the odd form reads one dword further: both stay inside
+// the buffers (CEIL_BUF leaves 5 entries beyond the longest line), and what is computed
+// past n is never read by a valid entry of a later pass.
+__device__ __forceinline__ void ceil_min_pass(const uint16_t *cur, uint16_t *nxt, int n, int off) {
+    const uint32_t *c = reinterpret_cast<const uint32_t *>(cur);
+    uint32_t *o = reinterpret_cast<uint32_t *>(nxt);
+    const int nd = (n + 1) >> 1, d = off >> 1;
+    if (off & 1)
+        for (int i = threadIdx.x; i < nd; i += CEIL_THREADS) o[i] = ceil_min2(c[i], (c[i + d] >> 16) | (c[i + d + 1] << 16));
+    else
+        for (int i = threadIdx.x; i < nd; i += CEIL_THREADS) o[i] = ceil_min2(c[i], c[i + d]);
+    __syncthreads();
+}
+
+// out[i] = min cur[i .. i+K) for i < n_out, cur valid on [0, n_out + K - 1): minima over
+// 2, 4, ... p <= K entries by doubling between the two buffers, then two overlapping
+// windows of p.  Returns the buffer holding the result; every pass ends in a barrier.
+__device__ __forceinline__ uint16_t *ceil_window_min(uint16_t *cur, uint16_t *nxt, int n_out, int K) {
+    int valid = n_out + K - 1, step = 1;
+    while (2 * step <= K) {
+        valid -= step;
+        ceil_min_pass(cur, nxt, valid, step);
+        uint16_t *t = cur;
+        cur = nxt;
+        nxt = t;
+        step *= 2;
+    }
+    ceil_min_pass(cur, nxt, n_out, K - step);
+    return nxt;
+}
+
+template <typename T>
+__device__ __forceinline__ T ceil_scale(T v, int g) {
+    const int s = (meter_sample<T>(v) * g + (1 << 15)) >> 16;  // |s * g| < 2^31: exact, arithmetic shift
+    if constexpr (sizeof(T) == 2) return (T)s;
+    else return (float)s * (1.0f / 32768.0f);
+}
+
+// One workgroup per CEIL_SPAN frames n in [base, base + CEIL_SPAN).  It needs h on
+// [base - W, base + span + W), so R on [base - 2W, base + span + 2W) and r on 11 more:
+// those r - 1 are staged in LDS as uint16 (2^16 - 1 outside the plane).  The whole grid
+// exits at once when TP0 <= C, and a workgroup whose staged r are all 2^16 writes
+// nothing.  The box sums come from one exclusive scan of h in uint32
+// ((span + 2W) * 2^16 < 2^32), divided by 2W + 1 with a multiply-high reciprocal
+// rcp = floor(2^32 / (2W + 1)) and one correction.
+template <int CH, typename T>
+__global__ void __launch_bounds__(CEIL_THREADS) ceil_apply_kernel(T *__restrict__ pcm, int64_t N, int64_t plane_len,
+                                                                  const uint16_t *__restrict__ plane, int C, int W,
+                                                                  unsigned rcp, CeilDev *st) {
+    __shared__ __attribute__((aligned(16))) uint16_t buf_a[CEIL_BUF], buf_b[CEIL_BUF];
+    __shared__ uint32_t ps[CEIL_HLEN + 1];
+    __shared__ uint32_t wsum[CEIL_THREADS / 64], wred[CEIL_THREADS / 64];
+    if (st->tp0 <= (unsigned)C) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t base = (int64_t)blockIdx.x * CEIL_SPAN;
+    const int D = 2 * W + 1;
+    const int n_r = CEIL_SPAN + 4 * W + 11, n_R = CEIL_SPAN + 4 * W, n_h = CEIL_SPAN + 2 * W;
+    const int64_t m_first = base - 2 * W;  // m (and j) of LDS index 0
+    int limited = 0;
+    for (int i = tid; i < n_r; i += CEIL_THREADS) {
+        const int64_t m = m_first + i;
+        const uint16_t v = (m >= 0 && m < plane_len) ? plane[m] : (uint16_t)(CEIL_ONE - 1);
+        buf_a[i] = v;
+        limited |= v != (uint16_t)(CEIL_ONE - 1);
+    }
+    if (!__syncthreads_or(limited)) return;
+    // R - 1, masked to 2^16 - 1 outside [0, N)
+    uint16_t *Rb = ceil_window_min(buf_a, buf_b, n_R, 12);
+    for (int i = tid; i < n_R; i += CEIL_THREADS) {
+        const int64_t j = m_first + i;
+        if (j < 0 || j >= N) Rb[i] = (uint16_t)(CEIL_ONE - 1);
+    }
+    __syncthreads();
+    // h - 1: index u is k = base - W + u
+    const uint16_t *hb = ceil_window_min(Rb, Rb == buf_a ? buf_b : buf_a, n_h, D);
+    // ps[u] = sum of h[v] for v < u
+    const int per = (n_h + CEIL_THREADS - 1) / CEIL_THREADS;
+    const int u0 = min(tid * per, n_h), u1 = min(u0 + per, n_h);
+    uint32_t tot = 0;
+    for (int u = u0; u < u1; ++u) tot += (uint32_t)hb[u] + 1u;
+    uint32_t inc = tot;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t v = __shfl_up(inc, o);
+        if (lane >= o) inc += v;
+    }
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    uint32_t run = inc - tot;
+    for (int w = 0; w < wave; ++w) run += wsum[w];
+    if (tid == 0) ps[0] = 0;
+    for (int u = u0; u < u1; ++u) {
+        run += (uint32_t)hb[u] + 1u;
+        ps[u + 1] = run;
+    }
+    __syncthreads();
+    unsigned count = 0;
+    int red = 0;
+    for (int t = tid; t < CEIL_SPAN; t += CEIL_THREADS) {
+        const int64_t n = base + t;
+        if (n >= N) break;
+        const uint32_t sum = ps[t + D] - ps[t];  // h[n - W .. n + W]
+        uint32_t g = __umulhi(sum, rcp);         // floor(sum / D) or one less
+        g += sum - g * (uint32_t)D >= (uint32_t)D ? 1u : 0u;
+        if (g == (uint32_t)CEIL_ONE) continue;
+        ++count;
+        red = max(red, CEIL_ONE - (int)g);
+        if constexpr (CH == 2 && sizeof(T) == 2) {
+            uint32_t *p = reinterpret_cast<uint32_t *>(pcm) + n;
+            const uint32_t d = *p;
+            const int l = ceil_scale<int16_t>((int16_t)(d & 0xFFFFu), (int)g);
+            const int r = ceil_scale<int16_t>((int16_t)(d >> 16), (int)g);
+            *p = ((uint32_t)l & 0xFFFFu) | ((uint32_t)r << 16);
+        } else if constexpr (CH == 2) {
+            float2 *p = reinterpret_cast<float2 *>(pcm) + n;
+            float2 d = *p;
+            d.x = ceil_scale<float>(d.x, (int)g);
+            d.y = ceil_scale<float>(d.y, (int)g);
+            *p = d;
+        } else {
+            pcm[n] = ceil_scale<T>(pcm[n], (int)g);
+        }
+    }
+    count = wave_sum_u32(count);
+    red = wave_max_i32(red);
+    if (lane == 0) {
+        wsum[wave] = count;
+        wred[wave] = (uint32_t)red;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < CEIL_THREADS / 64; ++w) {
+            count += wsum[w];
+            red = max(red, (int)wred[w]);
+        }
+        if (count) atomicAdd(&st->limited, (unsigned long long)count);
+        if (red) atomicMax(&st->max_red, (unsigned)red);
+    }
+}
+
+// The static trim: every sample by g (pointwise, in place).
+template <typename T>
+__global__ void __launch_bounds__(256) ceil_trim_kernel(T *__restrict__ pcm, int64_t n, int g) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) pcm[i] = ceil_scale<T>(pcm[i], g);
+}
+
+}  // namespace mm
+
+// ======================================================= host entry points
+namespace {
+
+void ceiling_clear(mm_ceiling *o, int64_t frames, int channels, int32_t C, int32_t W) {
+    memset(o, 0, sizeof *o);
+    o->frames = frames;
+    o->channels = channels;
+    o->ceiling_q28 = C;
+    o->window = W;
+    o->min_gain_q16 = CEIL_ONE;
+    o->trim_q16 = CEIL_ONE;
+}
+
+// why (C, W, frames, channels) is not a ceiling job, or null
+const char *ceiling_bad_args(int64_t frames, int channels, int32_t C, int32_t W) {
+    if (channels != 1 && channels != 2) return "channels must be 1 or 2";
+    if (C < (1 << 24) || C > (1 << 28)) return "ceiling_q28 out of range [2^24, 2^28]";
+    if (W < 1 || W > CEIL_MAX_W) return "ceiling window out of range [1, 1024]";
+    if (frames < 0 || frames >= ((int64_t)1 << 31) - METER_SPAN) return "frames out of range";
+    return nullptr;
+}
+
+// The chain's window: round-half-even(rate / 200) = 5 ms, within [1, 1024]
+// (design.ceiling_window).
+int ceiling_window(int rate) {
+    int q = rate / 200;
+    const int rem = rate % 200;
+    if (rem > 100 || (rem == 100 && (q & 1))) ++q;
+    return std::min(CEIL_MAX_W, std::max(1, q));
+}
+
+}  // namespace
+
+// The ceiling on a device-resident signal, in place (synchronous on return): need, apply
+// and the meter pass behind one sync; the trim and its meter pass behind one more.
+static int ceiling_device(mm_ctx *c, void *d_pcm, int kind, int64_t frames, int channels, int32_t C, int32_t W,
+                          mm_ceiling *out) {
+    if (!c || !out || (frames > 0 && !d_pcm)) return set_err(c, MM_ERR_ARG, "bad arguments");
+    if (kind != MM_OUT_I16 && kind != MM_OUT_F32) return set_err(c, MM_ERR_ARG, "kind %d (MM_OUT_I16 | MM_OUT_F32)", kind);
+    if (const char *why = ceiling_bad_args(frames, channels, C, W)) return set_err(c, MM_ERR_ARG, "%s", why);
+    ceiling_clear(out, frames, channels, C, W);
+    if (frames == 0) return MM_OK;
+    const int Ct = C - CEIL_GUARD;
+    const int64_t spans = (frames + 11 + METER_SPAN - 1) / METER_SPAN, plane_len = spans * METER_SPAN;
+    uint16_t *plane;
+    CeilDev *st;
+    MeterDev *res;
+    RET(get_buf(c, "ceil_r", (size_t)plane_len, &plane));
+    RET(get_buf(c, "ceil_res", 1, &st));
+    RET(get_buf(c, "meter_res", 1, &res));
+    HIPCHK(c, hipMemsetAsync(st, 0, sizeof(CeilDev), c->stream));
+    const dim3 gn((unsigned)spans), bn(METER_THREADS);
+    const dim3 ga((unsigned)((frames + CEIL_SPAN - 1) / CEIL_SPAN)), ba(CEIL_THREADS);
+    const unsigned rcp = (unsigned)(((uint64_t)1 << 32) / (uint64_t)(2 * W + 1));
+    if (kind == MM_OUT_I16) {
+        int16_t *p = static_cast<int16_t *>(d_pcm);
+        if (channels == 2) {
+            RET(launch(c, "ceil_need", ceil_need_kernel<2, int16_t>, gn, bn, 0, (const int16_t *)p, frames, Ct, plane, st));
+            RET(launch(c, "ceil_apply", ceil_apply_kernel<2, int16_t>, ga, ba, 0, p, frames, plane_len,
+                       (const uint16_t *)plane, (int)C, (int)W, rcp, st));
+        } else {
+            RET(launch(c, "ceil_need", ceil_need_kernel<1, int16_t>, gn, bn, 0, (const int16_t *)p, frames, Ct, plane, st));
+            RET(launch(c, "ceil_apply", ceil_apply_kernel<1, int16_t>, ga, ba, 0, p, frames, plane_len,
+                       (const uint16_t *)plane, (int)C, (int)W, rcp, st));
+        }
+    } else {
+        float *p = static_cast<float *>(d_pcm);
+        if (channels == 2) {
+            RET(launch(c, "ceil_need", ceil_need_kernel<2, float>, gn, bn, 0, (const float *)p, frames, Ct, plane, st));
+            RET(launch(c, "ceil_apply", ceil_apply_kernel<2, float>, ga, ba, 0, p, frames, plane_len,
+                       (const uint16_t *)plane, (int)C, (int)W, rcp, st));
+        } else {
+            RET(launch(c, "ceil_need", ceil_need_kernel<1, float>, gn, bn, 0, (const float *)p, frames, Ct, plane, st));
+            RET(launch(c, "ceil_apply", ceil_apply_kernel<1, float>, ga, ba, 0, p, frames, plane_len,
+                       (const uint16_t *)plane, (int)C, (int)W, rcp, st));
+        }
+    }
+    RET(meter_launch(c, d_pcm, kind, frames, channels, res));
+    CeilDev hs;
+    MeterDev hm;
+    HIPCHK(c, hipMemcpyAsync(&hs, st, sizeof hs, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&hm, res, sizeof hm, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    auto linked = [&](const MeterDev &m) {
+        int32_t tp = 0;
+        for (int ch = 0; ch < channels; ++ch) tp = std::max(tp, (int32_t)(m.key[ch] >> 32));
+        return tp;
+    };
+    out->tp_in_q28 = (int32_t)hs.tp0;
+    out->tp_limited_q28 = out->tp_out_q28 = linked(hm);
+    out->min_gain_q16 = CEIL_ONE - (int32_t)hs.max_red;
+    out->limited_frames = (int64_t)hs.limited;
+    if (out->tp_limited_q28 > C) {  // the residue: one static trim, provably under C
+        const int gt = (int)(((int64_t)Ct << 16) / out->tp_limited_q28);
+        const int64_t n = frames * channels;
+        if (kind == MM_OUT_I16)
+            RET(launch(c, "ceil_trim", ceil_trim_kernel<int16_t>, dim3(pw_blocks(n)), dim3(256), 0,
+                       static_cast<int16_t *>(d_pcm), n, gt));
+        else
+            RET(launch(c, "ceil_trim", ceil_trim_kernel<float>, dim3(pw_blocks(n)), dim3(256), 0,
+                       static_cast<float *>(d_pcm), n, gt));
+        RET(meter_launch(c, d_pcm, kind, frames, channels, res));
+        HIPCHK(c, hipMemcpyAsync(&hm, res, sizeof hm, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        out->trim_q16 = gt;
+        out->tp_out_q28 = linked(hm);
+    }
+    resolve_events(c);
+    return MM_OK;
+}
+
+// The chain's hook: the ceiling of track `slot` of `n` of the current master call.
+static int chain_ceiling(mm_ctx *c, const mm_job *j, void *d_out, int slot, int n) {
+    if (slot == 0) c->ceilings.assign((size_t)n, mm_ceiling{});
+    mm_ceiling *m = &c->ceilings[(size_t)slot];
+    if (!j->ceiling_q28) {
+        memset(m, 0, sizeof *m);
+        m->channels = j->channels;
+        return MM_OK;
+    }
+    return ceiling_device(c, d_out, j->out_kind, j->frames_proc, j->channels, j->ceiling_q28, ceiling_window(j->rate), m);
+}
+
+extern "C" {
+
+int mm_ceiling_span(void) { return CEIL_SPAN; }
+
+int mm_ceiling_max_window(void) { return CEIL_MAX_W; }
+
+int mm_ceiling_device(mm_ctx *c, void *d_pcm, int kind, int64_t frames, int channels, int32_t ceiling_q28,
+                      int32_t window, mm_ceiling *out) {
+    if (!c) return MM_ERR_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    return ceiling_device(c, d_pcm, kind, frames, channels, ceiling_q28, window, out);
+}
+
+int mm_ceiling_pcm(mm_ctx *c, void *pcm, int kind, int64_t frames, int channels, int32_t ceiling_q28, int32_t window,
+                   mm_ceiling *out) {
+    if (!c) return MM_ERR_ARG;
+    if (!out || (frames > 0 && !pcm) || (kind != MM_OUT_I16 && kind != MM_OUT_F32))
+        return set_err(c, MM_ERR_ARG, "bad arguments");
+    if (const char *why = ceiling_bad_args(frames, channels, ceiling_q28, window)) return set_err(c, MM_ERR_ARG, "%s", why);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)frames * channels * (kind == MM_OUT_I16 ? 2 : 4);
+    char *dio;
+    RET(get_buf(c, "ceil_io", std::max<size_t>(bytes, 1), &dio));
+    if (bytes) HIPCHK(c, hipMemcpyAsync(dio, pcm, bytes, hipMemcpyHostToDevice, c->stream));
+    RET(ceiling_device(c, dio, kind, frames, channels, ceiling_q28, window, out));
+    if (bytes && out->tp_in_q28 > ceiling_q28) {  // (an untouched signal is not copied back)
+        HIPCHK(c, hipMemcpyAsync(pcm, dio, bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return MM_OK;
+}
+
+int mm_last_ceilings(mm_ctx *c, int cap, mm_ceiling *out) {
+    if (!c || cap < 0 || (cap > 0 && !out)) return set_err(c, MM_ERR_ARG, "bad arguments");
+    if (c->ceilings.empty()) return set_err(c, MM_ERR_STATE, "the last master call set no ceiling");
+    const int n = (int)c->ceilings.size();
+    for (int i = 0; i < std::min(n, cap); ++i) out[i] = c->ceilings[(size_t)i];
+    return n;
+}
+
+// The definition restated in plain C++ on the host (no context, no GPU), in place on
+// interleaved int16: what the three kernels must reproduce, samples and statistics.
+int mm_ceiling_host(int16_t *pcm, int64_t frames, int channels, int32_t C, int32_t W, mm_ceiling *out) {
+    if (!out || (frames > 0 && !pcm) || ceiling_bad_args(frames, channels, C, W)) return MM_ERR_ARG;
+    constexpr TpTaps t = tp_taps();
+    ceiling_clear(out, frames, channels, C, W);
+    if (frames == 0) return MM_OK;
+    const int64_t N = frames, M = N + 11;
+    const int64_t Ct = C - CEIL_GUARD;
+    std::vector<int32_t> P((size_t)M);
+    auto measure = [&]() {  // P[m], returns its maximum (the linked true peak)
+        int32_t tp = 0;
+        for (int64_t m = 0; m < M; ++m) {
+            int32_t pm = 0;
+            for (int c = 0; c < channels; ++c)
+                for (int p = 0; p < 4; ++p) {
+                    int32_t acc = 0;
+                    for (int k = 0; k < 12; ++k) {
+                        const int64_t f = m - k;
+                        if (f >= 0 && f < N) acc += t.c[p][k] * (int32_t)pcm[f * channels + c];
+                    }
+                    pm = std::max(pm, acc < 0 ? -acc : acc);
+                }
+            P[(size_t)m] = pm;
+            tp = std::max(tp, pm);
+        }
+        return tp;
+    };
+    auto scale = [&](int64_t n, int32_t g) {
+        for (int c = 0; c < channels; ++c) {
+            int16_t &s = pcm[n * channels + c];
+            const int32_t v = (int32_t)s * g + (1 << 15);
+            s = (int16_t)(v >= 0 ? v >> 16 : -((-v + 65535) >> 16));  // floor(v / 2^16): the arithmetic shift
+        }
+    };
+    out->tp_in_q28 = out->tp_limited_q28 = out->tp_out_q28 = measure();
+    if (out->tp_in_q28 <= C) return MM_OK;
+    std::vector<int32_t> R((size_t)N), h((size_t)(N + 2 * (int64_t)W));
+    for (int64_t n = 0; n < N; ++n) {
+        int32_t v = CEIL_ONE;
+        for (int64_t m = n; m < n + 12; ++m)
+            v = std::min(v, P[(size_t)m] <= Ct ? CEIL_ONE : (int32_t)((Ct << 16) / P[(size_t)m]));
+        R[(size_t)n] = v;
+    }
+    for (int64_t k = -W; k < N + W; ++k) {  // h[k] at index k + W; R = 2^16 outside [0, N)
+        int32_t v = CEIL_ONE;
+        for (int64_t j = std::max<int64_t>(k - W, 0); j <= std::min<int64_t>(k + W, N - 1); ++j) v = std::min(v, R[(size_t)j]);
+        h[(size_t)(k + W)] = v;
+    }
+    int64_t sum = 0;
+    for (int64_t u = 0; u < 2 * (int64_t)W; ++u) sum += h[(size_t)u];
+    for (int64_t n = 0; n < N; ++n) {  // the box over h[n - W .. n + W] = indices n .. n + 2W
+        sum += h[(size_t)(n + 2 * W)];
+        const int32_t g = (int32_t)(sum / (2 * W + 1));
+        sum -= h[(size_t)n];
+        if (g == CEIL_ONE) continue;
+        ++out->limited_frames;
+        out->min_gain_q16 = std::min(out->min_gain_q16, g);
+        scale(n, g);
+    }
+    out->tp_limited_q28 = out->tp_out_q28 = measure();
+    if (out->tp_limited_q28 > C) {
+        out->trim_q16 = (int32_t)((Ct << 16) / out->tp_limited_q28);
+        for (int64_t n = 0; n < N; ++n) scale(n, out->trim_q16);
+        out->tp_out_q28 = measure();
+    }
+    return MM_OK;
+}
+
+}  // extern "C"

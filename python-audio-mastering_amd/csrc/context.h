@@ -91,6 +91,8 @@ struct mm_ctx {
     std::vector<mm_ctx *> children;
     // mastering report of the last master call (mm_last_meters; empty: it did not meter)
     std::vector<mm_meter> meters;
+    // ceilings of the last master call (mm_last_ceilings; empty: no job set one)
+    std::vector<mm_ceiling> ceilings;
     // rccl
     ncclComm_t comm = nullptr;
     int rank = 0, nranks = 1;

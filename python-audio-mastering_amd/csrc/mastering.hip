@@ -1,8 +1,8 @@
 // mastering.hip — host side of the C-ABI (include/mastering.h), one translation
 // unit: the launch sequence of the chain (a unit of n >= 1 tracks between two
 // syncs), loudness gating, the batch scheduler and the staged / time-sharded entry
-// points.  The context is context.h; wav.hip, comm.hip, ops.hip and meter.hip are
-// included at the end.
+// points.  The context is context.h; wav.hip, comm.hip, ops.hip, meter.hip and
+// ceiling.hip are included at the end.
 #include <rccl/rccl.h>
 
 #include <algorithm>
@@ -26,6 +26,8 @@ using namespace mm;
 
 // meter.hip: meter track `slot` of `n` of the current master call into c->meters
 static int chain_meter(mm_ctx *c, const mm_job *j, const void *d_out, int slot, int n);
+// ceiling.hip: hold track `slot` of `n` under its job's true-peak ceiling, into c->ceilings
+static int chain_ceiling(mm_ctx *c, const mm_job *j, void *d_out, int slot, int n);
 
 // ------------------------------------------------------- look-back plumbing
 // Transition tables of one filter stage (uploaded only when they change).
@@ -140,6 +142,8 @@ static int validate(mm_ctx *c, const mm_job *j) {
     if (j->frames_proc >= (int64_t)1 << 31 || j->frames_in >= (int64_t)1 << 31)
         return set_err(c, MM_ERR_ARG, "track longer than 2^31 frames (32-bit frame indexing)");
     if (j->eq.nsec < 0 || j->eq.nsec > 4) return set_err(c, MM_ERR_ARG, "eq.nsec %d", j->eq.nsec);
+    if (j->ceiling_q28 && (j->ceiling_q28 < (1 << 24) || j->ceiling_q28 > (1 << 28)))
+        return set_err(c, MM_ERR_ARG, "ceiling_q28 %d out of range [2^24, 2^28]", j->ceiling_q28);
     const int tpb = LB_THREADS / j->channels;
     if (j->eq.nsec > 0 && j->eq.tpb != tpb) return set_err(c, MM_ERR_ARG, "eq tables built for %d tiles/block, need %d", j->eq.tpb, tpb);
     if (j->multiband_on && j->xover.tpb != tpb) return set_err(c, MM_ERR_ARG, "crossover tables built for %d tiles/block", j->xover.tpb);
@@ -1429,12 +1433,14 @@ static int unit_complete(mm_ctx *c, const Unit &u, mm_result *res) {
 
 static int master_device(mm_ctx *c, const mm_job *j, const void *d_in, void *d_out, mm_result *res) {
     c->meters.clear();
+    c->ceilings.clear();
     Unit u;
     u.J = j;
     u.in = &d_in;
     u.out = &d_out;
     RET(unit_enqueue(c, u));
     RET(unit_complete(c, u, res));
+    if (j->ceiling_q28) RET(chain_ceiling(c, j, d_out, 0, 1));  // before the report: it measures what is delivered
     return j->meter_on ? chain_meter(c, j, d_out, 0, 1) : MM_OK;
 }
 
@@ -1578,6 +1584,7 @@ int mm_master_batch(mm_ctx *c, int n, const mm_job *jobs, const void *const *d_i
     HIPCHK(c, hipSetDevice(c->device));
     for (int i = 0; i < n; ++i) RET(validate(c, &jobs[i]));
     c->meters.clear();
+    c->ceilings.clear();
     std::vector<Unit> units = batch_units(jobs, d_in, d_out, n);
     const int nu = (int)units.size();
     const int S = std::min(nu, MM_BATCH_STREAMS);
@@ -1630,8 +1637,10 @@ int mm_master_batch(mm_ctx *c, int n, const mm_job *jobs, const void *const *d_i
         k->stats.clear();
         k->stat_order.clear();
     }
-    bool meter = false;
+    bool meter = false, ceiling = false;
     for (int i = 0; i < n; ++i) meter = meter || jobs[i].meter_on;
+    for (int i = 0; i < n; ++i) ceiling = ceiling || jobs[i].ceiling_q28;
+    for (int i = 0; i < n && ceiling; ++i) RET(chain_ceiling(c, &jobs[i], d_out[i], i, n));
     for (int i = 0; i < n && meter; ++i) RET(chain_meter(c, &jobs[i], d_out[i], i, n));
     return MM_OK;
 }
@@ -1829,3 +1838,4 @@ int mm_kernel_stats(mm_ctx *c, char *names, int names_cap, double *total_ms, int
 #include "comm.hip"
 #include "ops.hip"
 #include "meter.hip"
+#include "ceiling.hip"

@@ -270,6 +270,23 @@ bool meter_has_geometry(const mm_job *loud, int64_t frames) {
 
 }  // namespace
 
+// Queue one metering pass of a device-resident signal on the context's stream: the
+// result block (zeroed on the stream first) is read by the caller after its sync.
+// frames in [1, 2^31 - METER_SPAN), kind and channels already checked.
+static int meter_launch(mm_ctx *c, const void *d_pcm, int kind, int64_t frames, int channels, MeterDev *res) {
+    HIPCHK(c, hipMemsetAsync(res, 0, sizeof(MeterDev), c->stream));
+    const int64_t spans = (frames + 11 + METER_SPAN - 1) / METER_SPAN;
+    const dim3 grid((unsigned)std::min<int64_t>(spans, (int64_t)METER_WGS_PER_CU * c->n_cus)), block(METER_THREADS);
+    if (kind == MM_OUT_I16) {
+        const int16_t *p = static_cast<const int16_t *>(d_pcm);
+        if (channels == 2) return launch(c, "meter_i16", meter_i16_kernel<2, int16_t>, grid, block, 0, p, frames, spans, res);
+        return launch(c, "meter_i16", meter_i16_kernel<1, int16_t>, grid, block, 0, p, frames, spans, res);
+    }
+    const float *p = static_cast<const float *>(d_pcm);
+    if (channels == 2) return launch(c, "meter_i16", meter_i16_kernel<2, float>, grid, block, 0, p, frames, spans, res);
+    return launch(c, "meter_i16", meter_i16_kernel<1, float>, grid, block, 0, p, frames, spans, res);
+}
+
 // Meter a device-resident signal on the context's stream (synchronous on return).
 static int meter_device(mm_ctx *c, const void *d_pcm, int kind, int64_t frames, int channels, const mm_job *loud,
                         mm_meter *out) {
@@ -285,18 +302,7 @@ static int meter_device(mm_ctx *c, const void *d_pcm, int kind, int64_t frames, 
                        loud->channels);
     MeterDev *res;
     RET(get_buf(c, "meter_res", 1, &res));
-    HIPCHK(c, hipMemsetAsync(res, 0, sizeof(MeterDev), c->stream));
-    const int64_t spans = (frames + 11 + METER_SPAN - 1) / METER_SPAN;
-    const dim3 grid((unsigned)std::min<int64_t>(spans, (int64_t)METER_WGS_PER_CU * c->n_cus)), block(METER_THREADS);
-    if (kind == MM_OUT_I16) {
-        const int16_t *p = static_cast<const int16_t *>(d_pcm);
-        if (channels == 2) RET(launch(c, "meter_i16", meter_i16_kernel<2, int16_t>, grid, block, 0, p, frames, spans, res));
-        else RET(launch(c, "meter_i16", meter_i16_kernel<1, int16_t>, grid, block, 0, p, frames, spans, res));
-    } else {
-        const float *p = static_cast<const float *>(d_pcm);
-        if (channels == 2) RET(launch(c, "meter_i16", meter_i16_kernel<2, float>, grid, block, 0, p, frames, spans, res));
-        else RET(launch(c, "meter_i16", meter_i16_kernel<1, float>, grid, block, 0, p, frames, spans, res));
-    }
+    RET(meter_launch(c, d_pcm, kind, frames, channels, res));
     MeterDev h;
     HIPCHK(c, hipMemcpyAsync(&h, res, sizeof h, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -187,6 +187,27 @@ TRUE_PEAK_TAPS = np.array([_TRUE_PEAK_C[0], _TRUE_PEAK_C[1], _TRUE_PEAK_C[1][::-
                           dtype=np.float64) / 8192.0
 TRUE_PEAK_TAPS.setflags(write=False)
 
+# The true-peak ceiling (include/mastering.h: mm_ceiling).  The library works on the
+# integer ceiling alone and never evaluates a power.
+CEILING_MAX_WINDOW = 1024  # mm_ceiling_max_window()
+
+
+def ceiling_q28(db: float) -> int:
+    """A ceiling in dBTP as mm_job.ceiling_q28: floor(10**(db/20) * 2**28), for db in [-24, 0]."""
+    db = float(db)
+    if not -24.0 <= db <= 0.0:  # (NaN fails both comparisons)
+        raise ValueError(f"true-peak ceiling {db!r} dBTP outside [-24, 0]")
+    return int(math.floor(10.0 ** (db / 20.0) * 2.0 ** 28))
+
+
+def ceiling_window(rate: int) -> int:
+    """The chain's look-ahead window in frames: 5 ms, round-half-even(rate / 200) computed
+    in integers (220 at 44.1 kHz), within [1, CEILING_MAX_WINDOW]."""
+    q, rem = divmod(int(rate), 200)
+    if rem > 100 or (rem == 100 and q % 2 == 1):
+        q += 1
+    return min(CEILING_MAX_WINDOW, max(1, q))
+
 
 def crossover_sections(rate, low_hz=LOW_CROSSOVER, high_hz=HIGH_CROSSOVER):
     """AME:197-198: butter(4) LP and HP as 2 SOS sections each."""

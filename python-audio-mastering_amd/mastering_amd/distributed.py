@@ -348,6 +348,8 @@ def master_time_sharded(backend, plan: RankPlan, params: dict, d_in, d_out, coll
     """Run this rank's share of a time-sharded track (steps 1-5 above).
     `d_in` holds the rank's input slice [plan.in_lo, plan.in_hi) (decoded f32);
     `d_out` receives its processed frames [plan.f0, plan.f1)."""
+    if params.get("ceiling_dbtp") is not None:
+        raise ValueError("the true-peak ceiling needs the whole track: not available on the time-sharded path")
     # checked before any work or collective: the path depends only on the collective's
     # kind and the plan, the same on every rank (raises since round 5; see INTEGRATION.md)
     if isinstance(coll, LibraryCollectives) and (coll.ctx is not getattr(backend, "ctx", None)

@@ -51,7 +51,8 @@ class Job:
 
     def __init__(self, frames_in: int, rate: int, channels: int, params: dict, out_kind: int = native.MM_OUT_I16,
                  seg_bounds=None, check_length: bool = True, single_chunk: bool = False,
-                 crossover=(design.LOW_CROSSOVER, design.HIGH_CROSSOVER), report: bool = False):
+                 crossover=(design.LOW_CROSSOVER, design.HIGH_CROSSOVER), report: bool = False,
+                 ceiling_dbtp: float | None = None):
         """`seg_bounds` (time-sharded ranks, distributed.py): this range's loudness
         segment bounds relative to its first frame; the whole-track gating then
         happens on the host after the all-reduce.  `check_length=False` skips
@@ -61,7 +62,12 @@ class Job:
         chunks; `crossover`: apply_multiband_compressor's (low, high) Hz.  `report`:
         meter the delivered output at the end of the chain (mm_job.meter_on); its
         loudness is measured too whenever the track spans one 0.4 s block, with or
-        without a LUFS target."""
+        without a LUFS target.  `ceiling_dbtp` (in [-24, 0]): hold the delivered output
+        under this true-peak ceiling (mm_job.ceiling_q28, design.ceiling_q28) after the
+        chain and before the report; not on a time-sharded range, whose rank does not
+        hold its neighbours' frames."""
+        if ceiling_dbtp is not None and seg_bounds is not None:
+            raise ValueError("the true-peak ceiling needs the whole track: not available on a time-sharded range")
         if channels not in (1, 2):
             raise ValueError("only mono and stereo are supported (AME:119,137,152)")
         params = dict(params or {})
@@ -130,6 +136,8 @@ class Job:
         j.comp_max_iters = COMP_MAX_ITERS
         j.comp_super = comp_super_frames(self.rate, self.tile)
         j.meter_on = int(bool(report))
+        self.ceiling_dbtp = None if ceiling_dbtp is None else float(ceiling_dbtp)
+        j.ceiling_q28 = 0 if ceiling_dbtp is None else design.ceiling_q28(ceiling_dbtp)
         # --- loudness (with `report` alone: the geometry only, for the meter)
         if lufs is not None or (report and self.frames_proc >= 0.4 * self.rate):
             self._fill_iir(j.kweight, design.kweight_sections(self.rate), [2],
@@ -238,6 +246,52 @@ def _add_report(info: dict, job: "Job", ctx: native.Context) -> dict:
     return info
 
 
+def ceiling_dict(m: native.MMCeiling) -> dict:
+    """An mm_ceiling as `info["ceiling"]`: the struct's integers, the ceiling and the linked
+    true peak before and after in dBTP, the largest gain reduction in dB (limiter and
+    trim together) and whether the static trim ran.  No reference counterpart."""
+    d = {f: int(getattr(m, f)) for f, _ in native.MMCeiling._fields_}
+    d["ceiling_dbtp"] = _db(d["ceiling_q28"] / 2.0 ** 28)
+    d["tp_in_dbtp"] = _db(d["tp_in_q28"] / 2.0 ** 28)
+    d["tp_out_dbtp"] = _db(d["tp_out_q28"] / 2.0 ** 28)
+    d["max_reduction_db"] = -_db(d["min_gain_q16"] / 65536.0) - _db(d["trim_q16"] / 65536.0)
+    d["trimmed"] = d["trim_q16"] != 65536
+    return d
+
+
+def ceilings(ctx: native.Context, cap: int = native.BATCH_STREAMS) -> list:
+    """The mm_ceiling of every track of the context's last master call (mm_last_ceilings):
+    one for master_device, one per job for master_batch, in job order (frames 0: that
+    job set none).  RuntimeError if no job of that call had `ceiling_dbtp`."""
+    arr = (native.MMCeiling * max(cap, 1))()
+    n = ctx.check(ctx.lib.mm_last_ceilings(ctx.ptr, cap, arr), "mm_last_ceilings")
+    if n > cap:
+        return ceilings(ctx, n)
+    return list(arr[:n])
+
+
+def _add_ceiling(info: dict, job: "Job", ctx: native.Context) -> dict:
+    if job.job.ceiling_q28:
+        info["ceiling"] = ceiling_dict(ceilings(ctx, 1)[0])
+    return info
+
+
+def ceiling_pcm(pcm: np.ndarray, rate: int, ceiling_dbtp: float, window: int | None = None, device: int = 0):
+    """Hold an int16 (or float32 = int16 / 32768) array [N] or [N, ch] under a true-peak
+    ceiling without mastering it (mm_ceiling_pcm): returns (a new array, ceiling_dict).
+    `window`: look-ahead frames (default design.ceiling_window(rate))."""
+    ch = 1 if pcm.ndim == 1 else pcm.shape[1]
+    x, in_kind = _device_input(pcm)
+    x = x.copy()
+    kind = native.MM_OUT_I16 if in_kind == native.MM_IN_I16 else native.MM_OUT_F32
+    w = design.ceiling_window(rate) if window is None else int(window)
+    ctx = native.context(device)
+    m = native.MMCeiling()
+    ctx.check(ctx.lib.mm_ceiling_pcm(ctx.ptr, x.ctypes.data_as(ctypes.c_void_p), kind, x.shape[0], ch,
+                                     design.ceiling_q28(ceiling_dbtp), w, ctypes.byref(m)), "mm_ceiling_pcm")
+    return x, ceiling_dict(m)
+
+
 def meter_pcm(pcm: np.ndarray, rate: int, loudness: bool = True, device: int = 0) -> dict:
     """Meter an int16 (or float32 = int16 / 32768) array [N] or [N, ch] without
     mastering it: the report of `report_dict` (mm_meter_pcm)."""
@@ -256,11 +310,14 @@ def meter_pcm(pcm: np.ndarray, rate: int, loudness: bool = True, device: int = 0
 def master_pcm(pcm: np.ndarray, rate: int, params: dict, out_kind: int = native.MM_OUT_I16, device: int = 0):
     """Run the whole chain (AME:48-89) on a PCM array [N] or [N, ch] on the GPU.
     Returns (out_pcm, info) with out_pcm int16 (or f32 = int16/32768).
-    params['report'] (truthy) adds info['report'] (report_dict) on the output."""
+    params['report'] (truthy) adds info['report'] (report_dict) on the output;
+    params['ceiling_dbtp'] holds the output under that true-peak ceiling first and adds
+    info['ceiling'] (ceiling_dict)."""
     ch = 1 if pcm.ndim == 1 else pcm.shape[1]
     params = dict(params or {})
     report = bool(params.pop("report", False))
-    job = Job(pcm.shape[0], rate, ch, params, out_kind, report=report)
+    ceiling = params.pop("ceiling_dbtp", None)
+    job = Job(pcm.shape[0], rate, ch, params, out_kind, report=report, ceiling_dbtp=ceiling)
     x, job.job.in_kind = _device_input(pcm)
     shape = (job.frames_proc,) if ch == 1 else (job.frames_proc, ch)
     out = np.empty(shape, np.int16 if out_kind == native.MM_OUT_I16 else np.float32)
@@ -268,7 +325,7 @@ def master_pcm(pcm: np.ndarray, rate: int, params: dict, out_kind: int = native.
     res = native.MMResult()
     ctx.check(ctx.lib.mm_master(ctx.ptr, ctypes.byref(job.job), x.ctypes.data_as(ctypes.c_void_p),
                                 out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(res)), "mm_master")
-    return out, _add_report(_info(job, res), job, ctx)
+    return out, _add_report(_add_ceiling(_info(job, res), job, ctx), job, ctx)
 
 
 def wav_info(path: str, device: int = 0) -> native.MMWavInfo:
@@ -282,7 +339,8 @@ def wav_info(path: str, device: int = 0) -> native.MMWavInfo:
 def master_device(ctx: native.Context, job: Job, d_in: int, d_out: int, res: native.MMResult | None = None):
     """Device-resident variant (pointers from e.g. torch tensors).  With `res`
     the loudness, gain and compressor statistics are returned in it.  A job planned
-    with `report=True` is metered: `meters(ctx)[0]` (see report_dict)."""
+    with `report=True` is metered: `meters(ctx)[0]` (see report_dict); one planned with
+    `ceiling_dbtp` is held under it first: `ceilings(ctx)[0]` (see ceiling_dict)."""
     ctx.check(ctx.lib.mm_master_device(ctx.ptr, ctypes.byref(job.job), ctypes.c_void_p(d_in),
                                        ctypes.c_void_p(d_out), ctypes.byref(res) if res is not None else None),
               "mm_master_device")
@@ -295,7 +353,8 @@ def master_batch(ctx: native.Context, jobs, d_ins, d_outs, with_results: bool = 
     whole chunks, every stage launched once for the batch); otherwise up to
     native.BATCH_STREAMS of them are in flight at once, each on its own stream.
     Returns one MMResult per job (or None).  Jobs planned with `report=True` are
-    metered: `meters(ctx, len(jobs))` holds one mm_meter per job, in job order."""
+    metered: `meters(ctx, len(jobs))` holds one mm_meter per job, in job order; jobs
+    planned with `ceiling_dbtp` are held under it: `ceilings(ctx, len(jobs))`."""
     n = len(jobs)
     arr = (native.MMJob * n)(*[j.job for j in jobs])
     ins = (ctypes.c_void_p * n)(*[ctypes.c_void_p(int(p)) for p in d_ins])
@@ -309,22 +368,24 @@ def process(input_path: str, output_path: str, params: dict, device: int = 0, ve
     """Master `input_path` (16-bit PCM or 32-bit float WAV) into `output_path`
     (16-bit PCM WAV, as AME:98 exports; params['output_format']='f32' writes float).
     The file streams through pinned staging into HBM and back (mm_master_wav).
-    params['report'] (truthy) adds info['report'] (report_dict) on the written samples.
+    params['report'] (truthy) adds info['report'] (report_dict) on the written samples;
+    params['ceiling_dbtp'] holds them under that true-peak ceiling (info['ceiling']).
     Raises ValueError for unreadable/unsupported input and RuntimeError for device
     failures, like the reference (AME:110-113)."""
     params = dict(params or {})
     fmt = params.pop("output_format", "pcm16")
     report = bool(params.pop("report", False))
+    ceiling = params.pop("ceiling_dbtp", None)
     kind = native.MM_OUT_F32 if fmt == "f32" else native.MM_OUT_I16
     wi = wav_info(input_path, device)
     if verbose:
         print(f"Loaded {input_path}: {wi.frames} frames @ {wi.rate} Hz")
-    job = Job(wi.frames, wi.rate, wi.channels, params, kind, report=report)
+    job = Job(wi.frames, wi.rate, wi.channels, params, kind, report=report, ceiling_dbtp=ceiling)
     ctx = native.context(device)
     res = native.MMResult()
     ctx.check(ctx.lib.mm_master_wav(ctx.ptr, ctypes.byref(job.job), os.fsencode(input_path), os.fsencode(output_path),
                                     ctypes.byref(res)), "mm_master_wav")
-    info = _add_report(_info(job, res), job, ctx)
+    info = _add_report(_add_ceiling(_info(job, res), job, ctx), job, ctx)
     if verbose and info["loudness"] is not None:
         print(f"Current loudness: {info['loudness']:.2f} LUFS. Applying {info['gain_db']:.2f} dB gain...")
     info["output_path"] = os.path.abspath(output_path)

@@ -66,11 +66,20 @@ def report_line(report: dict) -> str:
     return f"{head}true peak {report['max_true_peak_dbtp']:.2f} dBTP"
 
 
+def ceiling_line(ceiling: dict) -> str:
+    """One status line for a true-peak ceiling (engine.ceiling_dict):
+    `Ceiling -1.00 dBTP: true peak +4.76 -> -1.02 dBTP, up to 5.78 dB reduction`."""
+    return (f"Ceiling {ceiling['ceiling_dbtp']:.2f} dBTP: true peak {ceiling['tp_in_dbtp']:+.2f} -> "
+            f"{ceiling['tp_out_dbtp']:+.2f} dBTP, up to {ceiling['max_reduction_db']:.2f} dB reduction")
+
+
 def process_audio(settings: dict, status_callback=None, device: int = 0):
     """Master settings['input_file'] into settings['output_file'] (mastering_gui.py:192-206).
     Reports through `status_callback`; returns the engine's info dict, or None on error.
     With a truthy settings['report'] the delivered output is metered (info['report'])
-    and one extra status line (report_line) precedes the completion message."""
+    and one extra status line (report_line) precedes the completion message; with
+    settings['ceiling_dbtp'] the output is held under that true-peak ceiling
+    (info['ceiling']) and ceiling_line is reported before it."""
     cb = _status(status_callback)
     src, dst = (settings or {}).get("input_file"), (settings or {}).get("output_file")
     if not src or not dst:
@@ -82,6 +91,8 @@ def process_audio(settings: dict, status_callback=None, device: int = 0):
     except Exception as e:  # the GUI shows the message; AME:110-113 re-raises to its caller
         cb(f"Error: {e}")
         return None
+    if isinstance(info, dict) and info.get("ceiling"):
+        cb(ceiling_line(info["ceiling"]))
     if isinstance(info, dict) and info.get("report"):
         cb(report_line(info["report"]))
     cb(f"Processing complete: {os.path.basename(dst)}")

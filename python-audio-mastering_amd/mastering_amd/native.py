@@ -52,7 +52,7 @@ class MMJob(ctypes.Structure):
                 ("n_blocks", ctypes.c_int64), ("block_lo", c_int64_p), ("block_hi", c_int64_p),
                 ("n_segs", ctypes.c_int64), ("seg_bounds", c_int64_p), ("block_scale", ctypes.c_double),
                 ("sat_table", ctypes.POINTER(ctypes.c_float)), ("sat_key", ctypes.c_uint64),
-                ("meter_on", ctypes.c_int32), ("_pad", ctypes.c_int32)]
+                ("meter_on", ctypes.c_int32), ("ceiling_q28", ctypes.c_int32)]
 
 
 class MMResult(ctypes.Structure):
@@ -74,6 +74,13 @@ class MMMeter(ctypes.Structure):
                 ("sample_peak", ctypes.c_int32 * 2), ("true_peak_q28", ctypes.c_int32 * 2),
                 ("true_peak_frame", ctypes.c_int64 * 2), ("clipped", ctypes.c_int64 * 2),
                 ("overs", ctypes.c_int64 * 2), ("loudness", ctypes.c_double)]
+
+
+class MMCeiling(ctypes.Structure):
+    _fields_ = [("frames", ctypes.c_int64), ("channels", ctypes.c_int32), ("window", ctypes.c_int32),
+                ("ceiling_q28", ctypes.c_int32), ("tp_in_q28", ctypes.c_int32), ("tp_limited_q28", ctypes.c_int32),
+                ("tp_out_q28", ctypes.c_int32), ("min_gain_q16", ctypes.c_int32), ("trim_q16", ctypes.c_int32),
+                ("limited_frames", ctypes.c_int64)]
 
 
 ABI_VERSION = 5  # MM_ABI_VERSION of include/mastering.h
@@ -98,7 +105,9 @@ EXPORTS = ("mm_create", "mm_destroy", "mm_last_error", "mm_sync", "mm_version", 
            "mm_op_saturation_legacy", "mm_op_soft_limiter_legacy", "mm_op_sosfilt_mix", "mm_op_compress_bands",
            "mm_solve_geometry", "mm_np_sum_f32", "mm_check_compressor_math",
            "mm_meter_device", "mm_meter_pcm", "mm_last_meters", "mm_op_true_peak", "mm_true_peak_host",
-           "mm_meter_span")
+           "mm_meter_span",
+           "mm_ceiling_device", "mm_ceiling_pcm", "mm_ceiling_host", "mm_last_ceilings", "mm_ceiling_span",
+           "mm_ceiling_max_window")
 
 _lib = None
 _lock = threading.Lock()
@@ -184,6 +193,15 @@ def load():
             "mm_op_true_peak": ([vp, ctypes.c_int, vp, ctypes.c_int64, ctypes.c_int, c_double_p], ctypes.c_int),
             "mm_true_peak_host": ([P(ctypes.c_int16), ctypes.c_int64, ctypes.c_int, P(MMMeter)], ctypes.c_int),
             "mm_meter_span": ([], ctypes.c_int),
+            "mm_ceiling_device": ([vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int32, ctypes.c_int32,
+                                   P(MMCeiling)], ctypes.c_int),
+            "mm_ceiling_pcm": ([vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int32, ctypes.c_int32,
+                                P(MMCeiling)], ctypes.c_int),
+            "mm_ceiling_host": ([P(ctypes.c_int16), ctypes.c_int64, ctypes.c_int, ctypes.c_int32, ctypes.c_int32,
+                                 P(MMCeiling)], ctypes.c_int),
+            "mm_last_ceilings": ([vp, ctypes.c_int, P(MMCeiling)], ctypes.c_int),
+            "mm_ceiling_span": ([], ctypes.c_int),
+            "mm_ceiling_max_window": ([], ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             fn = getattr(lib, name)

@@ -8,7 +8,9 @@ defaults to ``$MM_BUCKET_ROOT``.  Exactly like AME:92-107, the result is written
 ``.complete`` marker next to it; the marker appears only after the WAV is fully
 written (renamed into place), so a poller never sees a partial file.  With a truthy
 ``settings["report"]`` (no reference counterpart) the mastering report of the written
-file goes to ``<output>.report.json`` before the marker.
+file goes to ``<output>.report.json`` before the marker, and with
+``settings["ceiling_dbtp"]`` what the true-peak ceiling did goes to
+``<output>.ceiling.json`` the same way.
 
 ``wsgi_app`` is the handler as a plain WSGI callable (what gunicorn serves the
 reference's Flask app as), so no web framework is needed; ``handle_push`` is the
@@ -82,10 +84,11 @@ def process_audio_from_gcs(gcs_uri: str, settings: dict, root: str | None = None
             if os.path.exists(tmp):
                 os.remove(tmp)
         print(f"Exporting and uploading processed audio to {out_name}...")
-        if isinstance(info, dict) and info.get("report"):
-            with open(dst + ".report.json.part", "w") as f:
-                json.dump(_json_safe(info["report"]), f, indent=1, sort_keys=True)
-            os.replace(dst + ".report.json.part", dst + ".report.json")
+        for key in ("ceiling", "report"):  # part, then replace: a poller never sees half a file
+            if isinstance(info, dict) and info.get(key):
+                with open(f"{dst}.{key}.json.part", "w") as f:
+                    json.dump(_json_safe(info[key]), f, indent=1, sort_keys=True)
+                os.replace(f"{dst}.{key}.json.part", f"{dst}.{key}.json")
         with open(dst + ".complete", "wb"):
             pass
         print(f"Completion flag created at {out_name}.complete")
