@@ -42,6 +42,17 @@ extern "C" {
 
 #define MM_IN_F32 0  /* input: interleaved f32 (decoded PCM16 / 32768)           */
 #define MM_IN_I16 1  /* input: interleaved int16 PCM, decoded (x / 32768) on the GPU */
+/* Integer PCM above 16 bits (no reference counterpart), decoded on the GPU
+ * (mm_pcm_decode_device) at the top of the chain, which then runs as MM_IN_F32 on
+ * the decoded floats: every delivered byte and every field of mm_result, mm_meter
+ * and mm_ceiling equals those of the same call on that f32 array.  With s the
+ * sign-extended little-endian sample:
+ *   MM_IN_I24  packed 3-byte samples at any byte address: x = float(s) * 2^-23 (exact)
+ *   MM_IN_I32  4-byte aligned int32: x = RN_f32(s) * 2^-31 (one round-to-nearest-even
+ *              conversion, then an exact scale; INT32_MAX decodes to 1.0); a 24-bit
+ *              sample left-justified (s << 8) gives the MM_IN_I24 value */
+#define MM_IN_I24 2
+#define MM_IN_I32 3
 
 typedef struct mm_ctx mm_ctx;
 
@@ -110,7 +121,7 @@ typedef struct mm_job {
     int32_t comp_warmup;     /* super-tiles of speculative warm-up walk before each one */
     int32_t comp_max_iters;  /* cap on fix-up sweeps (exactness check)          */
     int32_t comp_super;      /* frames per super-tile of the envelope solve (rounded to whole tiles) */
-    int32_t in_kind;         /* MM_IN_F32 (0) or MM_IN_I16                      */
+    int32_t in_kind;         /* MM_IN_F32 (0), MM_IN_I16, MM_IN_I24 or MM_IN_I32 */
     /* loudness geometry (pyloudnorm integrated_loudness, block 0.4 s, step 0.1 s) */
     int64_t n_blocks;
     const int64_t *block_lo; /* host [n_blocks] first frame of each block        */
@@ -231,7 +242,10 @@ int mm_sync(mm_ctx *ctx);
    mm_op_true_peak, mm_true_peak_host, mm_meter_span); also under 5, in the place of
    mm_job's trailing pad (a caller that zeroed it gets what it got): mm_job.ceiling_q28,
    mm_ceiling and the ceiling entry points (mm_ceiling_device, mm_ceiling_pcm,
-   mm_ceiling_host, mm_last_ceilings, mm_ceiling_span, mm_ceiling_max_window).  A caller built against an older header must
+   mm_ceiling_host, mm_last_ceilings, mm_ceiling_span, mm_ceiling_max_window); and, as new values
+   of existing fields (no struct changed): mm_job.in_kind MM_IN_I24 / MM_IN_I32, mm_wav_info
+   bits 24 / 32 with format 1, and the decode entry points (mm_pcm_decode_device,
+   mm_op_pcm_decode, mm_pcm_decode_host, mm_pcm_decode_span).  A caller built against an older header must
    refuse a library whose version differs from its own MM_ABI_VERSION. */
 #define MM_ABI_VERSION 5
 int mm_version(void);
@@ -246,7 +260,7 @@ const char *mm_source_sha(void);
 
 /* ---- whole chain -------------------------------------------------------- */
 /* Host buffers: in = interleaved [frames_in*channels] of job->in_kind (f32 =
- * PCM16/32768, or int16 PCM), out = [frames_proc*channels] of out_kind.
+ * PCM16/32768, int16 PCM, packed 24-bit or int32 PCM), out = [frames_proc*channels] of out_kind.
  * Replaces AME:43-98 minus file/GCS IO. */
 int mm_master(mm_ctx *ctx, const mm_job *job, const void *in, void *out, mm_result *res);
 /* Same, with device-resident input/output (zero-copy; e.g. torch tensors). */
@@ -307,21 +321,39 @@ int mm_ceiling_span(void);
 /* The largest look-ahead window, in frames (1024). */
 int mm_ceiling_max_window(void);
 
+/* ---- 24- and 32-bit integer PCM --------------------------------------------- */
+/* Decode n_samples of `kind` (MM_IN_I24: any byte address; MM_IN_I32: 4-byte
+ * aligned, MM_ERR_ARG otherwise) at the device pointer d_in into n_samples floats
+ * at d_out, as MM_IN_I24 / MM_IN_I32 define.  Nothing outside the aligned dwords
+ * that hold input bytes is read, nothing outside d_out[0, n_samples) written.
+ * Synchronous on return. */
+int mm_pcm_decode_device(mm_ctx *ctx, int kind, const void *d_in, int64_t n_samples, float *d_out);
+/* The same on host buffers (a per-stage operator, like mm_op_pcm_to_float). */
+int mm_op_pcm_decode(mm_ctx *ctx, int kind, const void *in, int64_t n_samples, float *out);
+/* The definition restated in plain C++ on the host (no context, no GPU). */
+int mm_pcm_decode_host(int kind, const void *in, int64_t n_samples, float *out);
+/* Samples per workgroup pass of the decode kernel (where its seams lie). */
+int mm_pcm_decode_span(void);
+
 /* ---- WAV files (AME:43 decode, AME:98 export) ------------------------------ */
 typedef struct mm_wav_info {
     int64_t frames;          /* whole frames in the data chunk                   */
     int64_t data_offset;     /* byte offset of the samples in the file           */
     int32_t rate;
     int32_t channels;
-    int32_t format;          /* 1 = PCM16, 3 = IEEE float32 (EXTENSIBLE resolved) */
-    int32_t bits;
+    int32_t format;          /* 1 = integer PCM, 3 = IEEE float32 (EXTENSIBLE resolved) */
+    int32_t bits;            /* format 1: 16, 24 (packed) or 32; format 3: 32; for
+                                EXTENSIBLE the container's bits (valid-bits are ignored:
+                                samples are left-justified in the container)        */
 } mm_wav_info;
-/* Parse a RIFF/WAVE header (PCM16 or float32).  ctx may be NULL (no message). */
+/* Parse a RIFF/WAVE header (PCM 16/24/32-bit or float32; 24- and 32-bit PCM must
+ * have nBlockAlign == channels * bits / 8).  ctx may be NULL (no message). */
 int mm_wav_probe(mm_ctx *ctx, const char *path, mm_wav_info *info);
 /* Master a WAV file into out_path (PCM16 WAV for MM_OUT_I16, float32 WAV for
  * MM_OUT_F32).  The samples stream from the file through pinned, double-buffered
- * staging into HBM as they are read (PCM16 stays int16 across PCIe and is
- * decoded on the GPU) and the output streams back the same way.  job must be
+ * staging into HBM as they are read (integer PCM crosses PCIe as it lies in the
+ * file, 2, 3 or 4 bytes a sample, and is decoded on the GPU) and the output, 16-bit
+ * whatever the input's width, streams back the same way.  job must be
  * built for the probed frames/rate/channels; its in_kind is ignored (taken from
  * the file). */
 int mm_master_wav(mm_ctx *ctx, const mm_job *job, const char *in_path, const char *out_path, mm_result *res);

@@ -1,8 +1,8 @@
 // mastering.hip — host side of the C-ABI (include/mastering.h), one translation
 // unit: the launch sequence of the chain (a unit of n >= 1 tracks between two
 // syncs), loudness gating, the batch scheduler and the staged / time-sharded entry
-// points.  The context is context.h; wav.hip, comm.hip, ops.hip, meter.hip and
-// ceiling.hip are included at the end.
+// points.  The context is context.h, followed by decode.hip (24/32-bit PCM input);
+// wav.hip, comm.hip, ops.hip, meter.hip and ceiling.hip are included at the end.
 #include <rccl/rccl.h>
 
 #include <algorithm>
@@ -23,6 +23,7 @@
 using namespace mm;
 
 #include "context.h"
+#include "decode.hip"
 
 // meter.hip: meter track `slot` of `n` of the current master call into c->meters
 static int chain_meter(mm_ctx *c, const mm_job *j, const void *d_out, int slot, int n);
@@ -135,7 +136,7 @@ static int lb_prepare(mm_ctx *c, int64_t nblk, int ch, LbArgs &lb, int region = 
 static int validate(mm_ctx *c, const mm_job *j) {
     if (!j) return set_err(c, MM_ERR_ARG, "null job");
     if (j->channels != 1 && j->channels != 2) return set_err(c, MM_ERR_ARG, "channels must be 1 or 2");
-    if (j->in_kind != MM_IN_F32 && j->in_kind != MM_IN_I16) return set_err(c, MM_ERR_ARG, "in_kind %d", j->in_kind);
+    if (!in_sample_bytes(j->in_kind)) return set_err(c, MM_ERR_ARG, "in_kind %d", j->in_kind);
     if (j->tile < 16 || j->tile > 512) return set_err(c, MM_ERR_ARG, "tile %d out of range [16, 512]", j->tile);
     if (j->tiles_per_chunk < 1) return set_err(c, MM_ERR_ARG, "tiles_per_chunk < 1");
     if (j->frames_proc < 0 || j->frames_in < 0) return set_err(c, MM_ERR_ARG, "negative frame count");
@@ -598,6 +599,19 @@ static unsigned kw_nblk(const mm_job *j, int64_t G) {
 // ------------------------------------------------------------ chain A..C
 // nblk_kw: the blocks of the K-weighting stage that will follow on this line (0: none)
 static int stage_front(mm_ctx *c, const mm_job *j, const void *d_in, unsigned nblk_kw) {
+    mm_job jf;
+    if (j->in_kind == MM_IN_I24 || j->in_kind == MM_IN_I32) {
+        // 24/32-bit PCM: decoded once for the line (a fused timeline is one run of
+        // samples), and the job goes on as MM_IN_F32 on those floats
+        const int64_t n = j->frames_in * j->channels;
+        float *dec;
+        RET(get_buf(c, "pcm_dec", (size_t)std::max<int64_t>(n, 1), &dec));
+        RET(pcm_decode(c, j->in_kind, d_in, n, dec));
+        jf = *j;
+        jf.in_kind = MM_IN_F32;
+        j = &jf;
+        d_in = dec;
+    }
     const int T = j->tile, ch = j->channels, K = j->tiles_per_chunk;
     const int64_t N = j->frames_proc;
     const int64_t G = (N + T - 1) / T;
@@ -1342,7 +1356,7 @@ static int unit_enqueue(mm_ctx *c, Unit &u) {
     const void *tin = u.in[0];
     mm_job tj;
     if (fused) {
-        const size_t fb = (size_t)j0.channels * (j0.in_kind == MM_IN_I16 ? 2 : 4);
+        const size_t fb = (size_t)j0.channels * in_sample_bytes(j0.in_kind);
         bool in_place = true;
         for (int i = 0; i < u.n && in_place; ++i)
             in_place = u.J[i].frames_in == u.off[i + 1] - u.off[i] &&
@@ -1651,7 +1665,7 @@ int mm_master(mm_ctx *c, const mm_job *j, const void *in, void *out, mm_result *
     HIPCHK(c, hipSetDevice(c->device));
     char *d_in;
     void *d_out;
-    const size_t in_bytes = (size_t)j->frames_in * j->channels * (j->in_kind == MM_IN_I16 ? 2 : 4);
+    const size_t in_bytes = (size_t)j->frames_in * j->channels * in_sample_bytes(j->in_kind);
     const size_t out_bytes = (size_t)j->frames_proc * j->channels * (j->out_kind == MM_OUT_I16 ? 2 : 4);
     RET(get_buf(c, "host_in", std::max<size_t>(in_bytes, 1), &d_in));
     char *ob;

@@ -6,8 +6,10 @@ extern "C" {
 
 // ------------------------------------------------------------ WAV files
 // RIFF/WAVE codec of the file path (replaces pydub/ffmpeg decode, AME:43, and the
-// stdlib `wave` export, AME:98), mirroring mastering_amd/wavio.py: PCM16 or
-// IEEE float32 (WAVE_FORMAT_EXTENSIBLE resolved through its subformat), the
+// stdlib `wave` export, AME:98), mirroring mastering_amd/wavio.py: integer PCM of
+// 16, 24 (packed) or 32 bits or IEEE float32 (WAVE_FORMAT_EXTENSIBLE resolved through
+// its subformat; its valid-bits are ignored, samples are left-justified in the
+// container; the two wide PCM formats must carry their own block align), the
 // last fmt/data chunk wins, a data chunk running past the end of the file is
 // truncated to whole frames.
 static uint32_t le32(const unsigned char *p) { return p[0] | p[1] << 8 | p[2] << 16 | (uint32_t)p[3] << 24; }
@@ -20,7 +22,7 @@ static int wav_parse(mm_ctx *c, FILE *f, const char *path, mm_wav_info *info) {
     if (fseeko(f, 0, SEEK_SET) != 0 || fread(h, 1, 12, f) != 12 || memcmp(h, "RIFF", 4) || memcmp(h + 8, "WAVE", 4))
         return set_err(c, MM_ERR_ARG, "%s: not a RIFF/WAVE file", path);
     int64_t pos = 12, data_off = -1, data_size = 0;
-    int tag = -1, ch = 0, rate = 0, bits = 0;
+    int tag = -1, ch = 0, rate = 0, bits = 0, align = 0;
     while (pos + 8 <= fsize) {
         if (fseeko(f, pos, SEEK_SET) != 0 || fread(h, 1, 8, f) != 8) break;
         const int64_t size = le32(h + 4);
@@ -31,6 +33,7 @@ static int wav_parse(mm_ctx *c, FILE *f, const char *path, mm_wav_info *info) {
             tag = le16(b);
             ch = le16(b + 2);
             rate = (int)le32(b + 4);
+            align = le16(b + 12);
             bits = le16(b + 14);
             if (tag == 0xFFFE && nb >= 26) tag = le16(b + 24);
         } else if (!memcmp(h, "data", 4)) {
@@ -40,9 +43,13 @@ static int wav_parse(mm_ctx *c, FILE *f, const char *path, mm_wav_info *info) {
         pos += 8 + size + (size & 1);
     }
     if (tag < 0 || data_off < 0) return set_err(c, MM_ERR_ARG, "%s: missing fmt or data chunk", path);
-    if (!((tag == 1 && bits == 16) || (tag == 3 && bits == 32)))
+    const bool wide = tag == 1 && (bits == 24 || bits == 32);  // decoded by pcm_decode_kernel
+    if (!((tag == 1 && bits == 16) || (tag == 3 && bits == 32) || wide))
         return set_err(c, MM_ERR_ARG, "%s: unsupported WAV format tag=%d bits=%d", path, tag, bits);
     if (ch < 1 || rate < 1) return set_err(c, MM_ERR_ARG, "%s: bad fmt chunk (channels %d, rate %d)", path, ch, rate);
+    if (wide && align != ch * bits / 8)
+        return set_err(c, MM_ERR_ARG, "%s: unsupported WAV format tag=%d bits=%d with block align %d (not %d)", path, tag,
+                       bits, align, ch * bits / 8);
     info->frames = data_size / (ch * bits / 8);
     info->data_offset = data_off;
     info->rate = rate;
@@ -89,12 +96,13 @@ int mm_master_wav(mm_ctx *c, const mm_job *jin, const char *in_path, const char 
     mm_wav_info wi;
     RET(wav_parse(c, in.f, in_path, &wi));
     mm_job j = *jin;
-    j.in_kind = wi.format == 1 ? MM_IN_I16 : MM_IN_F32;
+    j.in_kind = wi.format != 1 ? MM_IN_F32 : wi.bits == 16 ? MM_IN_I16 : wi.bits == 24 ? MM_IN_I24 : MM_IN_I32;
     if (j.frames_in != wi.frames || j.channels != wi.channels || j.rate != wi.rate)
         return set_err(c, MM_ERR_ARG, "%s: job built for %lld frames x %d ch @ %d Hz, file has %lld x %d @ %d", in_path,
                        (long long)j.frames_in, j.channels, j.rate, (long long)wi.frames, wi.channels, wi.rate);
     RET(validate(c, &j));
-    const size_t in_bytes = (size_t)wi.frames * wi.channels * (wi.bits / 8);
+    // (the packed bytes as they lie in the file: a staging boundary may split a sample)
+    const size_t in_bytes = (size_t)wi.frames * wi.channels * in_sample_bytes(j.in_kind);
     const size_t out_bytes = (size_t)j.frames_proc * j.channels * (j.out_kind == MM_OUT_I16 ? 2 : 4);
     if (out_bytes > 0xFFFFFFFFull - 36) return set_err(c, MM_ERR_ARG, "output larger than a RIFF file can hold");
     char *d_in, *d_out;

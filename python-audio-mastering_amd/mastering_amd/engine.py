@@ -183,14 +183,20 @@ class Job:
         ctypes.memmove(dst.phi_blk_pow, bp.ctypes.data, bp.nbytes)
 
 
-def _device_input(pcm: np.ndarray):
+def _device_input(pcm: np.ndarray, wide: bool = False):
     """PCM as the library takes it: int16 stays int16 (decoded /32768 on the GPU,
-    AME:117-121; half the PCIe bytes), float32 is taken as decoded PCM."""
+    AME:117-121; half the PCIe bytes), float32 is taken as decoded PCM.  `wide` (the
+    mastering chain only; the meter and the ceiling are defined on the int16 grid):
+    int32 is 24- or 32-bit PCM left-justified, as wavio.read_wav returns it, decoded
+    on the GPU as x = RN_f32(s) * 2^-31 (MM_IN_I32)."""
     if pcm.dtype == np.int16:
         return np.ascontiguousarray(pcm), native.MM_IN_I16
     if pcm.dtype == np.float32:
         return np.ascontiguousarray(pcm), native.MM_IN_F32
-    raise TypeError("PCM must be int16 or float32")
+    if wide and pcm.dtype == np.int32:
+        return np.ascontiguousarray(pcm), native.MM_IN_I32
+    raise TypeError("PCM must be int16, float32 or (left-justified 24/32-bit) int32" if wide
+                    else "PCM must be int16 or float32")
 
 
 def _info(job: "Job", res: native.MMResult) -> dict:
@@ -309,7 +315,10 @@ def meter_pcm(pcm: np.ndarray, rate: int, loudness: bool = True, device: int = 0
 
 def master_pcm(pcm: np.ndarray, rate: int, params: dict, out_kind: int = native.MM_OUT_I16, device: int = 0):
     """Run the whole chain (AME:48-89) on a PCM array [N] or [N, ch] on the GPU.
-    Returns (out_pcm, info) with out_pcm int16 (or f32 = int16/32768).
+    Returns (out_pcm, info) with out_pcm int16 (or f32 = int16/32768).  The input is
+    int16, float32, or int32 holding 24- or 32-bit PCM left-justified (what
+    wavio.read_wav returns for such files): that is decoded on the GPU and mastered
+    exactly as the float32 array of the same values; the output stays 16-bit.
     params['report'] (truthy) adds info['report'] (report_dict) on the output;
     params['ceiling_dbtp'] holds the output under that true-peak ceiling first and adds
     info['ceiling'] (ceiling_dict)."""
@@ -318,7 +327,7 @@ def master_pcm(pcm: np.ndarray, rate: int, params: dict, out_kind: int = native.
     report = bool(params.pop("report", False))
     ceiling = params.pop("ceiling_dbtp", None)
     job = Job(pcm.shape[0], rate, ch, params, out_kind, report=report, ceiling_dbtp=ceiling)
-    x, job.job.in_kind = _device_input(pcm)
+    x, job.job.in_kind = _device_input(pcm, wide=True)
     shape = (job.frames_proc,) if ch == 1 else (job.frames_proc, ch)
     out = np.empty(shape, np.int16 if out_kind == native.MM_OUT_I16 else np.float32)
     ctx = native.context(device)
@@ -329,7 +338,7 @@ def master_pcm(pcm: np.ndarray, rate: int, params: dict, out_kind: int = native.
 
 
 def wav_info(path: str, device: int = 0) -> native.MMWavInfo:
-    """RIFF/WAVE header of `path` (PCM16 or float32), parsed by the library."""
+    """RIFF/WAVE header of `path` (PCM of 16, 24 or 32 bits, or float32), parsed by the library."""
     ctx = native.context(device)
     info = native.MMWavInfo()
     ctx.check(ctx.lib.mm_wav_probe(ctx.ptr, os.fsencode(path), ctypes.byref(info)), "mm_wav_probe")
@@ -365,9 +374,12 @@ def master_batch(ctx: native.Context, jobs, d_ins, d_outs, with_results: bool = 
 
 
 def process(input_path: str, output_path: str, params: dict, device: int = 0, verbose: bool = False) -> dict:
-    """Master `input_path` (16-bit PCM or 32-bit float WAV) into `output_path`
-    (16-bit PCM WAV, as AME:98 exports; params['output_format']='f32' writes float).
-    The file streams through pinned staging into HBM and back (mm_master_wav).
+    """Master `input_path` (16-, 24- or 32-bit PCM or 32-bit float WAV) into `output_path`
+    (16-bit PCM WAV, as AME:98 exports, whatever the input's width;
+    params['output_format']='f32' writes float).
+    The file streams through pinned staging into HBM and back (mm_master_wav); 24- and
+    32-bit PCM cross PCIe as they lie in the file and are decoded on the GPU, and give
+    exactly what the float32 file of the same values gives.
     params['report'] (truthy) adds info['report'] (report_dict) on the written samples;
     params['ceiling_dbtp'] holds them under that true-peak ceiling (info['ceiling']).
     Raises ValueError for unreadable/unsupported input and RuntimeError for device

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("MM_LIB") or os.path.join(_HERE, "libmastering_amd.so"
 
 MM_OUT_I16, MM_OUT_F32 = 0, 1
 MM_IN_F32, MM_IN_I16 = 0, 1
+MM_IN_I24, MM_IN_I32 = 2, 3  # packed 24-bit / int32 PCM, decoded on the GPU (mm_pcm_decode_device)
 MM_F32, MM_F64 = 0, 1  # per-stage operator sample dtypes
 MM_ERR_ARG = -1
 BATCH_STREAMS = 8  # MM_BATCH_STREAMS
@@ -107,7 +108,8 @@ EXPORTS = ("mm_create", "mm_destroy", "mm_last_error", "mm_sync", "mm_version", 
            "mm_meter_device", "mm_meter_pcm", "mm_last_meters", "mm_op_true_peak", "mm_true_peak_host",
            "mm_meter_span",
            "mm_ceiling_device", "mm_ceiling_pcm", "mm_ceiling_host", "mm_last_ceilings", "mm_ceiling_span",
-           "mm_ceiling_max_window")
+           "mm_ceiling_max_window",
+           "mm_pcm_decode_device", "mm_op_pcm_decode", "mm_pcm_decode_host", "mm_pcm_decode_span")
 
 _lib = None
 _lock = threading.Lock()
@@ -202,6 +204,10 @@ def load():
             "mm_last_ceilings": ([vp, ctypes.c_int, P(MMCeiling)], ctypes.c_int),
             "mm_ceiling_span": ([], ctypes.c_int),
             "mm_ceiling_max_window": ([], ctypes.c_int),
+            "mm_pcm_decode_device": ([vp, ctypes.c_int, vp, ctypes.c_int64, vp], ctypes.c_int),
+            "mm_op_pcm_decode": ([vp, ctypes.c_int, vp, ctypes.c_int64, vp], ctypes.c_int),
+            "mm_pcm_decode_host": ([ctypes.c_int, vp, ctypes.c_int64, vp], ctypes.c_int),
+            "mm_pcm_decode_span": ([], ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             fn = getattr(lib, name)

@@ -36,7 +36,8 @@ from .engine import Job
 
 __all__ = ["audio_segment_to_float_array", "float_array_to_audio_segment", "apply_saturation",
            "apply_stereo_width", "apply_eq_to_samples", "apply_shelf_filter", "apply_peak_filter",
-           "apply_multiband_compressor", "normalize_to_lufs", "soft_limiter", "integrated_loudness", "true_peak"]
+           "apply_multiband_compressor", "normalize_to_lufs", "soft_limiter", "integrated_loudness", "true_peak",
+           "decode_pcm"]
 
 _vp = ctypes.c_void_p
 
@@ -81,6 +82,30 @@ def audio_segment_to_float_array(audio_segment, device: int = 0) -> np.ndarray:
     out = np.empty(pcm.shape, np.float32)
     ctx = _ctx(device)
     ctx.check(ctx.lib.mm_op_pcm_to_float(ctx.ptr, _ptr(pcm), pcm.size, _ptr(out)), "mm_op_pcm_to_float")
+    return out
+
+
+def decode_pcm(raw, bits: int, device: int = 0) -> np.ndarray:
+    """24- or 32-bit integer PCM as float32 (mm_op_pcm_decode; no reference counterpart:
+    the reference wraps such samples on the way out).  bits 24: `raw` is the packed
+    little-endian bytes (uint8, a multiple of 3 of them), x = float(s) * 2^-23; bits 32:
+    `raw` is int32, x = RN_f32(s) * 2^-31.  Returns [n] float32 (int32 input keeps its
+    shape)."""
+    raw = np.asarray(raw)
+    if bits == 24:
+        if raw.dtype != np.uint8 or raw.size % 3:
+            raise TypeError("decode_pcm(bits=24): packed uint8 bytes expected, three per sample")
+        kind, shape = native.MM_IN_I24, (raw.size // 3,)
+    elif bits == 32:
+        if raw.dtype != np.int32:
+            raise TypeError("decode_pcm(bits=32): int32 samples expected")
+        kind, shape = native.MM_IN_I32, raw.shape
+    else:
+        raise ValueError("decode_pcm: bits must be 24 or 32")
+    raw = np.ascontiguousarray(raw)
+    out = np.empty(shape, np.float32)
+    ctx = _ctx(device)
+    ctx.check(ctx.lib.mm_op_pcm_decode(ctx.ptr, kind, _ptr(raw), out.size, _ptr(out)), "mm_op_pcm_decode")
     return out
 
 
