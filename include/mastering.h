@@ -210,6 +210,52 @@ typedef struct mm_ceiling {
     int64_t limited_frames;  /* frames with g < ONE                                 */
 } mm_ceiling;
 
+/* The sample-rate converter (no reference counterpart), all integers.  With g =
+ * gcd(rate_in, rate_out): L = rate_out / g, M = rate_in / g.  taps is the caller's table
+ * c[L][K] (design.resample_taps: a Kaiser-windowed sinc of 64 zero crossings a side, every
+ * phase with DC gain exactly 2^22).  For input s (int16, 0 outside [0, N)) the output has
+ * frames_out = ceil(N * L / M) frames; frame n of a channel is
+ *   q = n * M (int64), b = q / L, p = q % L
+ *   acc = sum_{k<K} c[p][k] * s[b + K/2 - k]
+ *   y = (acc + 2^21) >> 22 (arithmetic), delivered clipped to [-32768, 32767].
+ * Output frame 0 lies at input time 0: no latency, no tail.  Channels are independent.
+ * A table is refused (MM_ERR_ARG) unless K is even and 2 <= K <= 1024, 1 <= L, M <= 640,
+ * gcd(L, M) = 1, L != M, rate_in * L == rate_out * M and every row has sum |c| < 2^24.
+ * Then |acc| < 2^39: the sum is exact in int64 and in f64 FMAs in any order. */
+typedef struct mm_resampler {
+    int32_t rate_in, rate_out;
+    int32_t L, M, K;
+    int32_t _pad;
+    const int32_t *taps;     /* host [L][K]                                          */
+    uint64_t taps_key;       /* content key of taps (nonzero; the context keeps its
+                                device copy while the key and L, M, K stay the same).
+                                0: no key, checked and uploaded on every call          */
+} mm_resampler;
+
+typedef struct mm_resample {
+    int64_t frames_in;
+    int64_t frames_out;
+    int32_t channels;
+    int32_t rate_in, rate_out;
+    int32_t L, M, K;
+    int64_t clipped[2];      /* y outside the int16 range                            */
+    int32_t peak[2];         /* max |delivered sample|, 0..32768                     */
+} mm_resample;
+
+/* What mm_job cannot carry for a delivery at another rate (mm_deliver*): the converter
+ * and, acting on the converted signal, the ceiling and the report. */
+typedef struct mm_delivery {
+    const mm_resampler *rs;
+    int32_t ceiling_q28;     /* 0 = off; else as mm_job.ceiling_q28                  */
+    int32_t window;          /* the ceiling's look-ahead at rate_out (frames)        */
+    int32_t meter_on;        /* meter the delivered output (mm_last_meters)          */
+    int32_t _pad;
+    const struct mm_job *loud; /* a job carrying the loudness geometry of the OUTPUT
+                                (frames_proc = frames_out, channels, rate = rate_out,
+                                kweight with tpb 256, blocks, segments), as for
+                                mm_meter_device; NULL: peaks only                    */
+} mm_delivery;
+
 /* Geometry of the compressor's envelope solve for a job (mm_solve_geometry: the
    planning arithmetic stage C runs on, computed on the host without a GPU). */
 typedef struct mm_solve_geom {
@@ -245,7 +291,11 @@ int mm_sync(mm_ctx *ctx);
    mm_ceiling_host, mm_last_ceilings, mm_ceiling_span, mm_ceiling_max_window); and, as new values
    of existing fields (no struct changed): mm_job.in_kind MM_IN_I24 / MM_IN_I32, mm_wav_info
    bits 24 / 32 with format 1, and the decode entry points (mm_pcm_decode_device,
-   mm_op_pcm_decode, mm_pcm_decode_host, mm_pcm_decode_span).  A caller built against an older header must
+   mm_op_pcm_decode, mm_pcm_decode_host, mm_pcm_decode_span); and, as new structs and entry
+   points only (mm_job is unchanged): mm_resampler, mm_resample, mm_delivery, the converter
+   (mm_resample_device, mm_resample_pcm, mm_resample_host, mm_resample_frames,
+   mm_resample_span, mm_last_resample) and the delivery path (mm_deliver_device, mm_deliver,
+   mm_deliver_wav).  A caller built against an older header must
    refuse a library whose version differs from its own MM_ABI_VERSION. */
 #define MM_ABI_VERSION 5
 int mm_version(void);
@@ -320,6 +370,40 @@ int mm_last_ceilings(mm_ctx *ctx, int cap, mm_ceiling *out);
 int mm_ceiling_span(void);
 /* The largest look-ahead window, in frames (1024). */
 int mm_ceiling_max_window(void);
+
+/* ---- delivery at another sample rate ----------------------------------------- */
+/* Convert a device-resident signal, interleaved [frames][channels] of `kind` (MM_OUT_I16,
+ * or MM_OUT_F32 = the same PCM / 32768: both give the same integers), into d_out
+ * ([frames_out][channels] of the same kind) as mm_resampler defines.  frames = 0 is valid
+ * and gives frames_out = 0.  Synchronous on return. */
+int mm_resample_device(mm_ctx *ctx, const void *d_in, int kind, int64_t frames, int channels, const mm_resampler *rs,
+                       void *d_out, mm_resample *out);
+/* The same on host buffers. */
+int mm_resample_pcm(mm_ctx *ctx, const void *in, int kind, int64_t frames, int channels, const mm_resampler *rs,
+                    void *out_pcm, mm_resample *out);
+/* The definition restated in plain C++ on the host (no context, no GPU), interleaved
+ * int16 in and out: a CPU check of what the kernel computes. */
+int mm_resample_host(const int16_t *in, int64_t frames, int channels, const mm_resampler *rs, int16_t *out_pcm,
+                     mm_resample *out);
+/* *frames_out = ceil(frames * L / M). */
+int mm_resample_frames(int64_t frames, int32_t L, int32_t M, int64_t *frames_out);
+/* Output frames per workgroup of the converter's kernel (where its seams lie). */
+int mm_resample_span(void);
+/* mm_master_device / mm_master / mm_master_wav with a delivery: the chain runs into a
+ * context buffer, the converter writes the caller's output ([frames_out][channels] of
+ * job->out_kind; the WAV header carries rate_out and frames_out), then the delivery's
+ * ceiling and report act on it, so both hold for what is delivered.  The job must have
+ * ceiling_q28 == 0 and meter_on == 0 (MM_ERR_ARG: they would act at the source rate) and
+ * rs->rate_in == job->rate.  mm_result is the chain's (frames_out = frames_proc);
+ * mm_last_meters and mm_last_ceilings report slot 0 as after mm_master. */
+int mm_deliver_device(mm_ctx *ctx, const mm_job *job, const mm_delivery *dl, const void *d_in, void *d_out,
+                      mm_result *res);
+int mm_deliver(mm_ctx *ctx, const mm_job *job, const mm_delivery *dl, const void *in, void *out, mm_result *res);
+int mm_deliver_wav(mm_ctx *ctx, const mm_job *job, const mm_delivery *dl, const char *in_path, const char *out_path,
+                   mm_result *res);
+/* The converter's statistics of the last mm_deliver* call on this context; MM_ERR_STATE
+ * if the last master call was not a delivery. */
+int mm_last_resample(mm_ctx *ctx, mm_resample *out);
 
 /* ---- 24- and 32-bit integer PCM --------------------------------------------- */
 /* Decode n_samples of `kind` (MM_IN_I24: any byte address; MM_IN_I32: 4-byte

@@ -93,6 +93,12 @@ struct mm_ctx {
     std::vector<mm_meter> meters;
     // ceilings of the last master call (mm_last_ceilings; empty: no job set one)
     std::vector<mm_ceiling> ceilings;
+    // the converter's taps on the device ("rs_taps": content key and geometry; key 0: none)
+    // and the statistics of the last delivery (mm_last_resample)
+    uint64_t rs_key = 0;
+    int rs_L = 0, rs_M = 0, rs_K = 0;
+    mm_resample resample{};
+    bool resample_valid = false;
     // rccl
     ncclComm_t comm = nullptr;
     int rank = 0, nranks = 1;

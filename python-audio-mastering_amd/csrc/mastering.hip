@@ -1448,6 +1448,7 @@ static int unit_complete(mm_ctx *c, const Unit &u, mm_result *res) {
 static int master_device(mm_ctx *c, const mm_job *j, const void *d_in, void *d_out, mm_result *res) {
     c->meters.clear();
     c->ceilings.clear();
+    c->resample_valid = false;
     Unit u;
     u.J = j;
     u.in = &d_in;
@@ -1599,6 +1600,7 @@ int mm_master_batch(mm_ctx *c, int n, const mm_job *jobs, const void *const *d_i
     for (int i = 0; i < n; ++i) RET(validate(c, &jobs[i]));
     c->meters.clear();
     c->ceilings.clear();
+    c->resample_valid = false;
     std::vector<Unit> units = batch_units(jobs, d_in, d_out, n);
     const int nu = (int)units.size();
     const int S = std::min(nu, MM_BATCH_STREAMS);
@@ -1853,3 +1855,4 @@ int mm_kernel_stats(mm_ctx *c, char *names, int names_cap, double *total_ms, int
 #include "ops.hip"
 #include "meter.hip"
 #include "ceiling.hip"
+#include "resample.hip"

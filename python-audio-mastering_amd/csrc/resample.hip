@@ -1,0 +1,499 @@
+// resample.hip — deliver at another sample rate: an exact polyphase sample-rate converter
+// on the int16 grid, and the delivery path that runs it between the chain and the ceiling
+// (mm_deliver*).  No reference counterpart.  Everything is defined in integers
+// (include/mastering.h, mm_resampler): with L / M the rate ratio in lowest terms and
+// c[L][K] the caller's int32 taps (design.resample_taps), output frame n of a channel is
+//   q = n * M, b = q / L, p = q % L
+//   acc = sum_{k<K} c[p][k] * s[b + K/2 - k]        (s = 0 outside [0, N))
+//   y   = (acc + 2^21) >> 22, delivered clipped to int16
+// Every row has sum |c| < 2^24 (checked), so |acc| < 2^39: the sum is exact in int64 and
+// just as exact as an f64 FMA chain in any order.  The kernel sums in f64 FMAs (full rate
+// on this vector ALU, where the 64-bit integer multiply-add is a quarter-rate
+// instruction), the host restatement in int64; the results are the same
+// integers, so nothing depends on the launch geometry.
+//
+// One kernel.  A workgroup owns RS_SPAN consecutive output frames and stages the input
+// frames they read in LDS: a line of int16 for mono, and for stereo one dword a frame
+// (left in the low half).  Two de-interleaved int16 lines, as the meter stages its lines,
+// were measured 6.6 times slower for stereo int16: the compiler fuses the reads of two
+// neighbouring samples into one dword read at a 2-byte-aligned address, which the LDS
+// serves slowly whenever the address is odd; a frame's dword is always aligned and
+// halves the reads.  Outputs n and n + L share their phase, so a work item is RS_R
+// outputs of one residue n mod L: each tap is loaded once and meets RS_R samples a
+// channel.  The device copy of
+// the taps is kept transposed and in output order, D[k][n mod L] = c[(n mod L) * M % L][k],
+// so the lanes of a wave (consecutive n) read consecutive words of one row of D.
+//
+// Included at the end of mastering.hip after ceiling.hip (the meter's sample decoding and
+// wave reductions, ceiling_device, meter_device, the WAV helpers and master_device).
+
+namespace mm {
+
+constexpr int RS_THREADS = 256;
+constexpr int RS_SPAN = 1024;     // output frames per workgroup (mm_resample_span)
+constexpr int RS_R = 4;           // outputs per work item (they share one row of taps)
+constexpr int RS_LINE = 9216;     // frames a staged piece holds: a whole span up to M / L = 8 at K = 1024
+constexpr int RS_MAX_K = 1024;
+constexpr int RS_MAX_LM = 640;
+constexpr int RS_SHIFT = 22;      // taps are multiples of 2^-22
+constexpr int64_t RS_ROW_LIMIT = (int64_t)1 << 24;  // every row: sum |c| below this
+
+// device result block of one conversion (zeroed on the stream before the launch)
+struct RsDev {
+    unsigned long long clipped[2];
+    int peak[2];
+};
+
+struct RsArgs {
+    int64_t N;          // input frames
+    int64_t Nout;       // output frames
+    int L, M, K;
+    int sub;            // output frames per staged piece of a span: the largest whose input fits a line
+    const int32_t *D;   // [K][L], output order
+    RsDev *st;
+};
+
+template <typename T>
+__device__ __forceinline__ T rs_deliver(int y) {
+    if constexpr (sizeof(T) == 2) return (T)y;
+    else return (float)y * (1.0f / 32768.0f);
+}
+
+// The workgroup's span is cut into pieces of a.sub outputs (one piece for every rate pair
+// with M / L <= 8: a.sub == RS_SPAN); a piece starting at output m0 reads the input frames
+// [lo, lo + len), lo = b(m0) - K/2 + 1, len = b(last) - b(m0) + K <= RS_LINE.  Item i of a
+// piece of cnt outputs: residue r = i % min(L, cnt) and j-class jc = i / min(L, cnt); its
+// outputs are o = r + (jc + jj * nJC) * L < cnt, jj < RS_R (interleaved j, so that with
+// L = 1 the lanes of a wave are consecutive outputs).  An output beyond cnt computes on
+// the item's first output's samples (always in range) and is not stored.
+template <int CH, typename T>
+__global__ void __launch_bounds__(RS_THREADS) resample_kernel(const T *__restrict__ in, T *__restrict__ out, RsArgs a) {
+    // mono: int16 samples; stereo: one dword a frame, left in the low half
+    __shared__ __attribute__((aligned(16))) uint32_t lds[CH == 2 ? RS_LINE : RS_LINE / 2];
+    int16_t *const line = reinterpret_cast<int16_t *>(lds);
+    __shared__ unsigned red_clip[CH][RS_THREADS / 64];
+    __shared__ int red_pk[CH][RS_THREADS / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int L = a.L, M = a.M, K = a.K;
+    const int64_t n0 = (int64_t)blockIdx.x * RS_SPAN;
+    const int span = a.Nout - n0 < RS_SPAN ? (int)(a.Nout - n0) : RS_SPAN;
+    unsigned n_clip[CH];
+    int pk[CH];
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+        n_clip[c] = 0;
+        pk[c] = 0;
+    }
+    for (int s0 = 0; s0 < span; s0 += a.sub) {
+        const int cnt = min(a.sub, span - s0);
+        const int64_t m0 = n0 + s0;
+        const int64_t q0 = m0 * M;  // < 2^31 * 640
+        const int64_t b0 = q0 / L;
+        const int p0 = (int)(q0 - b0 * L);
+        const int rho0 = (int)(m0 % L);
+        const int len = (int)(((m0 + cnt - 1) * M) / L - b0) + K;
+        const int64_t lo = b0 - K / 2 + 1;  // frame of LDS index 0
+        if (s0) __syncthreads();            // the lines are free for the next piece
+        for (int i = tid; i < len; i += RS_THREADS) {
+            const int64_t f = lo + i;
+            const bool ok = f >= 0 && f < a.N;
+            if constexpr (CH == 2) {
+                uint32_t d = 0;
+                if (ok) {
+                    if constexpr (sizeof(T) == 2) {
+                        d = reinterpret_cast<const uint32_t *>(in)[f];
+                    } else {
+                        const float2 v = reinterpret_cast<const float2 *>(in)[f];
+                        d = ((uint32_t)meter_sample<float>(v.x) & 0xFFFFu) | ((uint32_t)meter_sample<float>(v.y) << 16);
+                    }
+                }
+                lds[i] = d;
+            } else {
+                line[i] = ok ? (int16_t)meter_sample<T>(in[f]) : (int16_t)0;
+            }
+        }
+        __syncthreads();
+        const int Lc = min(L, cnt);
+        const int J = (cnt + L - 1) / L, nJC = (J + RS_R - 1) / RS_R;
+        const int items = Lc * nJC;
+        for (int i = tid; i < items; i += RS_THREADS) {
+            const int jc = i / Lc, r = i - jc * Lc;
+            int rho = rho0 + r;  // (m0 + r) mod L: the row of D
+            rho -= rho >= L ? L : 0;
+            const int brel = (p0 + r * M) / L;  // b(m0 + r) - b0; r * M < 640 * 640
+            int o[RS_R], base[RS_R];  // base: LDS index of the sample that meets tap 0
+#pragma unroll
+            for (int jj = 0; jj < RS_R; ++jj) {
+                const int j = jc + jj * nJC;
+                o[jj] = r + j * L;
+                base[jj] = brel + (o[jj] < cnt ? j : jc) * M + K - 1;
+            }
+            double acc[CH][RS_R];
+#pragma unroll
+            for (int c = 0; c < CH; ++c)
+#pragma unroll
+                for (int jj = 0; jj < RS_R; ++jj) acc[c][jj] = 0.0;
+            // two taps a step (K is even), the next pair loaded before this one is used, so
+            // that a load's latency lies under a whole step of multiply-adds
+            const int32_t *tp = a.D + rho;
+            int32_t t0 = tp[0], t1 = tp[L];
+            for (int k = 0; k < K; k += 2) {
+                const double c0 = (double)t0, c1 = (double)t1;
+                if (k + 2 < K) {
+                    t0 = tp[(size_t)(k + 2) * L];
+                    t1 = tp[(size_t)(k + 3) * L];
+                }
+#pragma unroll
+                for (int jj = 0; jj < RS_R; ++jj) {
+                    if constexpr (CH == 2) {
+                        const uint32_t d0 = lds[base[jj] - k], d1 = lds[base[jj] - k - 1];
+                        acc[0][jj] = fma(c0, (double)((int)(d0 << 16) >> 16), acc[0][jj]);
+                        acc[1][jj] = fma(c0, (double)((int)d0 >> 16), acc[1][jj]);
+                        acc[0][jj] = fma(c1, (double)((int)(d1 << 16) >> 16), acc[0][jj]);
+                        acc[1][jj] = fma(c1, (double)((int)d1 >> 16), acc[1][jj]);
+                    } else {
+                        acc[0][jj] = fma(c0, (double)line[base[jj] - k], acc[0][jj]);
+                        acc[0][jj] = fma(c1, (double)line[base[jj] - k - 1], acc[0][jj]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int jj = 0; jj < RS_R; ++jj) {
+                if (o[jj] >= cnt) continue;
+                int y[CH];
+#pragma unroll
+                for (int c = 0; c < CH; ++c) {
+                    const long long v = ((long long)acc[c][jj] + (1ll << (RS_SHIFT - 1))) >> RS_SHIFT;  // arithmetic
+                    const int yc = v > 32767 ? 32767 : (v < -32768 ? -32768 : (int)v);
+                    n_clip[c] += v != yc ? 1u : 0u;
+                    pk[c] = max(pk[c], yc < 0 ? -yc : yc);
+                    y[c] = yc;
+                }
+                const int64_t n = m0 + o[jj];
+                if constexpr (CH == 2 && sizeof(T) == 2) {
+                    reinterpret_cast<uint32_t *>(out)[n] = ((uint32_t)y[0] & 0xFFFFu) | ((uint32_t)y[1] << 16);
+                } else if constexpr (CH == 2) {
+                    reinterpret_cast<float2 *>(out)[n] = make_float2(rs_deliver<float>(y[0]), rs_deliver<float>(y[1]));
+                } else {
+                    out[n] = rs_deliver<T>(y[0]);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+        const unsigned nc = wave_sum_u32(n_clip[c]);
+        const int p = wave_max_i32(pk[c]);
+        if (lane == 0) {
+            red_clip[c][wave] = nc;
+            red_pk[c][wave] = p;
+        }
+    }
+    __syncthreads();
+    if (tid < CH) {
+        unsigned nc = 0;
+        int p = 0;
+        for (int w = 0; w < RS_THREADS / 64; ++w) {
+            nc += red_clip[tid][w];
+            p = max(p, red_pk[tid][w]);
+        }
+        if (nc) atomicAdd(&a.st->clipped[tid], (unsigned long long)nc);
+        if (p) atomicMax(&a.st->peak[tid], p);
+    }
+}
+
+}  // namespace mm
+
+// ======================================================= host entry points
+namespace {
+
+int64_t rs_gcd(int64_t a, int64_t b) {
+    while (b) {
+        const int64_t t = a % b;
+        a = b;
+        b = t;
+    }
+    return a;
+}
+
+int64_t rs_frames(int64_t frames, int L, int M) { return (frames * L + M - 1) / M; }
+
+// why (L, M, K) is not a converter's geometry, or null
+const char *resample_bad_geometry(int L, int M, int K) {
+    if (K < 2 || K > RS_MAX_K || (K & 1)) return "K must be even and in [2, 1024]";
+    if (L < 1 || M < 1 || L > RS_MAX_LM || M > RS_MAX_LM) return "L and M must be in [1, 640]";
+    if (L == M || rs_gcd(L, M) != 1) return "L / M must be in lowest terms and not 1";
+    return nullptr;
+}
+
+// why the table is refused, or null (the rows are summed: L * K additions)
+const char *resample_bad_table(const mm_resampler *rs) {
+    if (!rs || !rs->taps) return "null resampler or taps";
+    if (const char *why = resample_bad_geometry(rs->L, rs->M, rs->K)) return why;
+    if (rs->rate_in < 1 || rs->rate_out < 1 || (int64_t)rs->rate_in * rs->L != (int64_t)rs->rate_out * rs->M)
+        return "rate_in * L must equal rate_out * M";
+    for (int p = 0; p < rs->L; ++p) {
+        int64_t sum = 0;
+        for (int k = 0; k < rs->K; ++k) {
+            const int64_t v = rs->taps[(size_t)p * rs->K + k];
+            sum += v < 0 ? -v : v;
+        }
+        if (sum >= RS_ROW_LIMIT) return "a row of taps has sum |c| >= 2^24";
+    }
+    return nullptr;
+}
+
+// why (frames, channels) cannot be converted by this geometry, or null
+const char *resample_bad_signal(int64_t frames, int channels, int L, int M) {
+    if (channels != 1 && channels != 2) return "channels must be 1 or 2";
+    if (frames < 0 || frames >= (int64_t)1 << 31) return "frames out of range";
+    if (rs_frames(frames, L, M) >= ((int64_t)1 << 31) - METER_SPAN) return "output frames out of range";
+    return nullptr;
+}
+
+void resample_clear(mm_resample *o, int64_t frames, int channels, const mm_resampler *rs) {
+    memset(o, 0, sizeof *o);
+    o->frames_in = frames;
+    o->frames_out = rs_frames(frames, rs->L, rs->M);
+    o->channels = channels;
+    o->rate_in = rs->rate_in;
+    o->rate_out = rs->rate_out;
+    o->L = rs->L;
+    o->M = rs->M;
+    o->K = rs->K;
+}
+
+}  // namespace
+
+// The device copy of the taps, transposed and in output order (D[k][rho] = c[rho * M % L][k]),
+// cached per context by the caller's content key (0: no key, checked and uploaded every call).
+static int resample_taps_device(mm_ctx *c, const mm_resampler *rs, const int32_t **out) {
+    int32_t *D;
+    const size_t n = (size_t)rs->L * rs->K;
+    if (rs->taps_key && rs->taps_key == c->rs_key && rs->L == c->rs_L && rs->M == c->rs_M && rs->K == c->rs_K) {
+        RET(get_buf(c, "rs_taps", n, &D));
+        *out = D;
+        return MM_OK;
+    }
+    if (const char *why = resample_bad_table(rs)) return set_err(c, MM_ERR_ARG, "resampler: %s", why);
+    c->rs_key = 0;
+    RET(get_buf(c, "rs_taps", n, &D));
+    std::vector<int32_t> t(n);
+    for (int rho = 0; rho < rs->L; ++rho) {
+        const int32_t *row = rs->taps + (size_t)((int64_t)rho * rs->M % rs->L) * rs->K;
+        for (int k = 0; k < rs->K; ++k) t[(size_t)k * rs->L + rho] = row[k];
+    }
+    HIPCHK(c, hipMemcpyAsync(D, t.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // (t leaves scope)
+    c->rs_key = rs->taps_key;
+    c->rs_L = rs->L;
+    c->rs_M = rs->M;
+    c->rs_K = rs->K;
+    *out = D;
+    return MM_OK;
+}
+
+// Convert a device-resident signal into d_out (synchronous on return).
+static int resample_device(mm_ctx *c, const void *d_in, int kind, int64_t frames, int channels, const mm_resampler *rs,
+                           void *d_out, mm_resample *out) {
+    if (!c || !out || !rs || (frames > 0 && (!d_in || !d_out))) return set_err(c, MM_ERR_ARG, "bad arguments");
+    if (kind != MM_OUT_I16 && kind != MM_OUT_F32) return set_err(c, MM_ERR_ARG, "kind %d (MM_OUT_I16 | MM_OUT_F32)", kind);
+    if (const char *why = resample_bad_geometry(rs->L, rs->M, rs->K)) return set_err(c, MM_ERR_ARG, "resampler: %s", why);
+    if (const char *why = resample_bad_signal(frames, channels, rs->L, rs->M)) return set_err(c, MM_ERR_ARG, "%s", why);
+    RsArgs a{};
+    RET(resample_taps_device(c, rs, &a.D));
+    resample_clear(out, frames, channels, rs);
+    if (out->frames_out == 0) return MM_OK;
+    RET(get_buf(c, "rs_res", 1, &a.st));
+    HIPCHK(c, hipMemsetAsync(a.st, 0, sizeof(RsDev), c->stream));
+    a.N = frames;
+    a.Nout = out->frames_out;
+    a.L = rs->L;
+    a.M = rs->M;
+    a.K = rs->K;
+    // a piece of `sub` outputs reads ((sub - 1) * M + p0) / L + K <= (sub - 1) * M / L + 1 + K frames
+    a.sub = (int)std::min<int64_t>(RS_SPAN, 1 + (int64_t)(RS_LINE - rs->K - 1) * rs->L / rs->M);
+    const dim3 grid((unsigned)((a.Nout + RS_SPAN - 1) / RS_SPAN)), block(RS_THREADS);
+    if (kind == MM_OUT_I16) {
+        const int16_t *p = static_cast<const int16_t *>(d_in);
+        int16_t *q = static_cast<int16_t *>(d_out);
+        if (channels == 2) RET(launch(c, "resample", resample_kernel<2, int16_t>, grid, block, 0, p, q, a));
+        else RET(launch(c, "resample", resample_kernel<1, int16_t>, grid, block, 0, p, q, a));
+    } else {
+        const float *p = static_cast<const float *>(d_in);
+        float *q = static_cast<float *>(d_out);
+        if (channels == 2) RET(launch(c, "resample", resample_kernel<2, float>, grid, block, 0, p, q, a));
+        else RET(launch(c, "resample", resample_kernel<1, float>, grid, block, 0, p, q, a));
+    }
+    RsDev h;
+    HIPCHK(c, hipMemcpyAsync(&h, a.st, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int ch = 0; ch < channels; ++ch) {
+        out->clipped[ch] = (int64_t)h.clipped[ch];
+        out->peak[ch] = h.peak[ch];
+    }
+    resolve_events(c);
+    return MM_OK;
+}
+
+// why (job, delivery) is refused, or null
+static const char *deliver_bad_args(const mm_job *j, const mm_delivery *dl) {
+    if (!j || !dl || !dl->rs) return "null job, delivery or resampler";
+    if (j->ceiling_q28 || j->meter_on) return "the job's ceiling_q28 and meter_on act at the source rate: set the delivery's";
+    if (j->channels != 1 && j->channels != 2) return "channels must be 1 or 2";
+    if (const char *why = resample_bad_geometry(dl->rs->L, dl->rs->M, dl->rs->K)) return why;
+    if (dl->rs->rate_in != j->rate) return "the resampler's rate_in is not the job's rate";
+    if (const char *why = resample_bad_signal(j->frames_proc, j->channels, dl->rs->L, dl->rs->M)) return why;
+    if (dl->ceiling_q28)
+        return ceiling_bad_args(rs_frames(j->frames_proc, dl->rs->L, dl->rs->M), j->channels, dl->ceiling_q28, dl->window);
+    return nullptr;
+}
+
+// The delivery path: the chain into a context buffer, the converter into d_out, then the
+// ceiling and the report on what is delivered (slot 0 of mm_last_ceilings / mm_last_meters).
+static int deliver_device(mm_ctx *c, const mm_job *j, const mm_delivery *dl, const void *d_in, void *d_out,
+                          mm_result *res) {
+    if (const char *why = deliver_bad_args(j, dl)) return set_err(c, MM_ERR_ARG, "delivery: %s", why);
+    const int kind = j->out_kind;
+    const size_t mid_bytes = (size_t)j->frames_proc * j->channels * (kind == MM_OUT_I16 ? 2 : 4);
+    char *mid;
+    RET(get_buf(c, "deliver_mid", std::max<size_t>(mid_bytes, 1), &mid));
+    RET(master_device(c, j, d_in, mid, res));
+    RET(resample_device(c, mid, kind, j->frames_proc, j->channels, dl->rs, d_out, &c->resample));
+    c->resample_valid = true;
+    const int64_t fo = c->resample.frames_out;
+    if (dl->ceiling_q28) {
+        c->ceilings.assign(1, mm_ceiling{});
+        RET(ceiling_device(c, d_out, kind, fo, j->channels, dl->ceiling_q28, dl->window, &c->ceilings[0]));
+    }
+    if (dl->meter_on) {
+        c->meters.assign(1, mm_meter{});
+        RET(meter_device(c, d_out, kind, fo, j->channels, dl->loud, &c->meters[0]));
+    }
+    return MM_OK;
+}
+
+extern "C" {
+
+int mm_resample_span(void) { return RS_SPAN; }
+
+int mm_resample_frames(int64_t frames, int32_t L, int32_t M, int64_t *frames_out) {
+    if (!frames_out || frames < 0 || frames >= (int64_t)1 << 31 || L < 1 || M < 1 || L > RS_MAX_LM || M > RS_MAX_LM)
+        return MM_ERR_ARG;
+    *frames_out = rs_frames(frames, L, M);
+    return MM_OK;
+}
+
+int mm_resample_device(mm_ctx *c, const void *d_in, int kind, int64_t frames, int channels, const mm_resampler *rs,
+                       void *d_out, mm_resample *out) {
+    if (!c) return MM_ERR_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    return resample_device(c, d_in, kind, frames, channels, rs, d_out, out);
+}
+
+int mm_resample_pcm(mm_ctx *c, const void *in, int kind, int64_t frames, int channels, const mm_resampler *rs, void *out_pcm,
+                    mm_resample *out) {
+    if (!c) return MM_ERR_ARG;
+    if (!out || !rs || (frames > 0 && (!in || !out_pcm)) || (kind != MM_OUT_I16 && kind != MM_OUT_F32))
+        return set_err(c, MM_ERR_ARG, "bad arguments");
+    if (const char *why = resample_bad_geometry(rs->L, rs->M, rs->K)) return set_err(c, MM_ERR_ARG, "resampler: %s", why);
+    if (const char *why = resample_bad_signal(frames, channels, rs->L, rs->M)) return set_err(c, MM_ERR_ARG, "%s", why);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t fb = (size_t)channels * (kind == MM_OUT_I16 ? 2 : 4);
+    const size_t in_bytes = (size_t)frames * fb, out_bytes = (size_t)rs_frames(frames, rs->L, rs->M) * fb;
+    char *din, *dout;
+    RET(get_buf(c, "rs_in", std::max<size_t>(in_bytes, 1), &din));
+    RET(get_buf(c, "rs_out", std::max<size_t>(out_bytes, 1), &dout));
+    if (in_bytes) HIPCHK(c, hipMemcpyAsync(din, in, in_bytes, hipMemcpyHostToDevice, c->stream));
+    RET(resample_device(c, din, kind, frames, channels, rs, dout, out));
+    if (out_bytes) {
+        HIPCHK(c, hipMemcpyAsync(out_pcm, dout, out_bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return MM_OK;
+}
+
+// The definition restated in plain C++ on the host (no context, no GPU): what the kernel
+// must reproduce, samples and statistics.  Nothing outside in[0, frames * channels) is
+// read, nothing outside out_pcm[0, frames_out * channels) written.
+int mm_resample_host(const int16_t *in, int64_t frames, int channels, const mm_resampler *rs, int16_t *out_pcm,
+                     mm_resample *out) {
+    if (!out || !rs || resample_bad_table(rs) || resample_bad_signal(frames, channels, rs->L, rs->M)) return MM_ERR_ARG;
+    if (frames > 0 && (!in || !out_pcm)) return MM_ERR_ARG;
+    resample_clear(out, frames, channels, rs);
+    const int64_t L = rs->L, M = rs->M, K = rs->K;
+    for (int64_t n = 0; n < out->frames_out; ++n) {
+        const int64_t q = n * M, b = q / L, p = q % L;
+        const int32_t *row = rs->taps + (size_t)(p * K);
+        for (int ch = 0; ch < channels; ++ch) {
+            int64_t acc = 0;
+            for (int64_t k = 0; k < K; ++k) {
+                const int64_t f = b + K / 2 - k;
+                if (f >= 0 && f < frames) acc += (int64_t)row[k] * in[f * channels + ch];
+            }
+            const int64_t v = acc + ((int64_t)1 << (RS_SHIFT - 1));
+            const int64_t y = v >= 0 ? v >> RS_SHIFT : -((-v + (((int64_t)1 << RS_SHIFT) - 1)) >> RS_SHIFT);  // floor
+            const int64_t d = std::min<int64_t>(32767, std::max<int64_t>(-32768, y));
+            if (d != y) ++out->clipped[ch];
+            out->peak[ch] = std::max(out->peak[ch], (int32_t)(d < 0 ? -d : d));
+            out_pcm[n * channels + ch] = (int16_t)d;
+        }
+    }
+    return MM_OK;
+}
+
+int mm_last_resample(mm_ctx *c, mm_resample *out) {
+    if (!c || !out) return set_err(c, MM_ERR_ARG, "bad arguments");
+    if (!c->resample_valid) return set_err(c, MM_ERR_STATE, "the last master call did not resample");
+    *out = c->resample;
+    return MM_OK;
+}
+
+int mm_deliver_device(mm_ctx *c, const mm_job *j, const mm_delivery *dl, const void *d_in, void *d_out, mm_result *res) {
+    if (!c) return MM_ERR_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    return deliver_device(c, j, dl, d_in, d_out, res);
+}
+
+int mm_deliver(mm_ctx *c, const mm_job *j, const mm_delivery *dl, const void *in, void *out, mm_result *res) {
+    if (!c) return MM_ERR_ARG;
+    RET(validate(c, j));
+    if (const char *why = deliver_bad_args(j, dl)) return set_err(c, MM_ERR_ARG, "delivery: %s", why);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t fb = (size_t)j->channels * (j->out_kind == MM_OUT_I16 ? 2 : 4);
+    const size_t in_bytes = (size_t)j->frames_in * j->channels * in_sample_bytes(j->in_kind);
+    const size_t out_bytes = (size_t)rs_frames(j->frames_proc, dl->rs->L, dl->rs->M) * fb;
+    char *d_in, *d_out;
+    RET(get_buf(c, "host_in", std::max<size_t>(in_bytes, 1), &d_in));
+    RET(get_buf(c, "host_out", std::max<size_t>(out_bytes, 1), &d_out));
+    if (in_bytes) HIPCHK(c, hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, c->stream));
+    RET(deliver_device(c, j, dl, d_in, d_out, res));
+    if (out_bytes) HIPCHK(c, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    resolve_events(c);
+    return MM_OK;
+}
+
+// mm_master_wav with the delivery path in the middle: the header carries the resampler's
+// rate_out and the converter's frames_out.
+int mm_deliver_wav(mm_ctx *c, const mm_job *jin, const mm_delivery *dl, const char *in_path, const char *out_path,
+                   mm_result *res) {
+    if (!c) return MM_ERR_ARG;
+    if (!jin || !dl || !in_path || !out_path) return set_err(c, MM_ERR_ARG, "null argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    FileCloser in{fopen(in_path, "rb")};
+    if (!in.f) return set_err(c, MM_ERR_ARG, "%s: cannot open", in_path);
+    mm_job j;
+    mm_wav_info wi;
+    RET(wav_job(c, in.f, in_path, jin, &j, &wi));
+    if (const char *why = deliver_bad_args(&j, dl)) return set_err(c, MM_ERR_ARG, "delivery: %s", why);
+    const size_t out_bytes = (size_t)rs_frames(j.frames_proc, dl->rs->L, dl->rs->M) * j.channels * (j.out_kind == MM_OUT_I16 ? 2 : 4);
+    if (out_bytes > 0xFFFFFFFFull - 36) return set_err(c, MM_ERR_ARG, "output larger than a RIFF file can hold");
+    char *d_in, *d_out;
+    RET(wav_stream_in(c, in.f, in_path, &j, &wi, &d_in));
+    RET(get_buf(c, "host_out", std::max<size_t>(out_bytes, 1), &d_out));
+    RET(deliver_device(c, &j, dl, d_in, d_out, res));
+    return wav_stream_out(c, out_path, j.out_kind, j.channels, dl->rs->rate_out, d_out, out_bytes);
+}
+
+}  // extern "C"

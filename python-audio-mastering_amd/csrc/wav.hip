@@ -1,6 +1,7 @@
 // wav.hip — the WAV file path of the C-ABI (mm_wav_probe, mm_master_wav): RIFF
 // codec and pinned double-buffered staging around the chain.  Included from
-// mastering.hip (its context helpers and master_device).
+// mastering.hip (its context helpers and master_device).  mm_deliver_wav (resample.hip)
+// runs on the same helpers: wav_job, wav_stream_in, wav_stream_out.
 
 extern "C" {
 
@@ -87,46 +88,48 @@ struct FileCloser {
 };
 }  // namespace
 
-int mm_master_wav(mm_ctx *c, const mm_job *jin, const char *in_path, const char *out_path, mm_result *res) {
-    if (!c) return MM_ERR_ARG;
-    if (!jin || !in_path || !out_path) return set_err(c, MM_ERR_ARG, "null argument");
-    HIPCHK(c, hipSetDevice(c->device));
-    FileCloser in{fopen(in_path, "rb")};
-    if (!in.f) return set_err(c, MM_ERR_ARG, "%s: cannot open", in_path);
-    mm_wav_info wi;
-    RET(wav_parse(c, in.f, in_path, &wi));
-    mm_job j = *jin;
-    j.in_kind = wi.format != 1 ? MM_IN_F32 : wi.bits == 16 ? MM_IN_I16 : wi.bits == 24 ? MM_IN_I24 : MM_IN_I32;
-    if (j.frames_in != wi.frames || j.channels != wi.channels || j.rate != wi.rate)
+// The job of a WAV run: the caller's job with in_kind taken from the parsed file, checked
+// against the file's geometry and validated.
+static int wav_job(mm_ctx *c, FILE *f, const char *in_path, const mm_job *jin, mm_job *j, mm_wav_info *wi) {
+    RET(wav_parse(c, f, in_path, wi));
+    *j = *jin;
+    j->in_kind = wi->format != 1 ? MM_IN_F32 : wi->bits == 16 ? MM_IN_I16 : wi->bits == 24 ? MM_IN_I24 : MM_IN_I32;
+    if (j->frames_in != wi->frames || j->channels != wi->channels || j->rate != wi->rate)
         return set_err(c, MM_ERR_ARG, "%s: job built for %lld frames x %d ch @ %d Hz, file has %lld x %d @ %d", in_path,
-                       (long long)j.frames_in, j.channels, j.rate, (long long)wi.frames, wi.channels, wi.rate);
-    RET(validate(c, &j));
+                       (long long)j->frames_in, j->channels, j->rate, (long long)wi->frames, wi->channels, wi->rate);
+    return validate(c, j);
+}
+
+// file -> pinned -> HBM ("host_in"): chunk k is read while chunk k-1 is in flight
+static int wav_stream_in(mm_ctx *c, FILE *f, const char *in_path, const mm_job *j, const mm_wav_info *wi, char **d_in_out) {
     // (the packed bytes as they lie in the file: a staging boundary may split a sample)
-    const size_t in_bytes = (size_t)wi.frames * wi.channels * in_sample_bytes(j.in_kind);
-    const size_t out_bytes = (size_t)j.frames_proc * j.channels * (j.out_kind == MM_OUT_I16 ? 2 : 4);
-    if (out_bytes > 0xFFFFFFFFull - 36) return set_err(c, MM_ERR_ARG, "output larger than a RIFF file can hold");
-    char *d_in, *d_out;
+    const size_t in_bytes = (size_t)wi->frames * wi->channels * in_sample_bytes(j->in_kind);
+    char *d_in;
     RET(get_buf(c, "host_in", std::max<size_t>(in_bytes, 1), &d_in));
-    RET(get_buf(c, "host_out", std::max<size_t>(out_bytes, 1), &d_out));
     RET(ensure_pinned(c));
-    // file -> pinned -> HBM: chunk k is read while chunk k-1 is in flight
-    if (fseeko(in.f, wi.data_offset, SEEK_SET) != 0) return set_err(c, MM_ERR_ARG, "%s: cannot seek", in_path);
+    if (fseeko(f, wi->data_offset, SEEK_SET) != 0) return set_err(c, MM_ERR_ARG, "%s: cannot seek", in_path);
     size_t k = 0;
     for (size_t off = 0; off < in_bytes; ++k) {
         const int b = (int)(k & 1);
         const size_t n = std::min(PIN_CHUNK, in_bytes - off);
         if (k >= 2) HIPCHK(c, hipEventSynchronize(c->pin_ev[b]));
-        if (fread(c->pin[b], 1, n, in.f) != n) return set_err(c, MM_ERR_ARG, "%s: short read", in_path);
+        if (fread(c->pin[b], 1, n, f) != n) return set_err(c, MM_ERR_ARG, "%s: short read", in_path);
         HIPCHK(c, hipMemcpyAsync(d_in + off, c->pin[b], n, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipEventRecord(c->pin_ev[b], c->stream));
         off += n;
     }
-    RET(master_device(c, &j, d_in, d_out, res));
-    // HBM -> pinned -> file: chunk k is written while chunk k+1 is copied back
+    *d_in_out = d_in;
+    return MM_OK;
+}
+
+// The 44-byte header, then HBM -> pinned -> file: chunk k is written while chunk k+1 is
+// copied back.  Synchronous on return.
+static int wav_stream_out(mm_ctx *c, const char *out_path, int out_kind, int channels, int rate, const char *d_out,
+                          size_t out_bytes) {
     FileCloser out{fopen(out_path, "wb")};
     if (!out.f) return set_err(c, MM_ERR_ARG, "%s: cannot create", out_path);
-    const int tag = j.out_kind == MM_OUT_I16 ? 1 : 3, bits = j.out_kind == MM_OUT_I16 ? 16 : 32;
-    const int ba = j.channels * bits / 8;
+    const int tag = out_kind == MM_OUT_I16 ? 1 : 3, bits = out_kind == MM_OUT_I16 ? 16 : 32;
+    const int ba = channels * bits / 8;
     unsigned char hdr[44];
     auto put32 = [&](int at, uint32_t v) {
         for (int i = 0; i < 4; ++i) hdr[at + i] = (unsigned char)(v >> (8 * i));
@@ -140,16 +143,15 @@ int mm_master_wav(mm_ctx *c, const mm_job *jin, const char *in_path, const char 
     memcpy(hdr + 8, "WAVEfmt ", 8);
     put32(16, 16);
     put16(20, tag);
-    put16(22, j.channels);
-    put32(24, j.rate);
-    put32(28, (uint32_t)j.rate * ba);
+    put16(22, channels);
+    put32(24, rate);
+    put32(28, (uint32_t)rate * ba);
     put16(32, ba);
     put16(34, bits);
     memcpy(hdr + 36, "data", 4);
     put32(40, (uint32_t)out_bytes);
     if (fwrite(hdr, 1, 44, out.f) != 44) return set_err(c, MM_ERR_ARG, "%s: write failed", out_path);
-    size_t prev_n = 0;
-    k = 0;
+    size_t prev_n = 0, k = 0;
     for (size_t off = 0; off < out_bytes; ++k) {
         const int b = (int)(k & 1);
         const size_t n = std::min(PIN_CHUNK, out_bytes - off);
@@ -170,6 +172,24 @@ int mm_master_wav(mm_ctx *c, const mm_job *jin, const char *in_path, const char 
     HIPCHK(c, hipStreamSynchronize(c->stream));
     resolve_events(c);
     return MM_OK;
+}
+
+int mm_master_wav(mm_ctx *c, const mm_job *jin, const char *in_path, const char *out_path, mm_result *res) {
+    if (!c) return MM_ERR_ARG;
+    if (!jin || !in_path || !out_path) return set_err(c, MM_ERR_ARG, "null argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    FileCloser in{fopen(in_path, "rb")};
+    if (!in.f) return set_err(c, MM_ERR_ARG, "%s: cannot open", in_path);
+    mm_job j;
+    mm_wav_info wi;
+    RET(wav_job(c, in.f, in_path, jin, &j, &wi));
+    const size_t out_bytes = (size_t)j.frames_proc * j.channels * (j.out_kind == MM_OUT_I16 ? 2 : 4);
+    if (out_bytes > 0xFFFFFFFFull - 36) return set_err(c, MM_ERR_ARG, "output larger than a RIFF file can hold");
+    char *d_in, *d_out;
+    RET(wav_stream_in(c, in.f, in_path, &j, &wi, &d_in));
+    RET(get_buf(c, "host_out", std::max<size_t>(out_bytes, 1), &d_out));
+    RET(master_device(c, &j, d_in, d_out, res));
+    return wav_stream_out(c, out_path, j.out_kind, j.channels, j.rate, d_out, out_bytes);
 }
 
 }  // extern "C"

@@ -209,6 +209,80 @@ def ceiling_window(rate: int) -> int:
     return min(CEILING_MAX_WINDOW, max(1, q))
 
 
+# The sample-rate converter (include/mastering.h: mm_resampler).  The library convolves
+# integers with the integer taps designed here and never evaluates a window.
+RESAMPLE_MAX_PHASES = 640   # L and M
+RESAMPLE_MAX_TAPS = 1024    # K
+RESAMPLE_CROSSINGS = 64     # zero crossings a side
+RESAMPLE_CUTOFF = 0.475     # of the lower sample rate
+RESAMPLE_BETA = 10.0        # Kaiser window
+RESAMPLE_ONE = 1 << 22      # DC gain of every phase
+
+
+def resample_geometry(rate_in: int, rate_out: int):
+    """(L, M, K) of the polyphase converter rate_in -> rate_out: L = rate_out / g and
+    M = rate_in / g with g their gcd, K = 2 * ceil(64 * max(L, M) / L) taps a phase (64
+    zero crossings a side, stretched by the decimation ratio).  ValueError outside the
+    library's limits (L, M <= 640, K <= 1024, L != M)."""
+    rate_in, rate_out = int(rate_in), int(rate_out)
+    if rate_in < 1 or rate_out < 1:
+        raise ValueError(f"sample rates must be positive (got {rate_in} -> {rate_out})")
+    g = math.gcd(rate_in, rate_out)
+    L, M = rate_out // g, rate_in // g
+    if L == M:
+        raise ValueError(f"resampling {rate_in} -> {rate_out} Hz: the rates are equal")
+    K = 2 * ((RESAMPLE_CROSSINGS * max(L, M) + L - 1) // L)
+    if L > RESAMPLE_MAX_PHASES or M > RESAMPLE_MAX_PHASES or K > RESAMPLE_MAX_TAPS:
+        raise ValueError(f"resampling {rate_in} -> {rate_out} Hz needs L = {L}, M = {M}, K = {K}: outside the "
+                         f"converter's limits (L, M <= {RESAMPLE_MAX_PHASES}, K <= {RESAMPLE_MAX_TAPS})")
+    return L, M, K
+
+
+@functools.lru_cache(maxsize=16)
+def _resample_table(rate_in: int, rate_out: int):
+    L, M, K = resample_geometry(rate_in, rate_out)
+    half = K // 2
+    p = np.arange(L, dtype=np.int64)[:, None]
+    k = np.arange(K, dtype=np.int64)[None, :]
+    d = p + (k - half) * L                    # distance in ticks of the L-times-oversampled grid
+    t = d / L
+    u = t / half
+    fc = RESAMPLE_CUTOFF * min(1.0, L / M)
+    w = np.where(np.abs(u) <= 1.0,
+                 np.i0(RESAMPLE_BETA * np.sqrt(np.maximum(1.0 - u * u, 0.0))) / np.i0(RESAMPLE_BETA), 0.0)
+    h = 2.0 * fc * np.sinc(2.0 * fc * t) * w
+    h = h / h.sum(axis=1, keepdims=True)
+    c = np.rint(h * RESAMPLE_ONE).astype(np.int64)
+    for row in c:  # DC gain exactly 2^22: the residue goes to the first tap of largest magnitude
+        row[int(np.argmax(np.abs(row)))] += RESAMPLE_ONE - int(row.sum())
+    c = np.ascontiguousarray(c, dtype=np.int32)
+    assert c.shape == (L, K) and int(np.abs(c.astype(np.int64)).sum(axis=1).max()) < 1 << 24
+    c.setflags(write=False)
+    head = np.array([L, M, K], np.int64).tobytes()
+    key = int.from_bytes(hashlib.blake2b(head + c.tobytes(), digest_size=8).digest(), "little") or 1
+    return L, M, K, c, key
+
+
+def resample_taps(rate_in: int, rate_out: int):
+    """The converter's taps (L, M, K, c): c int32 [L][K] (read-only), a Kaiser-windowed
+    sinc (beta 10, cutoff 0.475 of the lower rate) sampled at d = p + (k - K/2) * L ticks
+    of the oversampled grid for phase p and tap k, every row normalised to unit sum in
+    f64, rounded to multiples of 2^-22 and corrected on its largest tap so that each
+    phase has DC gain exactly 2^22.  ValueError for a pair outside the limits."""
+    return _resample_table(int(rate_in), int(rate_out))[:4]
+
+
+def resample_key(rate_in: int, rate_out: int) -> int:
+    """Content key (nonzero 64-bit) of resample_taps' table: the context caches its device
+    copy by this key (mm_resampler.taps_key)."""
+    return _resample_table(int(rate_in), int(rate_out))[4]
+
+
+def resample_frames(frames: int, L: int, M: int) -> int:
+    """Output frames of the converter: ceil(frames * L / M) (mm_resample_frames)."""
+    return -(-int(frames) * int(L) // int(M))
+
+
 def crossover_sections(rate, low_hz=LOW_CROSSOVER, high_hz=HIGH_CROSSOVER):
     """AME:197-198: butter(4) LP and HP as 2 SOS sections each."""
     lp = scipy.signal.butter(4, low_hz, btype="lowpass", fs=rate, output="sos")

@@ -350,6 +350,8 @@ def master_time_sharded(backend, plan: RankPlan, params: dict, d_in, d_out, coll
     `d_out` receives its processed frames [plan.f0, plan.f1)."""
     if params.get("ceiling_dbtp") is not None:
         raise ValueError("the true-peak ceiling needs the whole track: not available on the time-sharded path")
+    if params.get("output_rate") is not None:
+        raise ValueError("delivery at another rate needs the whole track: not available on the time-sharded path")
     # checked before any work or collective: the path depends only on the collective's
     # kind and the plan, the same on every rank (raises since round 5; see INTEGRATION.md)
     if isinstance(coll, LibraryCollectives) and (coll.ctx is not getattr(backend, "ctx", None)

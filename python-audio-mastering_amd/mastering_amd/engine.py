@@ -46,13 +46,29 @@ def comp_super_frames(rate: int, tile: int = design.DEFAULT_TILE) -> int:
     return max(1, int(round(COMP_SUPER_FRAMES / design.DEFAULT_TILE))) * tile
 
 
+class Resampler:
+    """The mm_resampler POD of a rate pair plus the taps it points to (design.resample_taps;
+    ValueError for a pair outside the converter's limits)."""
+
+    def __init__(self, rate_in: int, rate_out: int):
+        self.L, self.M, self.K, self.taps = design.resample_taps(rate_in, rate_out)
+        rs = native.MMResampler()
+        rs.rate_in, rs.rate_out, rs.L, rs.M, rs.K = int(rate_in), int(rate_out), self.L, self.M, self.K
+        rs.taps = self.taps.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        rs.taps_key = design.resample_key(rate_in, rate_out)
+        self.rs = rs
+
+    def frames_out(self, frames: int) -> int:
+        return design.resample_frames(frames, self.L, self.M)
+
+
 class Job:
     """A planned mastering job: the mm_job POD plus the host arrays it points to."""
 
     def __init__(self, frames_in: int, rate: int, channels: int, params: dict, out_kind: int = native.MM_OUT_I16,
                  seg_bounds=None, check_length: bool = True, single_chunk: bool = False,
                  crossover=(design.LOW_CROSSOVER, design.HIGH_CROSSOVER), report: bool = False,
-                 ceiling_dbtp: float | None = None):
+                 ceiling_dbtp: float | None = None, output_rate: int | None = None):
         """`seg_bounds` (time-sharded ranks, distributed.py): this range's loudness
         segment bounds relative to its first frame; the whole-track gating then
         happens on the host after the all-reduce.  `check_length=False` skips
@@ -65,9 +81,23 @@ class Job:
         without a LUFS target.  `ceiling_dbtp` (in [-24, 0]): hold the delivered output
         under this true-peak ceiling (mm_job.ceiling_q28, design.ceiling_q28) after the
         chain and before the report; not on a time-sharded range, whose rank does not
-        hold its neighbours' frames."""
+        hold its neighbours' frames.  `output_rate` (other than `rate`): plan a delivery
+        at that rate (mm_delivery, self.delivery; run it with mm_deliver*): the chain
+        runs at `rate`, its output is converted (design.resample_taps), and the ceiling
+        (window design.ceiling_window(output_rate)) and the report act on the converted
+        signal, so mm_job.ceiling_q28 and meter_on stay 0; None or `rate` itself plans
+        exactly the job planned without it.  ValueError for a rate pair outside the
+        converter's limits."""
         if ceiling_dbtp is not None and seg_bounds is not None:
             raise ValueError("the true-peak ceiling needs the whole track: not available on a time-sharded range")
+        if output_rate is not None and int(output_rate) == int(rate):
+            output_rate = None
+        if output_rate is not None and (seg_bounds is not None or single_chunk):
+            raise ValueError("delivery at another rate needs the whole chain: not available on a time-sharded "
+                             "range or a per-stage operator")
+        self.output_rate = None if output_rate is None else int(output_rate)
+        self.resampler = Resampler(rate, output_rate) if output_rate is not None else None
+        plan_report, report = report, bool(report) and output_rate is None  # (a delivery's report is planned below)
         if channels not in (1, 2):
             raise ValueError("only mono and stereo are supported (AME:119,137,152)")
         params = dict(params or {})
@@ -156,6 +186,18 @@ class Job:
             j.seg_bounds = self._segb.ctypes.data_as(native.c_int64_p)
             j.block_scale = scale
         self.job = j
+        self.frames_out, self.delivery = self.frames_proc, None
+        if self.resampler is not None:  # the ceiling and the report move behind the converter
+            self.frames_out = self.resampler.frames_out(self.frames_proc)
+            d = native.MMDelivery()
+            d.rs = ctypes.pointer(self.resampler.rs)
+            d.ceiling_q28, j.ceiling_q28 = j.ceiling_q28, 0
+            d.window = design.ceiling_window(self.output_rate)
+            d.meter_on = int(bool(plan_report))
+            if plan_report and self.frames_out >= 0.4 * self.output_rate:  # the output's loudness, as meter_pcm plans it
+                self._loud = Job(self.frames_out, self.output_rate, self.channels, {}, single_chunk=True, report=True)
+                d.loud = ctypes.pointer(self._loud.job)
+            self.delivery = d
 
     @staticmethod
     @functools.lru_cache(maxsize=32)
@@ -282,6 +324,49 @@ def _add_ceiling(info: dict, job: "Job", ctx: native.Context) -> dict:
     return info
 
 
+def resample_dict(m: native.MMResample) -> dict:
+    """An mm_resample as `info["resample"]`: the struct's integers (clipped and peak as
+    per-channel lists) and the largest delivered sample in dBFS.  No reference counterpart."""
+    ch = int(m.channels)
+    d = {f: int(getattr(m, f)) for f in ("frames_in", "frames_out", "channels", "rate_in", "rate_out", "L", "M", "K")}
+    d["clipped"] = [int(m.clipped[c]) for c in range(ch)]
+    d["peak"] = [int(m.peak[c]) for c in range(ch)]
+    d["peak_dbfs"] = _db(max(d["peak"], default=0) / 32768.0)
+    return d
+
+
+def _deliver_info(info: dict, job: "Job", ctx: native.Context) -> dict:
+    """The info of a delivery at another rate: the chain's, with the delivered frames and
+    rate, the converter's statistics and the ceiling and report of the converted signal."""
+    m = native.MMResample()
+    ctx.check(ctx.lib.mm_last_resample(ctx.ptr, ctypes.byref(m)), "mm_last_resample")
+    info["frames"], info["rate"], info["resample"] = job.frames_out, job.output_rate, resample_dict(m)
+    if job.delivery.ceiling_q28:
+        info["ceiling"] = ceiling_dict(ceilings(ctx, 1)[0])
+    if job.delivery.meter_on:
+        info["report"] = report_dict(meters(ctx, 1)[0], job.job.lufs_target if job.job.lufs_on else None)
+    return info
+
+
+def resample_pcm(pcm: np.ndarray, rate_in: int, rate_out: int, device: int = 0):
+    """Convert an int16 (or float32 = int16 / 32768) array [N] or [N, ch] to another
+    sample rate without mastering it (mm_resample_pcm): returns (a new array of
+    ceil(N * L / M) frames, resample_dict).  ValueError for a rate pair outside the
+    converter's limits (design.resample_geometry)."""
+    ch = 1 if pcm.ndim == 1 else pcm.shape[1]
+    x, in_kind = _device_input(pcm)
+    kind = native.MM_OUT_I16 if in_kind == native.MM_IN_I16 else native.MM_OUT_F32
+    rs = Resampler(rate_in, rate_out)
+    n_out = rs.frames_out(x.shape[0])
+    out = np.empty((n_out,) if pcm.ndim == 1 else (n_out, ch), x.dtype)
+    ctx = native.context(device)
+    m = native.MMResample()
+    ctx.check(ctx.lib.mm_resample_pcm(ctx.ptr, x.ctypes.data_as(ctypes.c_void_p), kind, x.shape[0], ch,
+                                      ctypes.byref(rs.rs), out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(m)),
+              "mm_resample_pcm")
+    return out, resample_dict(m)
+
+
 def ceiling_pcm(pcm: np.ndarray, rate: int, ceiling_dbtp: float, window: int | None = None, device: int = 0):
     """Hold an int16 (or float32 = int16 / 32768) array [N] or [N, ch] under a true-peak
     ceiling without mastering it (mm_ceiling_pcm): returns (a new array, ceiling_dict).
@@ -321,17 +406,27 @@ def master_pcm(pcm: np.ndarray, rate: int, params: dict, out_kind: int = native.
     exactly as the float32 array of the same values; the output stays 16-bit.
     params['report'] (truthy) adds info['report'] (report_dict) on the output;
     params['ceiling_dbtp'] holds the output under that true-peak ceiling first and adds
-    info['ceiling'] (ceiling_dict)."""
+    info['ceiling'] (ceiling_dict).  params['output_rate'] other than `rate` delivers at
+    that rate (mm_deliver): the chain's output is converted on the GPU, the ceiling and
+    the report then act on the converted signal, out_pcm has info['frames'] frames at
+    info['rate'] and info['resample'] (resample_dict) is added; absent or equal to `rate`,
+    the call is exactly the call without it."""
     ch = 1 if pcm.ndim == 1 else pcm.shape[1]
     params = dict(params or {})
     report = bool(params.pop("report", False))
     ceiling = params.pop("ceiling_dbtp", None)
-    job = Job(pcm.shape[0], rate, ch, params, out_kind, report=report, ceiling_dbtp=ceiling)
+    output_rate = params.pop("output_rate", None)
+    job = Job(pcm.shape[0], rate, ch, params, out_kind, report=report, ceiling_dbtp=ceiling, output_rate=output_rate)
     x, job.job.in_kind = _device_input(pcm, wide=True)
-    shape = (job.frames_proc,) if ch == 1 else (job.frames_proc, ch)
+    shape = (job.frames_out,) if ch == 1 else (job.frames_out, ch)
     out = np.empty(shape, np.int16 if out_kind == native.MM_OUT_I16 else np.float32)
     ctx = native.context(device)
     res = native.MMResult()
+    if job.delivery is not None:
+        ctx.check(ctx.lib.mm_deliver(ctx.ptr, ctypes.byref(job.job), ctypes.byref(job.delivery),
+                                     x.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p),
+                                     ctypes.byref(res)), "mm_deliver")
+        return out, _deliver_info(_info(job, res), job, ctx)
     ctx.check(ctx.lib.mm_master(ctx.ptr, ctypes.byref(job.job), x.ctypes.data_as(ctypes.c_void_p),
                                 out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(res)), "mm_master")
     return out, _add_report(_add_ceiling(_info(job, res), job, ctx), job, ctx)
@@ -349,7 +444,14 @@ def master_device(ctx: native.Context, job: Job, d_in: int, d_out: int, res: nat
     """Device-resident variant (pointers from e.g. torch tensors).  With `res`
     the loudness, gain and compressor statistics are returned in it.  A job planned
     with `report=True` is metered: `meters(ctx)[0]` (see report_dict); one planned with
-    `ceiling_dbtp` is held under it first: `ceilings(ctx)[0]` (see ceiling_dict)."""
+    `ceiling_dbtp` is held under it first: `ceilings(ctx)[0]` (see ceiling_dict).  One planned
+    with `output_rate` is delivered at that rate (mm_deliver_device): `d_out` then holds
+    `job.frames_out` frames."""
+    if job.delivery is not None:
+        ctx.check(ctx.lib.mm_deliver_device(ctx.ptr, ctypes.byref(job.job), ctypes.byref(job.delivery),
+                                            ctypes.c_void_p(d_in), ctypes.c_void_p(d_out),
+                                            ctypes.byref(res) if res is not None else None), "mm_deliver_device")
+        return res
     ctx.check(ctx.lib.mm_master_device(ctx.ptr, ctypes.byref(job.job), ctypes.c_void_p(d_in),
                                        ctypes.c_void_p(d_out), ctypes.byref(res) if res is not None else None),
               "mm_master_device")
@@ -365,6 +467,8 @@ def master_batch(ctx: native.Context, jobs, d_ins, d_outs, with_results: bool = 
     metered: `meters(ctx, len(jobs))` holds one mm_meter per job, in job order; jobs
     planned with `ceiling_dbtp` are held under it: `ceilings(ctx, len(jobs))`."""
     n = len(jobs)
+    if any(j.delivery is not None for j in jobs):
+        raise ValueError("delivery at another rate (output_rate) is not available for a batch")
     arr = (native.MMJob * n)(*[j.job for j in jobs])
     ins = (ctypes.c_void_p * n)(*[ctypes.c_void_p(int(p)) for p in d_ins])
     outs = (ctypes.c_void_p * n)(*[ctypes.c_void_p(int(p)) for p in d_outs])
@@ -382,22 +486,33 @@ def process(input_path: str, output_path: str, params: dict, device: int = 0, ve
     exactly what the float32 file of the same values gives.
     params['report'] (truthy) adds info['report'] (report_dict) on the written samples;
     params['ceiling_dbtp'] holds them under that true-peak ceiling (info['ceiling']).
+    params['output_rate'] other than the file's rate delivers at that rate (mm_deliver_wav):
+    the header carries it and info['frames'] / info['rate'] / info['resample'] describe the
+    written file; the ceiling and the report act on the converted samples.
     Raises ValueError for unreadable/unsupported input and RuntimeError for device
     failures, like the reference (AME:110-113)."""
     params = dict(params or {})
     fmt = params.pop("output_format", "pcm16")
     report = bool(params.pop("report", False))
     ceiling = params.pop("ceiling_dbtp", None)
+    output_rate = params.pop("output_rate", None)
     kind = native.MM_OUT_F32 if fmt == "f32" else native.MM_OUT_I16
     wi = wav_info(input_path, device)
     if verbose:
         print(f"Loaded {input_path}: {wi.frames} frames @ {wi.rate} Hz")
-    job = Job(wi.frames, wi.rate, wi.channels, params, kind, report=report, ceiling_dbtp=ceiling)
+    job = Job(wi.frames, wi.rate, wi.channels, params, kind, report=report, ceiling_dbtp=ceiling,
+              output_rate=output_rate)
     ctx = native.context(device)
     res = native.MMResult()
-    ctx.check(ctx.lib.mm_master_wav(ctx.ptr, ctypes.byref(job.job), os.fsencode(input_path), os.fsencode(output_path),
-                                    ctypes.byref(res)), "mm_master_wav")
-    info = _add_report(_add_ceiling(_info(job, res), job, ctx), job, ctx)
+    if job.delivery is not None:
+        ctx.check(ctx.lib.mm_deliver_wav(ctx.ptr, ctypes.byref(job.job), ctypes.byref(job.delivery),
+                                         os.fsencode(input_path), os.fsencode(output_path), ctypes.byref(res)),
+                  "mm_deliver_wav")
+        info = _deliver_info(_info(job, res), job, ctx)
+    else:
+        ctx.check(ctx.lib.mm_master_wav(ctx.ptr, ctypes.byref(job.job), os.fsencode(input_path),
+                                        os.fsencode(output_path), ctypes.byref(res)), "mm_master_wav")
+        info = _add_report(_add_ceiling(_info(job, res), job, ctx), job, ctx)
     if verbose and info["loudness"] is not None:
         print(f"Current loudness: {info['loudness']:.2f} LUFS. Applying {info['gain_db']:.2f} dB gain...")
     info["output_path"] = os.path.abspath(output_path)

@@ -84,6 +84,24 @@ class MMCeiling(ctypes.Structure):
                 ("limited_frames", ctypes.c_int64)]
 
 
+class MMResampler(ctypes.Structure):
+    _fields_ = [("rate_in", ctypes.c_int32), ("rate_out", ctypes.c_int32), ("L", ctypes.c_int32),
+                ("M", ctypes.c_int32), ("K", ctypes.c_int32), ("_pad", ctypes.c_int32),
+                ("taps", ctypes.POINTER(ctypes.c_int32)), ("taps_key", ctypes.c_uint64)]
+
+
+class MMResample(ctypes.Structure):
+    _fields_ = [("frames_in", ctypes.c_int64), ("frames_out", ctypes.c_int64), ("channels", ctypes.c_int32),
+                ("rate_in", ctypes.c_int32), ("rate_out", ctypes.c_int32), ("L", ctypes.c_int32),
+                ("M", ctypes.c_int32), ("K", ctypes.c_int32), ("clipped", ctypes.c_int64 * 2),
+                ("peak", ctypes.c_int32 * 2)]
+
+
+class MMDelivery(ctypes.Structure):
+    _fields_ = [("rs", ctypes.POINTER(MMResampler)), ("ceiling_q28", ctypes.c_int32), ("window", ctypes.c_int32),
+                ("meter_on", ctypes.c_int32), ("_pad", ctypes.c_int32), ("loud", ctypes.POINTER(MMJob))]
+
+
 ABI_VERSION = 5  # MM_ABI_VERSION of include/mastering.h
 
 
@@ -109,7 +127,9 @@ EXPORTS = ("mm_create", "mm_destroy", "mm_last_error", "mm_sync", "mm_version", 
            "mm_meter_span",
            "mm_ceiling_device", "mm_ceiling_pcm", "mm_ceiling_host", "mm_last_ceilings", "mm_ceiling_span",
            "mm_ceiling_max_window",
-           "mm_pcm_decode_device", "mm_op_pcm_decode", "mm_pcm_decode_host", "mm_pcm_decode_span")
+           "mm_pcm_decode_device", "mm_op_pcm_decode", "mm_pcm_decode_host", "mm_pcm_decode_span",
+           "mm_resample_device", "mm_resample_pcm", "mm_resample_host", "mm_resample_frames", "mm_resample_span",
+           "mm_last_resample", "mm_deliver_device", "mm_deliver", "mm_deliver_wav")
 
 _lib = None
 _lock = threading.Lock()
@@ -208,6 +228,19 @@ def load():
             "mm_op_pcm_decode": ([vp, ctypes.c_int, vp, ctypes.c_int64, vp], ctypes.c_int),
             "mm_pcm_decode_host": ([ctypes.c_int, vp, ctypes.c_int64, vp], ctypes.c_int),
             "mm_pcm_decode_span": ([], ctypes.c_int),
+            "mm_resample_device": ([vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, P(MMResampler), vp,
+                                    P(MMResample)], ctypes.c_int),
+            "mm_resample_pcm": ([vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, P(MMResampler), vp,
+                                 P(MMResample)], ctypes.c_int),
+            "mm_resample_host": ([P(ctypes.c_int16), ctypes.c_int64, ctypes.c_int, P(MMResampler), P(ctypes.c_int16),
+                                  P(MMResample)], ctypes.c_int),
+            "mm_resample_frames": ([ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, c_int64_p], ctypes.c_int),
+            "mm_resample_span": ([], ctypes.c_int),
+            "mm_last_resample": ([vp, P(MMResample)], ctypes.c_int),
+            "mm_deliver_device": ([vp, P(MMJob), P(MMDelivery), vp, vp, P(MMResult)], ctypes.c_int),
+            "mm_deliver": ([vp, P(MMJob), P(MMDelivery), vp, vp, P(MMResult)], ctypes.c_int),
+            "mm_deliver_wav": ([vp, P(MMJob), P(MMDelivery), ctypes.c_char_p, ctypes.c_char_p, P(MMResult)],
+                               ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             fn = getattr(lib, name)
