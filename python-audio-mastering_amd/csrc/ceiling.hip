@@ -10,15 +10,16 @@
 // g_t = floor(C_t * 2^16 / TP1): requantising moves |Y| by at most 8285.5 < 8286, so
 // the trimmed peak is at most C_t + 8285.5 < C.
 //
-// Three kernels.  ceil_need has the meter's structure (LDS int16 lines, 24 packed dot
-// products per frame and channel) and writes r - 1 as uint16 to a plane; ceil_apply
+// Three kernels.  ceil_need runs the meter's own oversampler (meter.hip: tp_stage,
+// tp_window, tp_frame) and writes r - 1 as uint16 to a plane; ceil_apply
 // stages the plane with its halo in LDS, forms both window minima by log-step doubling
 // and the box sums from one LDS scan, and rewrites the samples in place; ceil_trim is
 // pointwise.  The true peak after the limiter is the meter's own kernel.  All results
 // are integers combined with min / max / add: nothing depends on the launch geometry.
 //
-// Included at the end of mastering.hip after meter.hip (its taps, dot product, wave
-// reductions and meter_launch).
+// Included at the end of mastering.hip after pcm16.h (frames, wave reductions, refusals,
+// dispatch_pcm) and meter.hip (the oversampler, tp_host, meter_launch, meter_device).  The
+// end of a master call, finish_delivered, is here: the ceiling, then the report.
 
 namespace mm {
 
@@ -61,52 +62,18 @@ __global__ void __launch_bounds__(METER_THREADS) ceil_need_kernel(const T *__res
     __shared__ int red[METER_THREADS / 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t base = (int64_t)blockIdx.x * METER_SPAN;
-    const int64_t f0 = base - METER_HALO;  // frame of LDS index 0
-    for (int i = threadIdx.x; i < METER_LINE; i += METER_THREADS) {
-        const int64_t f = f0 + i;
-        const bool ok = f >= 0 && f < N;
-        if constexpr (CH == 2) {
-            int l = 0, r = 0;
-            if (ok) {
-                if constexpr (sizeof(T) == 2) {
-                    const uint32_t d = reinterpret_cast<const uint32_t *>(in)[f];
-                    l = (int16_t)(d & 0xFFFFu);
-                    r = (int16_t)(d >> 16);
-                } else {
-                    const float2 d = reinterpret_cast<const float2 *>(in)[f];
-                    l = meter_sample<float>(d.x);
-                    r = meter_sample<float>(d.y);
-                }
-            }
-            line[0][i] = (int16_t)l;
-            line[1][i] = (int16_t)r;
-        } else {
-            line[0][i] = ok ? (int16_t)meter_sample<T>(in[f]) : (int16_t)0;
-        }
-    }
-    __syncthreads();
+    tp_stage<CH, T>(line, in, N, base);
     int pm[METER_FPT];
 #pragma unroll
     for (int j = 0; j < METER_FPT; ++j) pm[j] = 0;
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
-        // window w[i] = s[m0 - 12 + i], i < 20, as dwords D[i] = (w[2i], w[2i+1])
-        const uint4 *src = reinterpret_cast<const uint4 *>(&line[c][threadIdx.x * METER_FPT]);
-        const uint4 a = src[0], b = src[1];
-        const uint2 e = *reinterpret_cast<const uint2 *>(src + 2);
-        const uint32_t D[10] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, e.x, e.y};
-        uint32_t P[19];  // P[i] = (w[i], w[i+1])
-#pragma unroll
-        for (int i = 0; i < 19; ++i) P[i] = (i & 1) ? ((D[i / 2] >> 16) | (D[i / 2 + 1] << 16)) : D[i / 2];
+        uint32_t P[19];
+        tp_window(&line[c][threadIdx.x * METER_FPT], P);
 #pragma unroll
         for (int j = 0; j < METER_FPT; ++j) {
 #pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                int acc = 0;
-#pragma unroll
-                for (int q = 0; q < 6; ++q) acc = tp_dot2(P[j + 11 - 2 * q], tp_pair(p, q), acc);
-                pm[j] = max(pm[j], acc < 0 ? -acc : acc);
-            }
+            for (int p = 0; p < 4; ++p) pm[j] = max(pm[j], tp_frame(P, j, p));
         }
     }
     int best = 0;
@@ -173,11 +140,14 @@ __device__ __forceinline__ uint16_t *ceil_window_min(uint16_t *cur, uint16_t *nx
     return nxt;
 }
 
-template <typename T>
-__device__ __forceinline__ T ceil_scale(T v, int g) {
-    const int s = (meter_sample<T>(v) * g + (1 << 15)) >> 16;  // |s * g| < 2^31: exact, arithmetic shift
-    if constexpr (sizeof(T) == 2) return (T)s;
-    else return (float)s * (1.0f / 32768.0f);
+// frame n of pcm by g, in place
+template <int CH, typename T>
+__device__ __forceinline__ void ceil_scale(T *pcm, int64_t n, int g) {
+    int s[CH];
+    load_frame<CH, T>(pcm, n, s);
+#pragma unroll
+    for (int c = 0; c < CH; ++c) s[c] = (s[c] * g + (1 << 15)) >> 16;  // |s * g| < 2^31: exact, arithmetic shift
+    store_frame<CH, T>(pcm, n, s);
 }
 
 // One workgroup per CEIL_SPAN frames n in [base, base + CEIL_SPAN).  It needs h on
@@ -248,21 +218,7 @@ __global__ void __launch_bounds__(CEIL_THREADS) ceil_apply_kernel(T *__restrict_
         if (g == (uint32_t)CEIL_ONE) continue;
         ++count;
         red = max(red, CEIL_ONE - (int)g);
-        if constexpr (CH == 2 && sizeof(T) == 2) {
-            uint32_t *p = reinterpret_cast<uint32_t *>(pcm) + n;
-            const uint32_t d = *p;
-            const int l = ceil_scale<int16_t>((int16_t)(d & 0xFFFFu), (int)g);
-            const int r = ceil_scale<int16_t>((int16_t)(d >> 16), (int)g);
-            *p = ((uint32_t)l & 0xFFFFu) | ((uint32_t)r << 16);
-        } else if constexpr (CH == 2) {
-            float2 *p = reinterpret_cast<float2 *>(pcm) + n;
-            float2 d = *p;
-            d.x = ceil_scale<float>(d.x, (int)g);
-            d.y = ceil_scale<float>(d.y, (int)g);
-            *p = d;
-        } else {
-            pcm[n] = ceil_scale<T>(pcm[n], (int)g);
-        }
+        ceil_scale<CH, T>(pcm, n, (int)g);
     }
     count = wave_sum_u32(count);
     red = wave_max_i32(red);
@@ -285,7 +241,7 @@ __global__ void __launch_bounds__(CEIL_THREADS) ceil_apply_kernel(T *__restrict_
 template <typename T>
 __global__ void __launch_bounds__(256) ceil_trim_kernel(T *__restrict__ pcm, int64_t n, int g) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) pcm[i] = ceil_scale<T>(pcm[i], g);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) ceil_scale<1, T>(pcm, i, g);
 }
 
 }  // namespace mm
@@ -303,22 +259,12 @@ void ceiling_clear(mm_ceiling *o, int64_t frames, int channels, int32_t C, int32
     o->trim_q16 = CEIL_ONE;
 }
 
-// why (C, W, frames, channels) is not a ceiling job, or null
+// why (C, W) on a signal of (frames, channels) is not a ceiling job, or null
 const char *ceiling_bad_args(int64_t frames, int channels, int32_t C, int32_t W) {
-    if (channels != 1 && channels != 2) return "channels must be 1 or 2";
+    if (const char *why = pcm_refusal(channels, frames, METER_MAX_FRAMES)) return why;
     if (C < (1 << 24) || C > (1 << 28)) return "ceiling_q28 out of range [2^24, 2^28]";
     if (W < 1 || W > CEIL_MAX_W) return "ceiling window out of range [1, 1024]";
-    if (frames < 0 || frames >= ((int64_t)1 << 31) - METER_SPAN) return "frames out of range";
     return nullptr;
-}
-
-// The chain's window: round-half-even(rate / 200) = 5 ms, within [1, 1024]
-// (design.ceiling_window).
-int ceiling_window(int rate) {
-    int q = rate / 200;
-    const int rem = rate % 200;
-    if (rem > 100 || (rem == 100 && (q & 1))) ++q;
-    return std::min(CEIL_MAX_W, std::max(1, q));
 }
 
 }  // namespace
@@ -328,7 +274,7 @@ int ceiling_window(int rate) {
 static int ceiling_device(mm_ctx *c, void *d_pcm, int kind, int64_t frames, int channels, int32_t C, int32_t W,
                           mm_ceiling *out) {
     if (!c || !out || (frames > 0 && !d_pcm)) return set_err(c, MM_ERR_ARG, "bad arguments");
-    if (kind != MM_OUT_I16 && kind != MM_OUT_F32) return set_err(c, MM_ERR_ARG, "kind %d (MM_OUT_I16 | MM_OUT_F32)", kind);
+    if (!pcm_kind_ok(kind)) return set_err(c, MM_ERR_ARG, PCM_BAD_KIND, kind);
     if (const char *why = ceiling_bad_args(frames, channels, C, W)) return set_err(c, MM_ERR_ARG, "%s", why);
     ceiling_clear(out, frames, channels, C, W);
     if (frames == 0) return MM_OK;
@@ -344,29 +290,13 @@ static int ceiling_device(mm_ctx *c, void *d_pcm, int kind, int64_t frames, int 
     const dim3 gn((unsigned)spans), bn(METER_THREADS);
     const dim3 ga((unsigned)((frames + CEIL_SPAN - 1) / CEIL_SPAN)), ba(CEIL_THREADS);
     const unsigned rcp = (unsigned)(((uint64_t)1 << 32) / (uint64_t)(2 * W + 1));
-    if (kind == MM_OUT_I16) {
-        int16_t *p = static_cast<int16_t *>(d_pcm);
-        if (channels == 2) {
-            RET(launch(c, "ceil_need", ceil_need_kernel<2, int16_t>, gn, bn, 0, (const int16_t *)p, frames, Ct, plane, st));
-            RET(launch(c, "ceil_apply", ceil_apply_kernel<2, int16_t>, ga, ba, 0, p, frames, plane_len,
-                       (const uint16_t *)plane, (int)C, (int)W, rcp, st));
-        } else {
-            RET(launch(c, "ceil_need", ceil_need_kernel<1, int16_t>, gn, bn, 0, (const int16_t *)p, frames, Ct, plane, st));
-            RET(launch(c, "ceil_apply", ceil_apply_kernel<1, int16_t>, ga, ba, 0, p, frames, plane_len,
-                       (const uint16_t *)plane, (int)C, (int)W, rcp, st));
-        }
-    } else {
-        float *p = static_cast<float *>(d_pcm);
-        if (channels == 2) {
-            RET(launch(c, "ceil_need", ceil_need_kernel<2, float>, gn, bn, 0, (const float *)p, frames, Ct, plane, st));
-            RET(launch(c, "ceil_apply", ceil_apply_kernel<2, float>, ga, ba, 0, p, frames, plane_len,
-                       (const uint16_t *)plane, (int)C, (int)W, rcp, st));
-        } else {
-            RET(launch(c, "ceil_need", ceil_need_kernel<1, float>, gn, bn, 0, (const float *)p, frames, Ct, plane, st));
-            RET(launch(c, "ceil_apply", ceil_apply_kernel<1, float>, ga, ba, 0, p, frames, plane_len,
-                       (const uint16_t *)plane, (int)C, (int)W, rcp, st));
-        }
-    }
+    RET(dispatch_pcm(kind, channels, [&](auto ch, auto t) {
+        using T = decltype(t);
+        T *p = static_cast<T *>(d_pcm);
+        RET(launch(c, "ceil_need", ceil_need_kernel<ch, T>, gn, bn, 0, (const T *)p, frames, Ct, plane, st));
+        return launch(c, "ceil_apply", ceil_apply_kernel<ch, T>, ga, ba, 0, p, frames, plane_len, (const uint16_t *)plane,
+                      (int)C, (int)W, rcp, st);
+    }));
     RET(meter_launch(c, d_pcm, kind, frames, channels, res));
     CeilDev hs;
     MeterDev hm;
@@ -385,12 +315,10 @@ static int ceiling_device(mm_ctx *c, void *d_pcm, int kind, int64_t frames, int 
     if (out->tp_limited_q28 > C) {  // the residue: one static trim, provably under C
         const int gt = (int)(((int64_t)Ct << 16) / out->tp_limited_q28);
         const int64_t n = frames * channels;
-        if (kind == MM_OUT_I16)
-            RET(launch(c, "ceil_trim", ceil_trim_kernel<int16_t>, dim3(pw_blocks(n)), dim3(256), 0,
-                       static_cast<int16_t *>(d_pcm), n, gt));
-        else
-            RET(launch(c, "ceil_trim", ceil_trim_kernel<float>, dim3(pw_blocks(n)), dim3(256), 0,
-                       static_cast<float *>(d_pcm), n, gt));
+        RET(dispatch_pcm(kind, 1, [&](auto, auto t) {  // (pointwise: the samples as one mono line)
+            using T = decltype(t);
+            return launch(c, "ceil_trim", ceil_trim_kernel<T>, dim3(pw_blocks(n)), dim3(256), 0, static_cast<T *>(d_pcm), n, gt);
+        }));
         RET(meter_launch(c, d_pcm, kind, frames, channels, res));
         HIPCHK(c, hipMemcpyAsync(&hm, res, sizeof hm, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -401,16 +329,16 @@ static int ceiling_device(mm_ctx *c, void *d_pcm, int kind, int64_t frames, int 
     return MM_OK;
 }
 
-// The chain's hook: the ceiling of track `slot` of `n` of the current master call.
-static int chain_ceiling(mm_ctx *c, const mm_job *j, void *d_out, int slot, int n) {
-    if (slot == 0) c->ceilings.assign((size_t)n, mm_ceiling{});
-    mm_ceiling *m = &c->ceilings[(size_t)slot];
-    if (!j->ceiling_q28) {
-        memset(m, 0, sizeof *m);
-        m->channels = j->channels;
-        return MM_OK;
-    }
-    return ceiling_device(c, d_out, j->out_kind, j->frames_proc, j->channels, j->ceiling_q28, ceiling_window(j->rate), m);
+// The end of a master call for delivered buffer i (results_reset sized the call's results):
+// the ceiling, then the report, which so measures what is delivered.  A track that did not
+// ask for what another track of the call asked for leaves a cleared entry.
+static int finish_delivered(mm_ctx *c, void *d_out, int kind, int64_t frames, int channels, int i, int32_t ceiling_q28,
+                            int32_t window, int meter_on, const mm_job *loud) {
+    if (ceiling_q28) RET(ceiling_device(c, d_out, kind, frames, channels, ceiling_q28, window, &c->ceilings[(size_t)i]));
+    else if (!c->ceilings.empty()) c->ceilings[(size_t)i].channels = channels;
+    if (meter_on) RET(meter_device(c, d_out, kind, frames, channels, loud, &c->meters[(size_t)i]));
+    else if (!c->meters.empty()) meter_clear(&c->meters[(size_t)i], 0, channels);
+    return MM_OK;
 }
 
 extern "C" {
@@ -429,20 +357,15 @@ int mm_ceiling_device(mm_ctx *c, void *d_pcm, int kind, int64_t frames, int chan
 int mm_ceiling_pcm(mm_ctx *c, void *pcm, int kind, int64_t frames, int channels, int32_t ceiling_q28, int32_t window,
                    mm_ceiling *out) {
     if (!c) return MM_ERR_ARG;
-    if (!out || (frames > 0 && !pcm) || (kind != MM_OUT_I16 && kind != MM_OUT_F32))
-        return set_err(c, MM_ERR_ARG, "bad arguments");
+    if (!out || (frames > 0 && !pcm) || !pcm_kind_ok(kind)) return set_err(c, MM_ERR_ARG, "bad arguments");
     if (const char *why = ceiling_bad_args(frames, channels, ceiling_q28, window)) return set_err(c, MM_ERR_ARG, "%s", why);
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t bytes = (size_t)frames * channels * (kind == MM_OUT_I16 ? 2 : 4);
+    const size_t bytes = pcm_bytes(kind, frames, channels);
     char *dio;
-    RET(get_buf(c, "ceil_io", std::max<size_t>(bytes, 1), &dio));
-    if (bytes) HIPCHK(c, hipMemcpyAsync(dio, pcm, bytes, hipMemcpyHostToDevice, c->stream));
+    RET(pcm_upload(c, "ceil_io", pcm, bytes, &dio));
     RET(ceiling_device(c, dio, kind, frames, channels, ceiling_q28, window, out));
-    if (bytes && out->tp_in_q28 > ceiling_q28) {  // (an untouched signal is not copied back)
-        HIPCHK(c, hipMemcpyAsync(pcm, dio, bytes, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    return MM_OK;
+    if (out->tp_in_q28 <= ceiling_q28) return MM_OK;  // (an untouched signal is not copied back)
+    return pcm_download(c, pcm, dio, bytes);
 }
 
 int mm_last_ceilings(mm_ctx *c, int cap, mm_ceiling *out) {
@@ -457,7 +380,6 @@ int mm_last_ceilings(mm_ctx *c, int cap, mm_ceiling *out) {
 // interleaved int16: what the three kernels must reproduce, samples and statistics.
 int mm_ceiling_host(int16_t *pcm, int64_t frames, int channels, int32_t C, int32_t W, mm_ceiling *out) {
     if (!out || (frames > 0 && !pcm) || ceiling_bad_args(frames, channels, C, W)) return MM_ERR_ARG;
-    constexpr TpTaps t = tp_taps();
     ceiling_clear(out, frames, channels, C, W);
     if (frames == 0) return MM_OK;
     const int64_t N = frames, M = N + 11;
@@ -467,15 +389,7 @@ int mm_ceiling_host(int16_t *pcm, int64_t frames, int channels, int32_t C, int32
         int32_t tp = 0;
         for (int64_t m = 0; m < M; ++m) {
             int32_t pm = 0;
-            for (int c = 0; c < channels; ++c)
-                for (int p = 0; p < 4; ++p) {
-                    int32_t acc = 0;
-                    for (int k = 0; k < 12; ++k) {
-                        const int64_t f = m - k;
-                        if (f >= 0 && f < N) acc += t.c[p][k] * (int32_t)pcm[f * channels + c];
-                    }
-                    pm = std::max(pm, acc < 0 ? -acc : acc);
-                }
+            for (int c = 0; c < channels; ++c) pm = std::max(pm, tp_host(pcm, N, channels, c, m));
             P[(size_t)m] = pm;
             tp = std::max(tp, pm);
         }

@@ -2,7 +2,8 @@
 // unit: the launch sequence of the chain (a unit of n >= 1 tracks between two
 // syncs), loudness gating, the batch scheduler and the staged / time-sharded entry
 // points.  The context is context.h, followed by decode.hip (24/32-bit PCM input);
-// wav.hip, comm.hip, ops.hip, meter.hip and ceiling.hip are included at the end.
+// wav.hip, comm.hip, ops.hip, then pcm16.h, meter.hip, ceiling.hip and resample.hip (with
+// mm_master* / mm_deliver*: a master call with or without a delivery) come at the end.
 #include <rccl/rccl.h>
 
 #include <algorithm>
@@ -25,10 +26,9 @@ using namespace mm;
 #include "context.h"
 #include "decode.hip"
 
-// meter.hip: meter track `slot` of `n` of the current master call into c->meters
-static int chain_meter(mm_ctx *c, const mm_job *j, const void *d_out, int slot, int n);
-// ceiling.hip: hold track `slot` of `n` under its job's true-peak ceiling, into c->ceilings
-static int chain_ceiling(mm_ctx *c, const mm_job *j, void *d_out, int slot, int n);
+// ceiling.hip: the end of a master call for delivered buffer i, the ceiling and then the report
+static int finish_delivered(mm_ctx *c, void *d_out, int kind, int64_t frames, int channels, int i, int32_t ceiling_q28,
+                            int32_t window, int meter_on, const mm_job *loud);
 
 // ------------------------------------------------------- look-back plumbing
 // Transition tables of one filter stage (uploaded only when they change).
@@ -1445,18 +1445,35 @@ static int unit_complete(mm_ctx *c, const Unit &u, mm_result *res) {
     return MM_OK;
 }
 
-static int master_device(mm_ctx *c, const mm_job *j, const void *d_in, void *d_out, mm_result *res) {
-    c->meters.clear();
-    c->ceilings.clear();
+// The per-call results of a master call (mm_last_meters, mm_last_ceilings, mm_last_resample):
+// none at its start; before its end one entry for each of the n delivered buffers of what
+// any of them asked for.
+static void results_reset(mm_ctx *c, int n = 0, bool ceiling = false, bool meter = false) {
+    c->meters.assign(meter ? (size_t)n : 0, mm_meter{});
+    c->ceilings.assign(ceiling ? (size_t)n : 0, mm_ceiling{});
     c->resample_valid = false;
+}
+
+// The chain's ceiling window: round-half-even(rate / 200) = 5 ms, within [1, 1024]
+// (design.ceiling_window).
+static int ceiling_window(int rate) {
+    int q = rate / 200;
+    const int rem = rate % 200;
+    if (rem > 100 || (rem == 100 && (q & 1))) ++q;
+    return std::min(mm_ceiling_max_window(), std::max(1, q));
+}
+
+static int master_device(mm_ctx *c, const mm_job *j, const void *d_in, void *d_out, mm_result *res) {
+    results_reset(c);
     Unit u;
     u.J = j;
     u.in = &d_in;
     u.out = &d_out;
     RET(unit_enqueue(c, u));
     RET(unit_complete(c, u, res));
-    if (j->ceiling_q28) RET(chain_ceiling(c, j, d_out, 0, 1));  // before the report: it measures what is delivered
-    return j->meter_on ? chain_meter(c, j, d_out, 0, 1) : MM_OK;
+    results_reset(c, 1, j->ceiling_q28, j->meter_on);
+    return finish_delivered(c, d_out, j->out_kind, j->frames_proc, j->channels, 0, j->ceiling_q28, ceiling_window(j->rate),
+                            j->meter_on, j);
 }
 
 // The units of a batch: one track, or consecutive same-settings tracks fused into one
@@ -1598,9 +1615,7 @@ int mm_master_batch(mm_ctx *c, int n, const mm_job *jobs, const void *const *d_i
     if (!c || n < 0 || (n > 0 && (!jobs || !d_in || !d_out))) return set_err(c, MM_ERR_ARG, "bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
     for (int i = 0; i < n; ++i) RET(validate(c, &jobs[i]));
-    c->meters.clear();
-    c->ceilings.clear();
-    c->resample_valid = false;
+    results_reset(c);
     std::vector<Unit> units = batch_units(jobs, d_in, d_out, n);
     const int nu = (int)units.size();
     const int S = std::min(nu, MM_BATCH_STREAMS);
@@ -1656,28 +1671,12 @@ int mm_master_batch(mm_ctx *c, int n, const mm_job *jobs, const void *const *d_i
     bool meter = false, ceiling = false;
     for (int i = 0; i < n; ++i) meter = meter || jobs[i].meter_on;
     for (int i = 0; i < n; ++i) ceiling = ceiling || jobs[i].ceiling_q28;
-    for (int i = 0; i < n && ceiling; ++i) RET(chain_ceiling(c, &jobs[i], d_out[i], i, n));
-    for (int i = 0; i < n && meter; ++i) RET(chain_meter(c, &jobs[i], d_out[i], i, n));
-    return MM_OK;
-}
-
-int mm_master(mm_ctx *c, const mm_job *j, const void *in, void *out, mm_result *res) {
-    if (!c) return MM_ERR_ARG;
-    RET(validate(c, j));
-    HIPCHK(c, hipSetDevice(c->device));
-    char *d_in;
-    void *d_out;
-    const size_t in_bytes = (size_t)j->frames_in * j->channels * in_sample_bytes(j->in_kind);
-    const size_t out_bytes = (size_t)j->frames_proc * j->channels * (j->out_kind == MM_OUT_I16 ? 2 : 4);
-    RET(get_buf(c, "host_in", std::max<size_t>(in_bytes, 1), &d_in));
-    char *ob;
-    RET(get_buf(c, "host_out", std::max<size_t>(out_bytes, 1), &ob));
-    d_out = ob;
-    if (in_bytes) HIPCHK(c, hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, c->stream));
-    RET(master_device(c, j, d_in, d_out, res));
-    if (out_bytes) HIPCHK(c, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    resolve_events(c);
+    results_reset(c, n, ceiling, meter);
+    for (int i = 0; i < n; ++i) {
+        const mm_job &j = jobs[i];
+        RET(finish_delivered(c, d_out[i], j.out_kind, j.frames_proc, j.channels, i, j.ceiling_q28, ceiling_window(j.rate),
+                             j.meter_on, &j));
+    }
     return MM_OK;
 }
 
@@ -1853,6 +1852,7 @@ int mm_kernel_stats(mm_ctx *c, char *names, int names_cap, double *total_ms, int
 #include "wav.hip"
 #include "comm.hip"
 #include "ops.hip"
+#include "pcm16.h"
 #include "meter.hip"
 #include "ceiling.hip"
 #include "resample.hip"

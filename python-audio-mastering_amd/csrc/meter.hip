@@ -9,8 +9,11 @@
 // All results are integers combined with max / add: nothing depends on the launch
 // geometry or on the order in which workgroups finish.
 //
-// Included at the end of mastering.hip (one translation unit), after ops.hip: the
-// host entry points use its context helpers and loudness_device.
+// This file owns the taps and the oversampler, on the device (tp_stage, tp_window, tp_frame)
+// and on the host (tp_host): ceil_need and mm_ceiling_host in ceiling.hip run the same.
+//
+// Included at the end of mastering.hip (one translation unit), after ops.hip (the
+// host entry points use its context helpers and loudness_device) and pcm16.h.
 
 namespace mm {
 
@@ -20,6 +23,7 @@ constexpr int METER_SPAN = METER_THREADS * METER_FPT;   // frames of m per workg
 constexpr int METER_WGS_PER_CU = 4;                     // resident workgroups a launch is capped at, per CU
 constexpr int METER_HALO = 12;                          // 11 frames of history + 1 so that windows start on a dword
 constexpr int METER_LINE = (METER_SPAN + METER_HALO + 7) / 8 * 8;  // int16 per channel line in LDS (16-byte multiple)
+constexpr int64_t METER_MAX_FRAMES = ((int64_t)1 << 31) - METER_SPAN;  // frames of a signal on the grid stay below this
 
 // H * 8192 of BS.1770-4 Annex 2, phases 0 and 1 (2 and 3 are their reversals)
 #define MM_TP_C0 14, 90, -161, 272, -487, 1125, 7964, -838, 390, -218, 122, -68
@@ -53,32 +57,39 @@ struct MeterDev {
     int _pad[2];
 };
 
-template <typename T>
-__device__ __forceinline__ int meter_sample(T v) {
-    if constexpr (sizeof(T) == 2) {
-        return (int)v;
-    } else {  // an MM_OUT_F32 buffer holds int16 / 32768 exactly
-        int k = (int)rintf(v * 32768.0f);
-        return min(32767, max(-32768, k));
+// The CH lines of the span at `base` and their halo, de-interleaved (zeros outside [0, N)).
+template <int CH, typename T>
+__device__ __forceinline__ void tp_stage(int16_t (&line)[CH][METER_LINE], const T *__restrict__ in, int64_t N, int64_t base) {
+    const int64_t f0 = base - METER_HALO;  // frame of LDS index 0
+    for (int i = threadIdx.x; i < METER_LINE; i += METER_THREADS) {
+        const int64_t f = f0 + i;
+        int s[CH] = {};
+        if (f >= 0 && f < N) load_frame<CH, T>(in, f, s);
+#pragma unroll
+        for (int c = 0; c < CH; ++c) line[c][i] = (int16_t)s[c];
     }
+    __syncthreads();
 }
 
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long w = __shfl_xor(v, o);
-        v = w > v ? w : v;
-    }
-    return v;
+// The window of the METER_FPT frames m0 .. at line position pos = m0 - base (a multiple of
+// 8): w[i] = s[m0 - 12 + i], i < 20, read as ten dwords D[i] = (w[2i], w[2i+1]) and kept in
+// both packings, P[i] = (w[i], w[i+1]).
+__device__ __forceinline__ void tp_window(const int16_t *pos, uint32_t (&P)[19]) {
+    const uint4 *src = reinterpret_cast<const uint4 *>(pos);
+    const uint4 a = src[0], b = src[1];
+    const uint2 e = *reinterpret_cast<const uint2 *>(src + 2);
+    const uint32_t D[10] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, e.x, e.y};
+#pragma unroll
+    for (int i = 0; i < 19; ++i) P[i] = (i & 1) ? ((D[i / 2] >> 16) | (D[i / 2 + 1] << 16)) : D[i / 2];
 }
 
-__device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-__device__ __forceinline__ int wave_max_i32(int v) {
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
-    return v;
+// |Y[m0 + j][p]| of a window: 6 packed dot products (the callers unroll over p < 4 and
+// combine the four in their own way)
+__device__ __forceinline__ int tp_frame(const uint32_t (&P)[19], int j, int p) {
+    int acc = 0;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) acc = tp_dot2(P[j + 11 - 2 * q], tp_pair(p, q), acc);
+    return acc < 0 ? -acc : acc;  // |Y| <= 542994228: the negation cannot overflow
 }
 
 // A workgroup takes spans blockIdx.x, blockIdx.x + gridDim.x, ... in turn; one span
@@ -112,52 +123,18 @@ __global__ void __launch_bounds__(METER_THREADS) meter_i16_kernel(const T *__res
     }
     for (int64_t span = blockIdx.x; span < spans; span += gridDim.x) {
         const int64_t base = span * METER_SPAN;
-        const int64_t f0 = base - METER_HALO;  // frame of LDS index 0
-        for (int i = threadIdx.x; i < METER_LINE; i += METER_THREADS) {
-            const int64_t f = f0 + i;
-            const bool ok = f >= 0 && f < N;
-            if constexpr (CH == 2) {
-                int l = 0, r = 0;
-                if (ok) {
-                    if constexpr (sizeof(T) == 2) {
-                        const uint32_t d = reinterpret_cast<const uint32_t *>(in)[f];
-                        l = (int16_t)(d & 0xFFFFu);
-                        r = (int16_t)(d >> 16);
-                    } else {
-                        const float2 d = reinterpret_cast<const float2 *>(in)[f];
-                        l = meter_sample<float>(d.x);
-                        r = meter_sample<float>(d.y);
-                    }
-                }
-                line[0][i] = (int16_t)l;
-                line[1][i] = (int16_t)r;
-            } else {
-                line[0][i] = ok ? (int16_t)meter_sample<T>(in[f]) : (int16_t)0;
-            }
-        }
-        __syncthreads();
+        tp_stage<CH, T>(line, in, N, base);
         const int64_t m0 = base + (int64_t)threadIdx.x * METER_FPT;
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
-            // window w[i] = s[m0 - 12 + i], i < 20, as dwords D[i] = (w[2i], w[2i+1])
-            const uint4 *src = reinterpret_cast<const uint4 *>(&line[c][threadIdx.x * METER_FPT]);
-            const uint4 a = src[0], b = src[1];
-            const uint2 e = *reinterpret_cast<const uint2 *>(src + 2);
-            const uint32_t D[10] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, e.x, e.y};
-            uint32_t P[19];  // P[i] = (w[i], w[i+1])
-#pragma unroll
-            for (int i = 0; i < 19; ++i) P[i] = (i & 1) ? ((D[i / 2] >> 16) | (D[i / 2 + 1] << 16)) : D[i / 2];
+            uint32_t P[19];
+            tp_window(&line[c][threadIdx.x * METER_FPT], P);
             unsigned cnt = 0;  // overs << 16 | clipped of this span
 #pragma unroll
             for (int j = 0; j < METER_FPT; ++j) {
                 int y[4];
 #pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    int acc = 0;
-#pragma unroll
-                    for (int q = 0; q < 6; ++q) acc = tp_dot2(P[j + 11 - 2 * q], tp_pair(p, q), acc);
-                    y[p] = acc < 0 ? -acc : acc;  // |Y| <= 542994228: the negation cannot overflow
-                }
+                for (int p = 0; p < 4; ++p) y[p] = tp_frame(P, j, p);
                 const int pm = max(max(y[0], y[1]), max(y[2], y[3]));
                 if (pm > best[c]) {  // strict: the smallest m of a tie stays
                     best[c] = pm;
@@ -277,24 +254,20 @@ static int meter_launch(mm_ctx *c, const void *d_pcm, int kind, int64_t frames, 
     HIPCHK(c, hipMemsetAsync(res, 0, sizeof(MeterDev), c->stream));
     const int64_t spans = (frames + 11 + METER_SPAN - 1) / METER_SPAN;
     const dim3 grid((unsigned)std::min<int64_t>(spans, (int64_t)METER_WGS_PER_CU * c->n_cus)), block(METER_THREADS);
-    if (kind == MM_OUT_I16) {
-        const int16_t *p = static_cast<const int16_t *>(d_pcm);
-        if (channels == 2) return launch(c, "meter_i16", meter_i16_kernel<2, int16_t>, grid, block, 0, p, frames, spans, res);
-        return launch(c, "meter_i16", meter_i16_kernel<1, int16_t>, grid, block, 0, p, frames, spans, res);
-    }
-    const float *p = static_cast<const float *>(d_pcm);
-    if (channels == 2) return launch(c, "meter_i16", meter_i16_kernel<2, float>, grid, block, 0, p, frames, spans, res);
-    return launch(c, "meter_i16", meter_i16_kernel<1, float>, grid, block, 0, p, frames, spans, res);
+    return dispatch_pcm(kind, channels, [&](auto ch, auto t) {
+        using T = decltype(t);
+        return launch(c, "meter_i16", meter_i16_kernel<ch, T>, grid, block, 0, static_cast<const T *>(d_pcm), frames, spans, res);
+    });
 }
 
 // Meter a device-resident signal on the context's stream (synchronous on return).
 static int meter_device(mm_ctx *c, const void *d_pcm, int kind, int64_t frames, int channels, const mm_job *loud,
                         mm_meter *out) {
     if (!c || !out || (frames > 0 && !d_pcm)) return set_err(c, MM_ERR_ARG, "bad arguments");
-    if (kind != MM_OUT_I16 && kind != MM_OUT_F32) return set_err(c, MM_ERR_ARG, "kind %d (MM_OUT_I16 | MM_OUT_F32)", kind);
-    if (channels != 1 && channels != 2) return set_err(c, MM_ERR_ARG, "channels must be 1 or 2");
-    if (frames < 0 || frames >= ((int64_t)1 << 31) - METER_SPAN)
-        return set_err(c, MM_ERR_ARG, "frames %lld out of range", (long long)frames);
+    if (!pcm_kind_ok(kind)) return set_err(c, MM_ERR_ARG, PCM_BAD_KIND, kind);
+    static const char RANGE[] = "frames %lld out of range";  // (this stage's words print the count)
+    if (const char *why = pcm_refusal(channels, frames, METER_MAX_FRAMES, RANGE))
+        return why == RANGE ? set_err(c, MM_ERR_ARG, RANGE, (long long)frames) : set_err(c, MM_ERR_ARG, "%s", why);
     meter_clear(out, frames, channels);
     if (frames == 0) return MM_OK;
     if (loud && meter_has_geometry(loud, frames) && (loud->frames_proc != frames || loud->channels != channels))
@@ -333,15 +306,20 @@ static int meter_device(mm_ctx *c, const void *d_pcm, int kind, int64_t frames, 
     return MM_OK;
 }
 
-// The chain's hook: meter track `slot` of `n` of the current master call.
-static int chain_meter(mm_ctx *c, const mm_job *j, const void *d_out, int slot, int n) {
-    if (slot == 0) c->meters.assign((size_t)n, mm_meter{});
-    mm_meter *m = &c->meters[(size_t)slot];
-    if (!j->meter_on) {
-        meter_clear(m, 0, j->channels);
-        return MM_OK;
+// max_p |Y_c[m][p]| in plain C++ on the host: the 12-tap loop of the definition, the one
+// formulation behind mm_true_peak_host and mm_ceiling_host.
+static int32_t tp_host(const int16_t *pcm, int64_t frames, int channels, int c, int64_t m) {
+    constexpr TpTaps t = tp_taps();
+    int32_t pm = 0;
+    for (int p = 0; p < 4; ++p) {
+        int32_t acc = 0;
+        for (int k = 0; k < 12; ++k) {
+            const int64_t f = m - k;
+            if (f >= 0 && f < frames) acc += t.c[p][k] * (int32_t)pcm[f * channels + c];
+        }
+        pm = std::max(pm, acc < 0 ? -acc : acc);
     }
-    return meter_device(c, d_out, j->out_kind, j->frames_proc, j->channels, j, m);
+    return pm;
 }
 
 extern "C" {
@@ -358,14 +336,11 @@ int mm_meter_device(mm_ctx *c, const void *d_pcm, int kind, int64_t frames, int 
 int mm_meter_pcm(mm_ctx *c, const void *pcm, int kind, int64_t frames, int channels, const mm_job *loud,
                  mm_meter *out) {
     if (!c) return MM_ERR_ARG;
-    if (frames < 0 || (frames > 0 && !pcm) || (channels != 1 && channels != 2) ||
-        (kind != MM_OUT_I16 && kind != MM_OUT_F32))
+    if (frames < 0 || (frames > 0 && !pcm) || (channels != 1 && channels != 2) || !pcm_kind_ok(kind))
         return set_err(c, MM_ERR_ARG, "bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t bytes = (size_t)frames * channels * (kind == MM_OUT_I16 ? 2 : 4);
     char *din;
-    RET(get_buf(c, "meter_in", std::max<size_t>(bytes, 1), &din));
-    if (bytes) HIPCHK(c, hipMemcpyAsync(din, pcm, bytes, hipMemcpyHostToDevice, c->stream));
+    RET(pcm_upload(c, "meter_in", pcm, pcm_bytes(kind, frames, channels), &din));
     return meter_device(c, din, kind, frames, channels, loud, out);
 }
 
@@ -412,21 +387,12 @@ int mm_op_true_peak(mm_ctx *c, int dtype, const void *in, int64_t frames, int ch
 // what the meter_i16 kernel must reproduce field for field.  loudness stays NaN.
 int mm_true_peak_host(const int16_t *pcm, int64_t frames, int channels, mm_meter *out) {
     if (!out || frames < 0 || (frames > 0 && !pcm) || (channels != 1 && channels != 2)) return MM_ERR_ARG;
-    constexpr TpTaps t = tp_taps();
     meter_clear(out, frames, channels);
     for (int c = 0; c < channels && frames > 0; ++c) {
         int32_t best = -1;
         int64_t best_m = 0;
         for (int64_t m = 0; m < frames + 11; ++m) {
-            int32_t pm = 0;
-            for (int p = 0; p < 4; ++p) {
-                int32_t acc = 0;
-                for (int k = 0; k < 12; ++k) {
-                    const int64_t f = m - k;
-                    if (f >= 0 && f < frames) acc += t.c[p][k] * (int32_t)pcm[f * channels + c];
-                }
-                pm = std::max(pm, acc < 0 ? -acc : acc);
-            }
+            const int32_t pm = tp_host(pcm, frames, channels, c, m);
             if (pm > best) {
                 best = pm;
                 best_m = m;

@@ -24,8 +24,10 @@
 // the taps is kept transposed and in output order, D[k][n mod L] = c[(n mod L) * M % L][k],
 // so the lanes of a wave (consecutive n) read consecutive words of one row of D.
 //
-// Included at the end of mastering.hip after ceiling.hip (the meter's sample decoding and
-// wave reductions, ceiling_device, meter_device, the WAV helpers and master_device).
+// Included last in mastering.hip, after pcm16.h (its frames and wave reductions are shared
+// with the meter and the ceiling, not their line layout), meter.hip, ceiling.hip and the
+// WAV helpers.  mm_master / mm_deliver and mm_master_wav / mm_deliver_wav are here, one
+// implementation each with the delivery optional.
 
 namespace mm {
 
@@ -52,12 +54,6 @@ struct RsArgs {
     const int32_t *D;   // [K][L], output order
     RsDev *st;
 };
-
-template <typename T>
-__device__ __forceinline__ T rs_deliver(int y) {
-    if constexpr (sizeof(T) == 2) return (T)y;
-    else return (float)y * (1.0f / 32768.0f);
-}
 
 // The workgroup's span is cut into pieces of a.sub outputs (one piece for every rate pair
 // with M / L <= 8: a.sub == RS_SPAN); a piece starting at output m0 reads the input frames
@@ -98,18 +94,11 @@ __global__ void __launch_bounds__(RS_THREADS) resample_kernel(const T *__restric
             const int64_t f = lo + i;
             const bool ok = f >= 0 && f < a.N;
             if constexpr (CH == 2) {
-                uint32_t d = 0;
-                if (ok) {
-                    if constexpr (sizeof(T) == 2) {
-                        d = reinterpret_cast<const uint32_t *>(in)[f];
-                    } else {
-                        const float2 v = reinterpret_cast<const float2 *>(in)[f];
-                        d = ((uint32_t)meter_sample<float>(v.x) & 0xFFFFu) | ((uint32_t)meter_sample<float>(v.y) << 16);
-                    }
-                }
-                lds[i] = d;
+                lds[i] = ok ? load_frame_packed<T>(in, f) : 0u;
             } else {
-                line[i] = ok ? (int16_t)meter_sample<T>(in[f]) : (int16_t)0;
+                int s[1] = {};
+                if (ok) load_frame<1, T>(in, f, s);
+                line[i] = (int16_t)s[0];
             }
         }
         __syncthreads();
@@ -169,14 +158,7 @@ __global__ void __launch_bounds__(RS_THREADS) resample_kernel(const T *__restric
                     pk[c] = max(pk[c], yc < 0 ? -yc : yc);
                     y[c] = yc;
                 }
-                const int64_t n = m0 + o[jj];
-                if constexpr (CH == 2 && sizeof(T) == 2) {
-                    reinterpret_cast<uint32_t *>(out)[n] = ((uint32_t)y[0] & 0xFFFFu) | ((uint32_t)y[1] << 16);
-                } else if constexpr (CH == 2) {
-                    reinterpret_cast<float2 *>(out)[n] = make_float2(rs_deliver<float>(y[0]), rs_deliver<float>(y[1]));
-                } else {
-                    out[n] = rs_deliver<T>(y[0]);
-                }
+                store_frame<CH, T>(out, m0 + o[jj], y);
             }
         }
     }
@@ -243,12 +225,10 @@ const char *resample_bad_table(const mm_resampler *rs) {
     return nullptr;
 }
 
-// why (frames, channels) cannot be converted by this geometry, or null
+// why (frames, channels) cannot be converted by this (checked) geometry, or null
 const char *resample_bad_signal(int64_t frames, int channels, int L, int M) {
-    if (channels != 1 && channels != 2) return "channels must be 1 or 2";
-    if (frames < 0 || frames >= (int64_t)1 << 31) return "frames out of range";
-    if (rs_frames(frames, L, M) >= ((int64_t)1 << 31) - METER_SPAN) return "output frames out of range";
-    return nullptr;
+    if (const char *why = pcm_refusal(channels, frames, (int64_t)1 << 31)) return why;
+    return rs_frames(frames, L, M) >= METER_MAX_FRAMES ? "output frames out of range" : nullptr;
 }
 
 void resample_clear(mm_resample *o, int64_t frames, int channels, const mm_resampler *rs) {
@@ -297,7 +277,7 @@ static int resample_taps_device(mm_ctx *c, const mm_resampler *rs, const int32_t
 static int resample_device(mm_ctx *c, const void *d_in, int kind, int64_t frames, int channels, const mm_resampler *rs,
                            void *d_out, mm_resample *out) {
     if (!c || !out || !rs || (frames > 0 && (!d_in || !d_out))) return set_err(c, MM_ERR_ARG, "bad arguments");
-    if (kind != MM_OUT_I16 && kind != MM_OUT_F32) return set_err(c, MM_ERR_ARG, "kind %d (MM_OUT_I16 | MM_OUT_F32)", kind);
+    if (!pcm_kind_ok(kind)) return set_err(c, MM_ERR_ARG, PCM_BAD_KIND, kind);
     if (const char *why = resample_bad_geometry(rs->L, rs->M, rs->K)) return set_err(c, MM_ERR_ARG, "resampler: %s", why);
     if (const char *why = resample_bad_signal(frames, channels, rs->L, rs->M)) return set_err(c, MM_ERR_ARG, "%s", why);
     RsArgs a{};
@@ -314,17 +294,10 @@ static int resample_device(mm_ctx *c, const void *d_in, int kind, int64_t frames
     // a piece of `sub` outputs reads ((sub - 1) * M + p0) / L + K <= (sub - 1) * M / L + 1 + K frames
     a.sub = (int)std::min<int64_t>(RS_SPAN, 1 + (int64_t)(RS_LINE - rs->K - 1) * rs->L / rs->M);
     const dim3 grid((unsigned)((a.Nout + RS_SPAN - 1) / RS_SPAN)), block(RS_THREADS);
-    if (kind == MM_OUT_I16) {
-        const int16_t *p = static_cast<const int16_t *>(d_in);
-        int16_t *q = static_cast<int16_t *>(d_out);
-        if (channels == 2) RET(launch(c, "resample", resample_kernel<2, int16_t>, grid, block, 0, p, q, a));
-        else RET(launch(c, "resample", resample_kernel<1, int16_t>, grid, block, 0, p, q, a));
-    } else {
-        const float *p = static_cast<const float *>(d_in);
-        float *q = static_cast<float *>(d_out);
-        if (channels == 2) RET(launch(c, "resample", resample_kernel<2, float>, grid, block, 0, p, q, a));
-        else RET(launch(c, "resample", resample_kernel<1, float>, grid, block, 0, p, q, a));
-    }
+    RET(dispatch_pcm(kind, channels, [&](auto ch, auto t) {
+        using T = decltype(t);
+        return launch(c, "resample", resample_kernel<ch, T>, grid, block, 0, static_cast<const T *>(d_in), static_cast<T *>(d_out), a);
+    }));
     RsDev h;
     HIPCHK(c, hipMemcpyAsync(&h, a.st, sizeof h, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -349,28 +322,67 @@ static const char *deliver_bad_args(const mm_job *j, const mm_delivery *dl) {
     return nullptr;
 }
 
-// The delivery path: the chain into a context buffer, the converter into d_out, then the
-// ceiling and the report on what is delivered (slot 0 of mm_last_ceilings / mm_last_meters).
+// what mm_deliver* take a null delivery for: it is refused as one without a resampler
+static const mm_delivery NO_DELIVERY{};
+
+// frames a master call delivers (dl null: no delivery at another rate; else checked)
+static int64_t delivered_frames(const mm_job *j, const mm_delivery *dl) {
+    return dl ? rs_frames(j->frames_proc, dl->rs->L, dl->rs->M) : j->frames_proc;
+}
+
+// A master call on device-resident buffers.  Without a delivery (dl null) the plain chain:
+// master_device.  With one, the chain into a context buffer, the converter into d_out, then
+// the ceiling and the report on what is delivered (slot 0 of mm_last_ceilings / _meters).
 static int deliver_device(mm_ctx *c, const mm_job *j, const mm_delivery *dl, const void *d_in, void *d_out,
                           mm_result *res) {
+    if (!dl) return master_device(c, j, d_in, d_out, res);
     if (const char *why = deliver_bad_args(j, dl)) return set_err(c, MM_ERR_ARG, "delivery: %s", why);
     const int kind = j->out_kind;
-    const size_t mid_bytes = (size_t)j->frames_proc * j->channels * (kind == MM_OUT_I16 ? 2 : 4);
     char *mid;
-    RET(get_buf(c, "deliver_mid", std::max<size_t>(mid_bytes, 1), &mid));
-    RET(master_device(c, j, d_in, mid, res));
+    RET(get_buf(c, "deliver_mid", std::max<size_t>(pcm_bytes(kind, j->frames_proc, j->channels), 1), &mid));
+    RET(master_device(c, j, d_in, mid, res));  // (the job asks for neither: its results stay empty)
     RET(resample_device(c, mid, kind, j->frames_proc, j->channels, dl->rs, d_out, &c->resample));
+    results_reset(c, 1, dl->ceiling_q28, dl->meter_on);
     c->resample_valid = true;
-    const int64_t fo = c->resample.frames_out;
-    if (dl->ceiling_q28) {
-        c->ceilings.assign(1, mm_ceiling{});
-        RET(ceiling_device(c, d_out, kind, fo, j->channels, dl->ceiling_q28, dl->window, &c->ceilings[0]));
-    }
-    if (dl->meter_on) {
-        c->meters.assign(1, mm_meter{});
-        RET(meter_device(c, d_out, kind, fo, j->channels, dl->loud, &c->meters[0]));
-    }
+    return finish_delivered(c, d_out, kind, c->resample.frames_out, j->channels, 0, dl->ceiling_q28, dl->window, dl->meter_on,
+                            dl->loud);
+}
+
+// mm_master and mm_deliver: upload, the call on the device, download.
+static int master_host(mm_ctx *c, const mm_job *j, const mm_delivery *dl, const void *in, void *out, mm_result *res) {
+    RET(validate(c, j));
+    if (const char *why = dl ? deliver_bad_args(j, dl) : nullptr) return set_err(c, MM_ERR_ARG, "delivery: %s", why);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t in_bytes = (size_t)j->frames_in * j->channels * in_sample_bytes(j->in_kind);
+    const size_t out_bytes = pcm_bytes(j->out_kind, delivered_frames(j, dl), j->channels);
+    char *d_in, *d_out;
+    RET(pcm_upload(c, "host_in", in, in_bytes, &d_in));
+    RET(get_buf(c, "host_out", std::max<size_t>(out_bytes, 1), &d_out));
+    RET(deliver_device(c, j, dl, d_in, d_out, res));
+    RET(pcm_download(c, out, d_out, out_bytes));
+    resolve_events(c);
     return MM_OK;
+}
+
+// mm_master_wav and mm_deliver_wav: file -> HBM, the call on the device, HBM -> file.  With
+// a delivery the header carries the resampler's rate_out and the converter's frames_out.
+static int master_wav(mm_ctx *c, const mm_job *jin, const mm_delivery *dl, const char *in_path, const char *out_path,
+                      mm_result *res) {
+    if (!jin || !in_path || !out_path) return set_err(c, MM_ERR_ARG, "null argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    FileCloser in{fopen(in_path, "rb")};
+    if (!in.f) return set_err(c, MM_ERR_ARG, "%s: cannot open", in_path);
+    mm_job j;
+    mm_wav_info wi;
+    RET(wav_job(c, in.f, in_path, jin, &j, &wi));
+    if (const char *why = dl ? deliver_bad_args(&j, dl) : nullptr) return set_err(c, MM_ERR_ARG, "delivery: %s", why);
+    const size_t out_bytes = pcm_bytes(j.out_kind, delivered_frames(&j, dl), j.channels);
+    if (out_bytes > 0xFFFFFFFFull - 36) return set_err(c, MM_ERR_ARG, "output larger than a RIFF file can hold");
+    char *d_in, *d_out;
+    RET(wav_stream_in(c, in.f, in_path, &j, &wi, &d_in));
+    RET(get_buf(c, "host_out", std::max<size_t>(out_bytes, 1), &d_out));
+    RET(deliver_device(c, &j, dl, d_in, d_out, res));
+    return wav_stream_out(c, out_path, j.out_kind, j.channels, dl ? dl->rs->rate_out : j.rate, d_out, out_bytes);
 }
 
 extern "C" {
@@ -394,23 +406,16 @@ int mm_resample_device(mm_ctx *c, const void *d_in, int kind, int64_t frames, in
 int mm_resample_pcm(mm_ctx *c, const void *in, int kind, int64_t frames, int channels, const mm_resampler *rs, void *out_pcm,
                     mm_resample *out) {
     if (!c) return MM_ERR_ARG;
-    if (!out || !rs || (frames > 0 && (!in || !out_pcm)) || (kind != MM_OUT_I16 && kind != MM_OUT_F32))
-        return set_err(c, MM_ERR_ARG, "bad arguments");
+    if (!out || !rs || (frames > 0 && (!in || !out_pcm)) || !pcm_kind_ok(kind)) return set_err(c, MM_ERR_ARG, "bad arguments");
     if (const char *why = resample_bad_geometry(rs->L, rs->M, rs->K)) return set_err(c, MM_ERR_ARG, "resampler: %s", why);
     if (const char *why = resample_bad_signal(frames, channels, rs->L, rs->M)) return set_err(c, MM_ERR_ARG, "%s", why);
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t fb = (size_t)channels * (kind == MM_OUT_I16 ? 2 : 4);
-    const size_t in_bytes = (size_t)frames * fb, out_bytes = (size_t)rs_frames(frames, rs->L, rs->M) * fb;
+    const size_t out_bytes = pcm_bytes(kind, rs_frames(frames, rs->L, rs->M), channels);
     char *din, *dout;
-    RET(get_buf(c, "rs_in", std::max<size_t>(in_bytes, 1), &din));
+    RET(pcm_upload(c, "rs_in", in, pcm_bytes(kind, frames, channels), &din));
     RET(get_buf(c, "rs_out", std::max<size_t>(out_bytes, 1), &dout));
-    if (in_bytes) HIPCHK(c, hipMemcpyAsync(din, in, in_bytes, hipMemcpyHostToDevice, c->stream));
     RET(resample_device(c, din, kind, frames, channels, rs, dout, out));
-    if (out_bytes) {
-        HIPCHK(c, hipMemcpyAsync(out_pcm, dout, out_bytes, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    return MM_OK;
+    return pcm_download(c, out_pcm, dout, out_bytes);
 }
 
 // The definition restated in plain C++ on the host (no context, no GPU): what the kernel
@@ -452,48 +457,26 @@ int mm_last_resample(mm_ctx *c, mm_resample *out) {
 int mm_deliver_device(mm_ctx *c, const mm_job *j, const mm_delivery *dl, const void *d_in, void *d_out, mm_result *res) {
     if (!c) return MM_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    return deliver_device(c, j, dl, d_in, d_out, res);
+    return deliver_device(c, j, dl ? dl : &NO_DELIVERY, d_in, d_out, res);
+}
+
+int mm_master(mm_ctx *c, const mm_job *j, const void *in, void *out, mm_result *res) {
+    return c ? master_host(c, j, nullptr, in, out, res) : MM_ERR_ARG;
 }
 
 int mm_deliver(mm_ctx *c, const mm_job *j, const mm_delivery *dl, const void *in, void *out, mm_result *res) {
-    if (!c) return MM_ERR_ARG;
-    RET(validate(c, j));
-    if (const char *why = deliver_bad_args(j, dl)) return set_err(c, MM_ERR_ARG, "delivery: %s", why);
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t fb = (size_t)j->channels * (j->out_kind == MM_OUT_I16 ? 2 : 4);
-    const size_t in_bytes = (size_t)j->frames_in * j->channels * in_sample_bytes(j->in_kind);
-    const size_t out_bytes = (size_t)rs_frames(j->frames_proc, dl->rs->L, dl->rs->M) * fb;
-    char *d_in, *d_out;
-    RET(get_buf(c, "host_in", std::max<size_t>(in_bytes, 1), &d_in));
-    RET(get_buf(c, "host_out", std::max<size_t>(out_bytes, 1), &d_out));
-    if (in_bytes) HIPCHK(c, hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, c->stream));
-    RET(deliver_device(c, j, dl, d_in, d_out, res));
-    if (out_bytes) HIPCHK(c, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    resolve_events(c);
-    return MM_OK;
+    return c ? master_host(c, j, dl ? dl : &NO_DELIVERY, in, out, res) : MM_ERR_ARG;
 }
 
-// mm_master_wav with the delivery path in the middle: the header carries the resampler's
-// rate_out and the converter's frames_out.
+int mm_master_wav(mm_ctx *c, const mm_job *jin, const char *in_path, const char *out_path, mm_result *res) {
+    return c ? master_wav(c, jin, nullptr, in_path, out_path, res) : MM_ERR_ARG;
+}
+
 int mm_deliver_wav(mm_ctx *c, const mm_job *jin, const mm_delivery *dl, const char *in_path, const char *out_path,
                    mm_result *res) {
     if (!c) return MM_ERR_ARG;
-    if (!jin || !dl || !in_path || !out_path) return set_err(c, MM_ERR_ARG, "null argument");
-    HIPCHK(c, hipSetDevice(c->device));
-    FileCloser in{fopen(in_path, "rb")};
-    if (!in.f) return set_err(c, MM_ERR_ARG, "%s: cannot open", in_path);
-    mm_job j;
-    mm_wav_info wi;
-    RET(wav_job(c, in.f, in_path, jin, &j, &wi));
-    if (const char *why = deliver_bad_args(&j, dl)) return set_err(c, MM_ERR_ARG, "delivery: %s", why);
-    const size_t out_bytes = (size_t)rs_frames(j.frames_proc, dl->rs->L, dl->rs->M) * j.channels * (j.out_kind == MM_OUT_I16 ? 2 : 4);
-    if (out_bytes > 0xFFFFFFFFull - 36) return set_err(c, MM_ERR_ARG, "output larger than a RIFF file can hold");
-    char *d_in, *d_out;
-    RET(wav_stream_in(c, in.f, in_path, &j, &wi, &d_in));
-    RET(get_buf(c, "host_out", std::max<size_t>(out_bytes, 1), &d_out));
-    RET(deliver_device(c, &j, dl, d_in, d_out, res));
-    return wav_stream_out(c, out_path, j.out_kind, j.channels, dl->rs->rate_out, d_out, out_bytes);
+    if (!dl) return set_err(c, MM_ERR_ARG, "null argument");
+    return master_wav(c, jin, dl, in_path, out_path, res);
 }
 
 }  // extern "C"

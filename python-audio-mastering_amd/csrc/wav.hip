@@ -1,7 +1,7 @@
-// wav.hip — the WAV file path of the C-ABI (mm_wav_probe, mm_master_wav): RIFF
-// codec and pinned double-buffered staging around the chain.  Included from
-// mastering.hip (its context helpers and master_device).  mm_deliver_wav (resample.hip)
-// runs on the same helpers: wav_job, wav_stream_in, wav_stream_out.
+// wav.hip — the WAV file path of the C-ABI: mm_wav_probe, and the RIFF codec and pinned
+// double-buffered staging (wav_job, wav_stream_in, wav_stream_out) that mm_master_wav and
+// mm_deliver_wav run around the chain (master_wav in resample.hip).  Included from
+// mastering.hip (its context helpers).
 
 extern "C" {
 
@@ -172,24 +172,6 @@ static int wav_stream_out(mm_ctx *c, const char *out_path, int out_kind, int cha
     HIPCHK(c, hipStreamSynchronize(c->stream));
     resolve_events(c);
     return MM_OK;
-}
-
-int mm_master_wav(mm_ctx *c, const mm_job *jin, const char *in_path, const char *out_path, mm_result *res) {
-    if (!c) return MM_ERR_ARG;
-    if (!jin || !in_path || !out_path) return set_err(c, MM_ERR_ARG, "null argument");
-    HIPCHK(c, hipSetDevice(c->device));
-    FileCloser in{fopen(in_path, "rb")};
-    if (!in.f) return set_err(c, MM_ERR_ARG, "%s: cannot open", in_path);
-    mm_job j;
-    mm_wav_info wi;
-    RET(wav_job(c, in.f, in_path, jin, &j, &wi));
-    const size_t out_bytes = (size_t)j.frames_proc * j.channels * (j.out_kind == MM_OUT_I16 ? 2 : 4);
-    if (out_bytes > 0xFFFFFFFFull - 36) return set_err(c, MM_ERR_ARG, "output larger than a RIFF file can hold");
-    char *d_in, *d_out;
-    RET(wav_stream_in(c, in.f, in_path, &j, &wi, &d_in));
-    RET(get_buf(c, "host_out", std::max<size_t>(out_bytes, 1), &d_out));
-    RET(master_device(c, &j, d_in, d_out, res));
-    return wav_stream_out(c, out_path, j.out_kind, j.channels, j.rate, d_out, out_bytes);
 }
 
 }  // extern "C"

@@ -277,21 +277,18 @@ def report_dict(m: native.MMMeter, lufs_target=None) -> dict:
     return rep
 
 
+def _last(ctx: native.Context, fn_name: str, struct, cap: int) -> list:
+    """The per-track structs of the context's last master call (mm_last_meters / mm_last_ceilings)."""
+    arr = (struct * max(cap, 1))()
+    n = ctx.check(getattr(ctx.lib, fn_name)(ctx.ptr, cap, arr), fn_name)
+    return _last(ctx, fn_name, struct, n) if n > cap else list(arr[:n])
+
+
 def meters(ctx: native.Context, cap: int = native.BATCH_STREAMS) -> list:
     """The mm_meter of every track of the context's last master call (mm_last_meters):
     one for master_device, one per job for master_batch.  RuntimeError if that call did
     not meter (no job had `report`)."""
-    arr = (native.MMMeter * max(cap, 1))()
-    n = ctx.check(ctx.lib.mm_last_meters(ctx.ptr, cap, arr), "mm_last_meters")
-    if n > cap:
-        return meters(ctx, n)
-    return list(arr[:n])
-
-
-def _add_report(info: dict, job: "Job", ctx: native.Context) -> dict:
-    if job.job.meter_on:
-        info["report"] = report_dict(meters(ctx, 1)[0], job.job.lufs_target if job.job.lufs_on else None)
-    return info
+    return _last(ctx, "mm_last_meters", native.MMMeter, cap)
 
 
 def ceiling_dict(m: native.MMCeiling) -> dict:
@@ -311,17 +308,7 @@ def ceilings(ctx: native.Context, cap: int = native.BATCH_STREAMS) -> list:
     """The mm_ceiling of every track of the context's last master call (mm_last_ceilings):
     one for master_device, one per job for master_batch, in job order (frames 0: that
     job set none).  RuntimeError if no job of that call had `ceiling_dbtp`."""
-    arr = (native.MMCeiling * max(cap, 1))()
-    n = ctx.check(ctx.lib.mm_last_ceilings(ctx.ptr, cap, arr), "mm_last_ceilings")
-    if n > cap:
-        return ceilings(ctx, n)
-    return list(arr[:n])
-
-
-def _add_ceiling(info: dict, job: "Job", ctx: native.Context) -> dict:
-    if job.job.ceiling_q28:
-        info["ceiling"] = ceiling_dict(ceilings(ctx, 1)[0])
-    return info
+    return _last(ctx, "mm_last_ceilings", native.MMCeiling, cap)
 
 
 def resample_dict(m: native.MMResample) -> dict:
@@ -335,17 +322,26 @@ def resample_dict(m: native.MMResample) -> dict:
     return d
 
 
-def _deliver_info(info: dict, job: "Job", ctx: native.Context) -> dict:
-    """The info of a delivery at another rate: the chain's, with the delivered frames and
-    rate, the converter's statistics and the ceiling and report of the converted signal."""
-    m = native.MMResample()
-    ctx.check(ctx.lib.mm_last_resample(ctx.ptr, ctypes.byref(m)), "mm_last_resample")
-    info["frames"], info["rate"], info["resample"] = job.frames_out, job.output_rate, resample_dict(m)
-    if job.delivery.ceiling_q28:
+def _finish_info(info: dict, job: "Job", ctx: native.Context) -> dict:
+    """The chain's info with what the end of the master call added: the ceiling and the
+    report of the delivered signal and, for a delivery at another rate, the delivered
+    frames and rate and the converter's statistics."""
+    end = job.job if job.delivery is None else job.delivery  # who carries ceiling_q28 and meter_on
+    if job.delivery is not None:
+        m = native.MMResample()
+        ctx.check(ctx.lib.mm_last_resample(ctx.ptr, ctypes.byref(m)), "mm_last_resample")
+        info["frames"], info["rate"], info["resample"] = job.frames_out, job.output_rate, resample_dict(m)
+    if end.ceiling_q28:
         info["ceiling"] = ceiling_dict(ceilings(ctx, 1)[0])
-    if job.delivery.meter_on:
+    if end.meter_on:
         info["report"] = report_dict(meters(ctx, 1)[0], job.job.lufs_target if job.job.lufs_on else None)
     return info
+
+
+def _out_kind(pcm: np.ndarray):
+    """An int16 or float32 array as the stages on the delivered signal take it: (array, kind)."""
+    x, in_kind = _device_input(pcm)
+    return x, native.MM_OUT_I16 if in_kind == native.MM_IN_I16 else native.MM_OUT_F32
 
 
 def resample_pcm(pcm: np.ndarray, rate_in: int, rate_out: int, device: int = 0):
@@ -354,8 +350,7 @@ def resample_pcm(pcm: np.ndarray, rate_in: int, rate_out: int, device: int = 0):
     ceil(N * L / M) frames, resample_dict).  ValueError for a rate pair outside the
     converter's limits (design.resample_geometry)."""
     ch = 1 if pcm.ndim == 1 else pcm.shape[1]
-    x, in_kind = _device_input(pcm)
-    kind = native.MM_OUT_I16 if in_kind == native.MM_IN_I16 else native.MM_OUT_F32
+    x, kind = _out_kind(pcm)
     rs = Resampler(rate_in, rate_out)
     n_out = rs.frames_out(x.shape[0])
     out = np.empty((n_out,) if pcm.ndim == 1 else (n_out, ch), x.dtype)
@@ -372,9 +367,8 @@ def ceiling_pcm(pcm: np.ndarray, rate: int, ceiling_dbtp: float, window: int | N
     ceiling without mastering it (mm_ceiling_pcm): returns (a new array, ceiling_dict).
     `window`: look-ahead frames (default design.ceiling_window(rate))."""
     ch = 1 if pcm.ndim == 1 else pcm.shape[1]
-    x, in_kind = _device_input(pcm)
+    x, kind = _out_kind(pcm)
     x = x.copy()
-    kind = native.MM_OUT_I16 if in_kind == native.MM_IN_I16 else native.MM_OUT_F32
     w = design.ceiling_window(rate) if window is None else int(window)
     ctx = native.context(device)
     m = native.MMCeiling()
@@ -387,8 +381,7 @@ def meter_pcm(pcm: np.ndarray, rate: int, loudness: bool = True, device: int = 0
     """Meter an int16 (or float32 = int16 / 32768) array [N] or [N, ch] without
     mastering it: the report of `report_dict` (mm_meter_pcm)."""
     ch = 1 if pcm.ndim == 1 else pcm.shape[1]
-    x, in_kind = _device_input(pcm)
-    kind = native.MM_OUT_I16 if in_kind == native.MM_IN_I16 else native.MM_OUT_F32
+    x, kind = _out_kind(pcm)
     job = Job(x.shape[0], rate, ch, {}, single_chunk=True, report=True) if loudness else None
     ctx = native.context(device)
     m = native.MMMeter()
@@ -426,10 +419,10 @@ def master_pcm(pcm: np.ndarray, rate: int, params: dict, out_kind: int = native.
         ctx.check(ctx.lib.mm_deliver(ctx.ptr, ctypes.byref(job.job), ctypes.byref(job.delivery),
                                      x.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p),
                                      ctypes.byref(res)), "mm_deliver")
-        return out, _deliver_info(_info(job, res), job, ctx)
-    ctx.check(ctx.lib.mm_master(ctx.ptr, ctypes.byref(job.job), x.ctypes.data_as(ctypes.c_void_p),
-                                out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(res)), "mm_master")
-    return out, _add_report(_add_ceiling(_info(job, res), job, ctx), job, ctx)
+    else:
+        ctx.check(ctx.lib.mm_master(ctx.ptr, ctypes.byref(job.job), x.ctypes.data_as(ctypes.c_void_p),
+                                    out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(res)), "mm_master")
+    return out, _finish_info(_info(job, res), job, ctx)
 
 
 def wav_info(path: str, device: int = 0) -> native.MMWavInfo:
@@ -508,11 +501,10 @@ def process(input_path: str, output_path: str, params: dict, device: int = 0, ve
         ctx.check(ctx.lib.mm_deliver_wav(ctx.ptr, ctypes.byref(job.job), ctypes.byref(job.delivery),
                                          os.fsencode(input_path), os.fsencode(output_path), ctypes.byref(res)),
                   "mm_deliver_wav")
-        info = _deliver_info(_info(job, res), job, ctx)
     else:
         ctx.check(ctx.lib.mm_master_wav(ctx.ptr, ctypes.byref(job.job), os.fsencode(input_path),
                                         os.fsencode(output_path), ctypes.byref(res)), "mm_master_wav")
-        info = _add_report(_add_ceiling(_info(job, res), job, ctx), job, ctx)
+    info = _finish_info(_info(job, res), job, ctx)
     if verbose and info["loudness"] is not None:
         print(f"Current loudness: {info['loudness']:.2f} LUFS. Applying {info['gain_db']:.2f} dB gain...")
     info["output_path"] = os.path.abspath(output_path)

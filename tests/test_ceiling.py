@@ -126,6 +126,22 @@ def test_host_restatement_random(n, ch, W):
     assert st["tp_out_q28"] <= C
 
 
+@pytest.mark.parametrize("ch", [1, 2])
+@pytest.mark.parametrize("n", [1, 11, 12, 13, 500])
+def test_host_tp_in_is_the_meters_linked_peak(n, ch):
+    """mm_ceiling_host and mm_true_peak_host share one host FIR: on full-scale noise (the
+    LCG of tools/diag/ceiling_host_check.cpp) tp_in_q28 == max_c true_peak_q28[c]."""
+    from test_meter import host_meter
+    W = 16
+    s, v = n * 31 + W * 7 + ch, np.empty(n * ch, np.int64)
+    for i in range(n * ch):
+        s = (s * 1664525 + 1013904223) & 0xFFFFFFFF
+        v[i] = s >> 16
+    pcm = v.astype(np.uint16).view(np.int16).reshape((n, ch) if ch == 2 else (n,))
+    _, st = host_ceiling(pcm, 1 << 27, W)
+    assert st["tp_in_q28"] == max(host_meter(pcm)["true_peak_q28"])
+
+
 @pytest.mark.parametrize("W", [1, 16, 220, 1024])
 @pytest.mark.parametrize("name", ["under", "limited", "trimmed"])
 def test_host_restatement_branch_inputs(branch_inputs, branch_refs, name, W):
