@@ -1,6 +1,7 @@
 // context.h — the library's context (mm_ctx: stream, device buffers, the chain's
-// control block and cached tables) and the helpers every host file uses: errors,
-// device buffers, the timed launch.  Included by mastering.hip after the kernels.
+// control block (control.h) and cached tables) and the helpers every host file uses:
+// errors, device buffers, the timed launch.  Included by mastering.hip after the
+// kernels and control.h.
 #pragma once
 
 namespace {
@@ -20,6 +21,17 @@ struct KStat {
     int64_t n = 0;
 };
 
+// The envelope solve kept across the queued launches (stage_compress -> comp_sweeps /
+// comp_back), and what the context learnt from its last one.
+struct Solve {
+    bool on = false;
+    CompArgs ca{};
+    uint32_t stamp = 0;  // stamp of the last queued fix-up sweep
+    int iters = 0, pending = 0;
+    int queue = 0;     // sweeps to queue with the next solve (0: COMP_SWEEPS; then the last solve's need + 1)
+    uint64_t sig = 0;  // settings and geometry of the solve `queue` was learnt on (comp_signature)
+};
+
 }  // namespace
 
 struct mm_ctx {
@@ -33,37 +45,8 @@ struct mm_ctx {
     mm_job job{};
     int64_t G = 0;
     short2 *mix = nullptr;
-    unsigned *lb_error = nullptr;
-    // per-chain control words, zeroed by ONE memset at the chain start: the three
-    // IIR stages' ticket/status regions and the compressor's sweep flags; a
-    // region is "fresh" until its first use (repeats zero their own words)
-    unsigned *ctl_lb[3] = {nullptr, nullptr, nullptr};
-    bool ctl_fresh[3] = {false, false, false};
-    bool comp_flags_fresh = false;
-    // compressor state kept across the queued launches (stage_front -> comp_sweeps/comp_back)
-    bool comp_on = false;
-    CompArgs ca{};
-    uint32_t comp_stamp = 0;  // stamp of the last queued fix-up sweep
-    unsigned *comp_changed = nullptr;
-    char *ctl = nullptr;                // the chain's control block (setup_control)
-    size_t ctl_bytes = 0, ctl_rba = 0;  // its size and readback area
-    size_t ctl_region = 0;              // bytes of each of its look-back regions (lb_prepare)
-    // the block is zero from ctl_clean_ptr up to ctl_clean_bytes: the last chain's
-    // tail (finalize) zeroed it, so the next setup_control queues no fill
-    bool ctl_clean = false;
-    char *ctl_clean_ptr = nullptr;
-    size_t ctl_clean_bytes = 0;
-    bool tail_readback = false;         // the last queued finalize hands the readback area over
-    uint32_t *ctl_claims = nullptr;     // its zeroed claim stamps
-    int comp_iters = 0, comp_pending = 0;
-    // a fused timeline's tracks with padding: {end, end of the last chunk} pairs on the
-    // device for comp_trim_kernel (unit_enqueue sets them around stage_front; 0: none)
-    const int64_t *comp_pad = nullptr;
-    int comp_pad_n = 0;
-    int comp_queue = 0;  // sweeps to queue with the next solve (0: COMP_SWEEPS; then the last solve's need + 1)
-    uint64_t comp_sig = 0;  // settings and geometry of the solve comp_queue was learnt on (comp_signature)
-    // loudness on the device
-    double *gate_out = nullptr;         // [2]: L, gain
+    ChainCtl ctl;  // the chain's control block and its readback (control.h)
+    Solve comp;    // the envelope solve queued on it
     std::vector<int64_t> geom_cache;    // loudness geometry already on the device (upload_geometry)
     // exact block energies (kw_blocks_kernel): per block its first frame and program
     int64_t *kb_lo = nullptr;
@@ -84,9 +67,6 @@ struct mm_ctx {
     uint64_t sat_key = 0;             // content key of the exciter table on the device (0: none)
     bool sat_codes = false;           // its correction codes are complete (no entry needs the table)
     std::map<std::string, std::vector<double>> mats_cache;
-    // pinned block the chain's results are copied into (one sync per chain)
-    char *rb = nullptr, *rb_dev = nullptr;  // (rb_dev: its device address)
-    size_t rb_cap = 0;
     // batch execution (mm_master_batch): child contexts, one stream each
     std::vector<mm_ctx *> children;
     // mastering report of the last master call (mm_last_meters; empty: it did not meter)

@@ -1,7 +1,8 @@
 // mastering.hip — host side of the C-ABI (include/mastering.h), one translation
 // unit: the launch sequence of the chain (a unit of n >= 1 tracks between two
 // syncs), loudness gating, the batch scheduler and the staged / time-sharded entry
-// points.  The context is context.h, followed by decode.hip (24/32-bit PCM input);
+// points.  The chain's control block is control.h, the context that holds it
+// context.h, followed by decode.hip (24/32-bit PCM input);
 // wav.hip, comm.hip, ops.hip, then pcm16.h, meter.hip, ceiling.hip and resample.hip (with
 // mm_master* / mm_deliver*: a master call with or without a delivery) come at the end.
 #include <rccl/rccl.h>
@@ -23,6 +24,7 @@
 
 using namespace mm;
 
+#include "control.h"
 #include "context.h"
 #include "decode.hip"
 
@@ -106,19 +108,14 @@ static int upload_zw(mm_ctx *c, const char *name, const mm_iir &f, int T, const 
     return MM_OK;
 }
 
-// Per-launch look-back state for nblk blocks of CH lines: the ticket and the
-// status words are zeroed by a memset on the stream right before the launch.
-static size_t lb_flag_bytes(int64_t nblk) { return ((16 + (size_t)nblk * 4) + 15) / 16 * 16; }
-
-// region: the chain's pre-zeroed control region of this stage (0 eq, 1 crossover,
-// 2 K-weighting), used once and only by a launch it was sized for; otherwise (or
-// on a repeat) a private memset.
+// Per-launch look-back state for nblk blocks of CH lines.  region: the chain's
+// pre-zeroed control region of this stage (ChainCtl::take_region) and its error
+// word; otherwise (-1, or a region already used) the ticket and the status words
+// are zeroed by a private memset right before the launch, and the caller of a
+// launch outside a chain sets lb.error.
 static int lb_prepare(mm_ctx *c, int64_t nblk, int ch, LbArgs &lb, int region = -1) {
-    char *flags;
-    if (region >= 0 && c->ctl_fresh[region] && lb_flag_bytes(nblk) <= c->ctl_region) {
-        flags = reinterpret_cast<char *>(c->ctl_lb[region]);
-        c->ctl_fresh[region] = false;
-    } else {
+    char *flags = c->ctl.take_region(region, nblk);
+    if (!flags) {
         const size_t flag_bytes = lb_flag_bytes(nblk);
         RET(get_buf(c, "lb_flags", flag_bytes, &flags));
         HIPCHK(c, hipMemsetAsync(flags, 0, flag_bytes, c->stream));
@@ -127,8 +124,7 @@ static int lb_prepare(mm_ctx *c, int64_t nblk, int ch, LbArgs &lb, int region = 
     lb.status = reinterpret_cast<unsigned *>(flags + 16);
     RET(get_buf(c, "lb_agg", (size_t)nblk * ch * 8, &lb.agg));
     RET(get_buf(c, "lb_incl", (size_t)nblk * ch * 8, &lb.incl));
-    if (c->lb_error) lb.error = c->lb_error;
-    else RET(get_buf(c, "lb_error", 4, &lb.error));
+    if (region >= 0) lb.error = &c->ctl.dev()->lb_error;
     lb.init = nullptr;
     return MM_OK;
 }
@@ -210,76 +206,33 @@ static int launch_eq(mm_ctx *c, int nsec, int ch, unsigned nblk, const EqArgs &e
 constexpr int COMP_SWEEPS = 8;  // queued by a context's first solve (a sweep after a quiet one exits at once)
 
 static int comp_sweeps(mm_ctx *c, int n) {
-    CompArgs &ca = c->ca;
+    Solve &sv = c->comp;
+    CompArgs &ca = sv.ca;
     const int64_t NS = ca.GS;
-    if (!c->comp_flags_fresh)  // flags only (the walked count accumulates)
-        HIPCHK(c, hipMemsetAsync(c->comp_changed, 0, 16 * sizeof(unsigned int), c->stream));
-    c->comp_flags_fresh = false;
+    unsigned *flags;
+    HIPCHK(c, c->ctl.take_flags(c->stream, &flags));
     for (int k = 0; k < n; ++k) {
-        ca.sweep_idx = (int)c->comp_stamp;
-        ca.stamp = ++c->comp_stamp;
+        ca.sweep_idx = (int)sv.stamp;
+        ca.stamp = ++sv.stamp;
         ca.heads = ca.stamp > 1 ? 1 : 0;  // the chain's first sweep is a Jacobi step
-        ca.changed = c->comp_changed + k;
-        const unsigned int *prevf = k > 0 ? c->comp_changed + (k - 1) : nullptr;
+        ca.changed = flags + k;
+        const unsigned int *prevf = k > 0 ? flags + (k - 1) : nullptr;
         RET(launch(c, "comp_fix", comp_fix_kernel, dim3(blocks_for(NS, 64), 3), dim3(64), 0, ca, prevf));
     }
-    c->comp_pending = n;
+    sv.pending = n;
     return MM_OK;
 }
 
 // gains + overlay into q2, every tile starting from its stored entry state
 static int comp_back(mm_ctx *c) {
-    const CompArgs &ca = c->ca;
+    const CompArgs &ca = c->comp.ca;
     const int64_t nchunks = ca.GS / ca.SPC;  // (chunk-aligned blocks of APPLY_TILES tiles)
     return launch(c, "comp_apply", comp_apply_kernel,
                   dim3((unsigned)(nchunks * ((ca.K + APPLY_TILES - 1) / APPLY_TILES))), dim3(3 * APPLY_TILES), 0, ca);
 }
 
-// Pinned readback block of one chain pass (offsets in bytes): look-back error
-// word, sweep flags, re-walked frame count, loudness + gain, per-chunk active counts.
-constexpr size_t RB_ERR = 0, RB_FLAGS = 16, RB_WALKED = 80, RB_LG = 96, RB_TOTALS = 128;
-// finalize's done counters after the readback area (FIN_DONE_LINES lines of 128 B and
-// the top one; FinArgs::done)
-constexpr size_t FIN_DONE_BYTES = (size_t)(FIN_DONE_LINES + 1) * 128;
-static size_t rb_bytes(int64_t nch) { return RB_TOTALS + (size_t)12 * nch; }
-
-static int64_t comp_chunks(const mm_ctx *c) { return c->comp_on ? c->ca.GS / c->ca.SPC : 0; }
-
-static int ensure_rb(mm_ctx *c, size_t bytes) {
-    if (c->rb_cap >= bytes) return MM_OK;
-    if (c->rb) HIPCHK(c, hipHostFree(c->rb));
-    c->rb = c->rb_dev = nullptr;
-    c->rb_cap = 0;
-    // mapped and coherent: the chain's last finalize block writes it directly
-    HIPCHK(c, hipHostMalloc((void **)&c->rb, bytes, hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(c, hipHostGetDevicePointer((void **)&c->rb_dev, c->rb, 0));
-    c->rb_cap = bytes;
-    return MM_OK;
-}
-
-// Hand the readback area over in the chain's last finalize launch (FinArgs::ctl),
-// instead of a copy after it.
-static int attach_tail(mm_ctx *c, FinArgs &fa) {
-    c->tail_readback = false;
-    if (!c->ctl) return MM_OK;
-    const size_t rbb = rb_bytes(comp_chunks(c));
-    RET(ensure_rb(c, rbb + 64));
-    fa.ctl = c->ctl;
-    fa.ctl_bytes = (int64_t)c->ctl_bytes;
-    fa.rb_area = (int64_t)(c->ctl_rba + FIN_DONE_BYTES);
-    fa.rb_bytes = (int)rbb;
-    fa.rb_host = c->rb_dev;
-    fa.done = reinterpret_cast<unsigned *>(c->ctl + c->ctl_rba);
-    c->tail_readback = true;
-    return MM_OK;
-}
-
-// Queue the D2H copy of everything the host checks after the chain (no sync): the
-// readback area of the control block, in ONE copy.
 static int queue_readback(mm_ctx *c) {
-    const int64_t nch = comp_chunks(c);
-    RET(ensure_rb(c, rb_bytes(nch) + 64));
-    HIPCHK(c, hipMemcpyAsync(c->rb, c->ctl, rb_bytes(nch), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, c->ctl.queue_copy(c->stream));
     return MM_OK;
 }
 
@@ -287,11 +240,12 @@ static int queue_readback(mm_ctx *c) {
 // block only waits on blocks that started before it) and whether the queued
 // sweeps converged.
 static int evaluate_chain(mm_ctx *c, bool *converged) {
-    if (*reinterpret_cast<const unsigned *>(c->rb + RB_ERR)) return set_err(c, MM_ERR_STATE, "IIR look-back timed out");
-    if (c->comp_on && c->ca.trace) {  // MM_FIX_TRACE: the three slowest walkers of every sweep
-        const int64_t NS = c->ca.GS;
+    Solve &sv = c->comp;
+    if (c->ctl.head().lb_error) return set_err(c, MM_ERR_STATE, "IIR look-back timed out");
+    if (sv.on && sv.ca.trace) {  // MM_FIX_TRACE: the three slowest walkers of every sweep
+        const int64_t NS = sv.ca.GS;
         std::vector<uint32_t> tr((size_t)16 * 3 * NS * 4);
-        HIPCHK(c, hipMemcpy(tr.data(), c->ca.trace, tr.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(tr.data(), sv.ca.trace, tr.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
         if (const char *path = getenv("MM_FIX_TRACE_DUMP")) {  // every walker record: [sweep][band][super-tile][4]
             if (FILE *f = fopen(path, "wb")) {
                 fwrite(tr.data(), sizeof(uint32_t), tr.size(), f);
@@ -321,56 +275,46 @@ static int evaluate_chain(mm_ctx *c, bool *converged) {
         }
     }
     *converged = true;
-    if (c->comp_on && c->comp_pending) {
-        const unsigned *flags = reinterpret_cast<const unsigned *>(c->rb + RB_FLAGS);
+    if (sv.on && sv.pending) {
+        const unsigned *flags = c->ctl.head().flags;
         int k = 0;
-        while (k < c->comp_pending && flags[k]) ++k;
-        c->comp_iters += k;
-        *converged = k < c->comp_pending;
-        c->comp_pending = 0;
-        // the solve needed comp_iters flagged sweeps and one quiet one: queue that + 1
-        if (*converged) c->comp_queue = std::min(16, std::max(3, c->comp_iters + 2));
-        if (!*converged && c->comp_iters >= c->job.comp_max_iters)
-            return set_err(c, MM_ERR_STATE, "compressor did not converge in %d sweeps", c->comp_iters);
+        while (k < sv.pending && flags[k]) ++k;
+        sv.iters += k;
+        *converged = k < sv.pending;
+        sv.pending = 0;
+        // the solve needed `iters` flagged sweeps and one quiet one: queue that + 1
+        if (*converged) sv.queue = std::min(16, std::max(3, sv.iters + 2));
+        if (!*converged && sv.iters >= c->job.comp_max_iters)
+            return set_err(c, MM_ERR_STATE, "compressor did not converge in %d sweeps", sv.iters);
     }
     return MM_OK;
 }
 
-// An extension after a tail hand-over starts from a zeroed control block: the
-// per-chunk active counts (comp_rms, once per chain) and the earlier passes'
-// re-walked counts are kept on the host and merged into the last readback.
-struct RbKeep {
-    bool on = false;
-    std::vector<int32_t> tot;
-    unsigned long long walked[2] = {0, 0};
-};
-static void rb_keep(mm_ctx *c, RbKeep &k) {
-    if (!c->tail_readback) return;  // (a copied readback: the device words accumulate)
-    const int32_t *tot = reinterpret_cast<const int32_t *>(c->rb + RB_TOTALS);
-    if (!k.on) k.tot.assign(tot, tot + 3 * comp_chunks(c));
-    const unsigned long long *w = reinterpret_cast<const unsigned long long *>(c->rb + RB_WALKED);
-    k.walked[0] += w[0];
-    k.walked[1] += w[1];
-    k.on = true;
-    c->comp_flags_fresh = true;  // the sweep flags are zero as well
-}
-// After the chain's last pass: merge what rb_keep held, and note a zeroed block.
-static void rb_finish(mm_ctx *c, const RbKeep &k) {
-    if (k.on) {
-        memcpy(c->rb + RB_TOTALS, k.tot.data(), k.tot.size() * sizeof(int32_t));
-        unsigned long long *w = reinterpret_cast<unsigned long long *>(c->rb + RB_WALKED);
-        w[0] += k.walked[0];
-        w[1] += k.walked[1];
+// The chain's one sync, its readback queued: a rare unconverged solve is resumed
+// with 8 more sweeps, the back end and `requeue_tail` (what follows the apply and
+// brings the next readback) until it has converged (ChainCtl::keep / finish merge
+// what the passes' readbacks carried).
+template <typename Tail>
+static int solve_to_convergence(mm_ctx *c, Tail requeue_tail) {
+    for (;;) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        bool converged;
+        RET(evaluate_chain(c, &converged));
+        if (converged) break;
+        c->ctl.keep();
+        RET(comp_sweeps(c, 8));
+        RET(comp_back(c));
+        RET(requeue_tail());
     }
-    c->ctl_clean = c->tail_readback;
-    c->ctl_clean_ptr = c->ctl;
-    c->ctl_clean_bytes = c->ctl_bytes;
+    c->ctl.finish();
+    return MM_OK;
 }
 
-static int chain_check(mm_ctx *c, bool *converged) {
+// A chain without a tail (the staged entry points, the operators): ONE copy of the
+// readback area, then the sync.
+static int chain_check(mm_ctx *c) {
     RET(queue_readback(c));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return evaluate_chain(c, converged);
+    return solve_to_convergence(c, [c] { return queue_readback(c); });
 }
 
 // Geometry of the envelope solve (the C-ABI's mm_solve_geometry): TPS tiles per
@@ -397,35 +341,12 @@ static int solve_geometry(const mm_job *j, mm_solve_geom *g) {
     return g->chunk_plane_bytes < ((int64_t)1 << 31) ? MM_OK : MM_ERR_ARG;
 }
 
-// Control words of the whole chain: the readback area (RB_* layout: look-back
-// error word, sweep flags, re-walked count, loudness + gain, per-chunk active
-// counts), finalize's done counters, the sweeps' claim stamps, then the eq /
-// crossover / K-weighting look-back regions (each fresh until its first use).  The chain's
-// last finalize hands the readback area to the mapped host block and leaves the
-// whole block zeroed (FinArgs::ctl), so a chain after a completed one starts with
-// no fill and ends with no copy; otherwise ONE memset here and ONE copy at the end.
-static int setup_control(mm_ctx *c, unsigned nblk, int64_t nch, int64_t claims) {
-    const size_t region = lb_flag_bytes(nblk);  // >= the K-weighting stage's (256 tiles per block)
-    const size_t rba = (rb_bytes(nch) + 255) / 256 * 256, cla = ((size_t)claims * 4 + 255) / 256 * 256;
-    const size_t bytes = rba + FIN_DONE_BYTES + cla + 3 * region;
-    char *ctl;
-    RET(get_buf(c, "ctl", bytes, &ctl));
-    if (!c->ctl_clean || ctl != c->ctl_clean_ptr || bytes > c->ctl_clean_bytes)
-        HIPCHK(c, hipMemsetAsync(ctl, 0, bytes, c->stream));
-    c->ctl_clean = false;
-    c->ctl = ctl;
-    c->ctl_bytes = bytes;
-    c->ctl_rba = rba;
-    c->ctl_region = region;
-    c->lb_error = reinterpret_cast<unsigned *>(ctl + RB_ERR);
-    c->comp_changed = reinterpret_cast<unsigned *>(ctl + RB_FLAGS);
-    c->gate_out = reinterpret_cast<double *>(ctl + RB_LG);
-    c->ctl_claims = reinterpret_cast<uint32_t *>(ctl + rba + FIN_DONE_BYTES);
-    for (int r = 0; r < 3; ++r) {
-        c->ctl_lb[r] = reinterpret_cast<unsigned *>(ctl + rba + FIN_DONE_BYTES + cla + r * region);
-        c->ctl_fresh[r] = true;
-    }
-    c->comp_flags_fresh = true;
+// Begin a chain: its control block, laid out by ctl_layout (control.h).
+static int begin_chain(mm_ctx *c, unsigned nblk, unsigned nblk_kw, const mm_solve_geom *sg) {
+    const CtlLayout lay = ctl_layout(nblk, nblk_kw, sg);
+    char *blk;
+    RET(get_buf(c, "ctl", lay.bytes, &blk));
+    HIPCHK(c, c->ctl.begin(lay, blk, c->stream));
     return MM_OK;
 }
 
@@ -456,7 +377,10 @@ static uint64_t comp_signature(const mm_job *j) {
     return h;
 }
 
-static int stage_compress(mm_ctx *c, const mm_job *j, short2 *const bands[3], const double *tile_e, short2 **q2_out) {
+// pad: a fused timeline's tracks with padding, n_pad {end, end of the last chunk}
+// pairs on the device for comp_trim_kernel (0: none).
+static int stage_compress(mm_ctx *c, const mm_job *j, short2 *const bands[3], const double *tile_e, short2 **q2_out,
+                          const int64_t *pad = nullptr, int n_pad = 0) {
     const int T = j->tile, ch = j->channels, K = j->tiles_per_chunk;
     const int64_t N = j->frames_proc;
     const int64_t G = c->G;
@@ -481,10 +405,8 @@ static int stage_compress(mm_ctx *c, const mm_job *j, short2 *const bands[3], co
     ca.q_out = q2;
     *q2_out = q2;
     double *st, *ends, *luts, *tstc, *descc, *mmax, *mmaxc, *ced, *cedc;
-    uint32_t *claims;
     RET(get_buf(c, "comp_start", (size_t)3 * NS, &st));
     RET(get_buf(c, "comp_end", (size_t)3 * NS, &ends));
-    claims = c->ctl_claims;  // zeroed with the control block (sized by stage_front: claims, then cbtot)
     RET(get_buf(c, "comp_lut", (size_t)3 * 32769, &luts));
     const int64_t NC = nchunks * K;  // compact indices
     RET(get_buf(c, "comp_mmax", (size_t)3 * G, &mmax));
@@ -504,8 +426,7 @@ static int stage_compress(mm_ctx *c, const mm_job *j, short2 *const bands[3], co
     int32_t *se0s;
     RET(get_buf(c, "comp_sdesc", ca.sjump ? (size_t)3 * NS * SREC : 1, &sdesc));
     RET(get_buf(c, "comp_se0", ca.sjump ? (size_t)3 * NS : 1, &se0s));
-    unsigned int *changed = c->comp_changed;  // zeroed with the chain's control words
-    ca.walked = reinterpret_cast<unsigned long long *>(c->ctl + RB_WALKED);
+    ca.walked = c->ctl.dev()->walked;  // (zeroed and read back with the control block, as total / claim / cbtot)
     ca.trace = nullptr;
     if (getenv("MM_FIX_TRACE")) {  // diagnostics: per-walker sweep records, printed by evaluate_chain
         RET(get_buf(c, "comp_trace", (size_t)16 * 3 * NS * 4, &ca.trace));
@@ -515,9 +436,8 @@ static int stage_compress(mm_ctx *c, const mm_job *j, short2 *const bands[3], co
     ca.RP = sg.rows;
     ca.chunk_elems = sg.chunk_plane_bytes / 8;  // SPC / 64 column blocks of 64 x RP
     const int64_t ms_elems = ca.chunk_elems * nchunks;
-    int32_t *cnt, *tot;
+    int32_t *cnt;
     RET(get_buf(c, "comp_cnt", (size_t)3 * G, &cnt));
-    tot = reinterpret_cast<int32_t *>(c->ctl + RB_TOTALS);  // zeroed and read back with the control block
     for (int b = 0; b < 3; ++b) {
         double *msb;
         char nm[16];
@@ -545,7 +465,7 @@ static int stage_compress(mm_ctx *c, const mm_job *j, short2 *const bands[3], co
         ca.rcp_release[b] = 1.0 / j->band[b].release_frames;
         ca.cnt[b] = cnt + (size_t)b * G;
         ca.mmax[b] = mmax + (size_t)b * G;
-        ca.total[b] = tot + (size_t)b * nchunks;
+        ca.total[b] = c->ctl.dev_totals(b);
         ca.rank[b] = ranks + (size_t)b * G;
         ca.nact[b] = nacts + (size_t)b * nchunks;
         ca.tl[b] = tls + (size_t)b * NC;
@@ -556,34 +476,33 @@ static int stage_compress(mm_ctx *c, const mm_job *j, short2 *const bands[3], co
         ca.descc[b] = descc + (size_t)b * DREC * NC;
         ca.start[b] = st + (size_t)b * NS;
         ca.end[b] = ends + (size_t)b * NS;
-        ca.claim[b] = claims + (size_t)b * NS;
+        ca.claim[b] = c->ctl.claims(b);
         ca.sdesc[b] = ca.sjump ? sdesc + (size_t)b * NS * SREC : nullptr;
         ca.se0[b] = ca.sjump ? se0s + (size_t)b * NS : nullptr;
-        ca.cbtot[b] = reinterpret_cast<int32_t *>(claims + (size_t)3 * NS) + (size_t)b * (NS / 64);
+        ca.cbtot[b] = c->ctl.cbtot(b);
     }
     // column block = one workgroup (RMS_TPS x 64 tiles): gathers / stores through LDS
     RET(launch(c, "comp_rms", comp_rms_t_kernel, dim3((unsigned)(NS / 64), 3), dim3(256), 0, ca));
-    if (c->comp_pad_n > 0)  // a timeline: the padding's frames leave the per-chunk statistics
-        RET(launch(c, "comp_trim", comp_trim_kernel, dim3((unsigned)c->comp_pad_n, 3), dim3(64), 0, ca, c->comp_pad));
+    if (n_pad > 0)  // a timeline: the padding's frames leave the per-chunk statistics
+        RET(launch(c, "comp_trim", comp_trim_kernel, dim3((unsigned)n_pad, 3), dim3(64), 0, ca, pad));
     RET(launch(c, "comp_describe", comp_describe_kernel, dim3((unsigned)(NS / 64), 3), dim3(64 * ca.TPS), 0, ca));
     RET(launch(c, "comp_pass0", comp_pass0_kernel, dim3(blocks_for(NS, PASS0_BLOCK), 3), dim3(PASS0_BLOCK), 0, ca));
-    c->comp_on = true;
-    c->ca = ca;
-    c->comp_stamp = 0;
-    c->comp_changed = changed;
-    c->comp_iters = 0;
-    c->comp_pending = 0;
+    Solve &sv = c->comp;
+    sv.on = true;
+    sv.ca = ca;
+    sv.stamp = 0;
+    sv.iters = sv.pending = 0;
     // as many as the last solve on this context needed (+ 1 spare) when this job has
     // the same compressor settings and geometry: a stream of similar jobs queues few
     // idle sweeps and rarely resumes from the host; a job with other settings or
     // another length starts from COMP_SWEEPS again (a P_HOT job after P_FULL ones
     // would otherwise resume from the host)
     const uint64_t sig = comp_signature(j);
-    if (sig != c->comp_sig) {
-        c->comp_queue = 0;
-        c->comp_sig = sig;
+    if (sig != sv.sig) {
+        sv.queue = 0;
+        sv.sig = sig;
     }
-    int sweeps = c->comp_queue > 0 ? c->comp_queue : COMP_SWEEPS;
+    int sweeps = sv.queue > 0 ? sv.queue : COMP_SWEEPS;
     if (const char *e = getenv("MM_COMP_SWEEPS")) sweeps = std::max(1, std::min(16, atoi(e)));  // tests / tuning
     RET(comp_sweeps(c, sweeps));
     RET(comp_back(c));
@@ -597,8 +516,10 @@ static unsigned kw_nblk(const mm_job *j, int64_t G) {
 }
 
 // ------------------------------------------------------------ chain A..C
-// nblk_kw: the blocks of the K-weighting stage that will follow on this line (0: none)
-static int stage_front(mm_ctx *c, const mm_job *j, const void *d_in, unsigned nblk_kw) {
+// nblk_kw: the blocks of the K-weighting stage that will follow on this line (0: none);
+// pad, n_pad: as stage_compress
+static int stage_front(mm_ctx *c, const mm_job *j, const void *d_in, unsigned nblk_kw, const int64_t *pad = nullptr,
+                       int n_pad = 0) {
     mm_job jf;
     if (j->in_kind == MM_IN_I24 || j->in_kind == MM_IN_I32) {
         // 24/32-bit PCM: decoded once for the line (a fused timeline is one run of
@@ -623,15 +544,9 @@ static int stage_front(mm_ctx *c, const mm_job *j, const void *d_in, unsigned nb
     RET(get_buf(c, "q1", TG, &q1));
     const int tpb = LB_THREADS / ch;
     const unsigned nblk = blocks_for(std::max<int64_t>(G, 1), tpb);
-    int64_t nch = 0, spc = 0;
-    if (j->multiband_on) {
-        mm_solve_geom sg;
-        solve_geometry(j, &sg);  // (checked by stage_compress)
-        nch = sg.chunks;
-        spc = sg.cols_per_chunk;
-    }
-    // (each look-back region also holds the K-weighting stage's blocks: sub-tile lanes)
-    RET(setup_control(c, std::max(nblk, nblk_kw), nch, 3 * nch * spc + 3 * nch * spc / 64));  // claim stamps, column-block counts
+    mm_solve_geom sg{};
+    if (j->multiband_on) solve_geometry(j, &sg);  // (checked by stage_compress)
+    RET(begin_chain(c, nblk, nblk_kw, j->multiband_on ? &sg : nullptr));
 
     EqArgs ea{};
     ea.in = j->in_kind == MM_IN_I16 ? nullptr : static_cast<const float *>(d_in);
@@ -736,10 +651,10 @@ static int stage_front(mm_ctx *c, const mm_job *j, const void *d_in, unsigned nb
 
         // --- stage C: 3-band compressor + overlay (AME:207-210)
         short2 *q2;
-        RET(stage_compress(c, j, bands, tile_e, &q2));
+        RET(stage_compress(c, j, bands, tile_e, &q2, pad, n_pad));
         mix = q2;
     } else {
-        c->comp_on = false;
+        c->comp.on = false;
     }
     c->mix = mix;
     c->staged = true;
@@ -756,6 +671,13 @@ struct LineGeom {
     int64_t *bounds = nullptr, *trk_blk = nullptr, *trk_tile0 = nullptr, *trk_end = nullptr;
     int32_t *s0 = nullptr, *s1 = nullptr;
 };
+
+// Frames [lo, hi) of a gating block as the range of the S segments (bounds B[0..S])
+// that begin in it.
+static std::pair<int64_t, int64_t> seg_range(const int64_t *B, int64_t S, int64_t lo, int64_t hi) {
+    return {std::min<int64_t>(std::lower_bound(B, B + S + 1, lo) - B, S),
+            std::min<int64_t>(std::lower_bound(B, B + S + 1, hi) - B, S)};
+}
 
 // A single track's geometry (kept on the context, uploaded only when it changes).
 static int upload_geometry(mm_ctx *c, const mm_job *j, LineGeom *g) {
@@ -774,10 +696,11 @@ static int upload_geometry(mm_ctx *c, const mm_job *j, LineGeom *g) {
     RET(get_buf(c, "gate_s1", (size_t)j->n_blocks, &g->s1));
     if (key == c->geom_cache) return MM_OK;
     std::vector<int32_t> s0((size_t)j->n_blocks), s1((size_t)j->n_blocks);
-    const int64_t *B = j->seg_bounds, S = j->n_segs;
-    for (int64_t b = 0; b < j->n_blocks; ++b) {  // as mm_gate_loudness
-        s0[b] = (int32_t)std::min<int64_t>(std::lower_bound(B, B + S + 1, j->block_lo[b]) - B, S);
-        s1[b] = (int32_t)std::min<int64_t>(std::lower_bound(B, B + S + 1, j->block_hi[b]) - B, S);
+    const int64_t S = j->n_segs;
+    for (int64_t b = 0; b < j->n_blocks; ++b) {
+        const auto r = seg_range(j->seg_bounds, S, j->block_lo[b], j->block_hi[b]);
+        s0[b] = (int32_t)r.first;
+        s1[b] = (int32_t)r.second;
     }
     HIPCHK(c, hipMemcpyAsync(g->bounds, j->seg_bounds, (S + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(g->s0, s0.data(), s0.size() * 4, hipMemcpyHostToDevice, c->stream));
@@ -1052,8 +975,7 @@ static int kweight_energies(mm_ctx *c, const double *carry_in_host, double *seg_
         HIPCHK(c, hipMemcpyAsync(range_end_host, lend, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (seg_host)
         HIPCHK(c, hipMemcpyAsync(seg_host, seg, c->job.n_segs * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    bool conv;
-    return chain_check(c, &conv);
+    return chain_check(c);
 }
 
 // the gate: block energies and levels from the segment energies in parallel (unless
@@ -1105,13 +1027,10 @@ extern "C" int mm_gate_loudness(const mm_job *j, const double *seg_energy, doubl
     if (!j || !seg_energy || !loudness) return MM_ERR_ARG;
     const int64_t nb = j->n_blocks;
     std::vector<double> z((size_t)nb), l((size_t)nb);
-    const int64_t *B = j->seg_bounds;
-    const int64_t S = j->n_segs;
     for (int64_t b = 0; b < nb; ++b) {
-        int64_t s0 = std::lower_bound(B, B + S + 1, j->block_lo[b]) - B;
-        int64_t s1 = std::lower_bound(B, B + S + 1, j->block_hi[b]) - B;
+        const auto r = seg_range(j->seg_bounds, j->n_segs, j->block_lo[b], j->block_hi[b]);
         double acc = 0.0;
-        for (int64_t s = s0; s < s1 && s < S; ++s) acc += seg_energy[s];
+        for (int64_t s = r.first; s < r.second; ++s) acc += seg_energy[s];
         z[b] = j->block_scale * acc;
         l[b] = -0.691 + 10.0 * std::log10(z[b]);
     }
@@ -1140,9 +1059,9 @@ extern "C" int mm_gate_loudness(const mm_job *j, const double *seg_energy, doubl
 // the chain's last finalize launch, which hands the readback area over.
 static int finalize(mm_ctx *c, const mm_job *j, int64_t G, int64_t g_off, double gain, const double *gain_dev,
                     int use_gain, void *d_out, bool tail = false) {
-    c->tail_readback = false;
-    if (G == 0) return MM_OK;
     FinArgs fa{};
+    HIPCHK(c, c->ctl.attach_tail(tail && G > 0 ? &fa : nullptr));
+    if (G == 0) return MM_OK;
     fa.N_proc = j->frames_proc;
     fa.G = G;
     fa.Gs = c->G;
@@ -1155,7 +1074,6 @@ static int finalize(mm_ctx *c, const mm_job *j, int64_t G, int64_t g_off, double
     fa.gain_dev = gain_dev;
     fa.mix = c->mix;
     fa.out = d_out;
-    if (tail) RET(attach_tail(c, fa));
     const size_t lds = (size_t)FIN_TILES * (j->tile + 1) * sizeof(short2);
     if (fa.ch == 2)
         return launch(c, "finalize", finalize_kernel<2>, dim3(blocks_for(G, FIN_TILES)), dim3(256), lds, fa);
@@ -1166,13 +1084,7 @@ static int finalize(mm_ctx *c, const mm_job *j, int64_t G, int64_t g_off, double
 static int stage_chunks(mm_ctx *c, const mm_job *j, const void *d_in) {
     RET(validate(c, j));
     RET(stage_front(c, j, d_in, j->lufs_on ? kw_nblk(j, (j->frames_proc + j->tile - 1) / j->tile) : 0u));
-    for (;;) {
-        bool converged;
-        RET(chain_check(c, &converged));
-        if (converged) return MM_OK;
-        RET(comp_sweeps(c, 8));
-        RET(comp_back(c));
-    }
+    return chain_check(c);
 }
 
 // ------------------------------------------------------------------ units
@@ -1285,10 +1197,10 @@ static int unit_geometry(mm_ctx *c, Unit *p) {
         }
         for (int64_t s = 1; s <= j.n_segs; ++s) bounds.push_back(o + j.seg_bounds[s]);
         tblk[i] = (int64_t)s0.size();
-        const int64_t *B = j.seg_bounds, S = j.n_segs;
-        for (int64_t b = 0; b < j.n_blocks; ++b) {  // as mm_gate_loudness
-            s0.push_back((int32_t)(base + std::min<int64_t>(std::lower_bound(B, B + S + 1, j.block_lo[b]) - B, S)));
-            s1.push_back((int32_t)(base + std::min<int64_t>(std::lower_bound(B, B + S + 1, j.block_hi[b]) - B, S)));
+        for (int64_t b = 0; b < j.n_blocks; ++b) {
+            const auto r = seg_range(j.seg_bounds, j.n_segs, j.block_lo[b], j.block_hi[b]);
+            s0.push_back((int32_t)(base + r.first));
+            s1.push_back((int32_t)(base + r.second));
         }
         tt0[i] = o / T;
         tend[i] = o + j.frames_proc;
@@ -1331,14 +1243,14 @@ static int unit_geometry(mm_ctx *c, Unit *p) {
 static int unit_tail(mm_ctx *c, const Unit &u) {
     const mm_job &j0 = u.J[0];
     const bool fused = u.n > 1, lufs = j0.lufs_on && c->G > 0;
-    // lg[2i] = L, lg[2i+1] = gain: a single track's in the readback area (setup_control)
-    double *lg = c->gate_out;
+    // lg[2i] = L, lg[2i+1] = gain: a single track's in the readback area
+    double *lg = c->ctl.dev()->lg;
     if (fused) RET(get_buf(c, "fz_lg", (size_t)2 * u.n, &lg));
     if (lufs) RET(line_loudness(c, &j0, fused ? u.P : j0.frames_proc, u.geom, lg));
     for (int i = 0; i < u.n; ++i)
         RET(finalize(c, &u.J[i], fused ? u.nch[i] * j0.tiles_per_chunk : c->G, fused ? u.off[i] / j0.tile : 0, 1.0,
                      lufs ? lg + 2 * i + 1 : nullptr, j0.lufs_on, u.out[i], i == u.n - 1));
-    return c->tail_readback ? MM_OK : queue_readback(c);
+    return c->ctl.tail ? MM_OK : queue_readback(c);
 }
 
 // Queue a unit without host round trips: loudness geometry (uploaded first: its
@@ -1355,6 +1267,7 @@ static int unit_enqueue(mm_ctx *c, Unit &u) {
     const mm_job *line = &j0;
     const void *tin = u.in[0];
     mm_job tj;
+    const int64_t *pad = nullptr;
     if (fused) {
         const size_t fb = (size_t)j0.channels * in_sample_bytes(j0.in_kind);
         bool in_place = true;
@@ -1386,35 +1299,23 @@ static int unit_enqueue(mm_ctx *c, Unit &u) {
             int64_t *d;
             RET(get_buf(c, "fz_pad", u.pad.size(), &d));
             HIPCHK(c, hipMemcpyAsync(d, u.pad.data(), u.pad.size() * 8, hipMemcpyHostToDevice, c->stream));
-            c->comp_pad = d;
-            c->comp_pad_n = (int)(u.pad.size() / 2);
+            pad = d;
         }
     }
-    const int rc = stage_front(c, line, tin, lufs ? kw_nblk(&j0, G) : 0u);
-    c->comp_pad_n = 0;
-    RET(rc);
+    RET(stage_front(c, line, tin, lufs ? kw_nblk(&j0, G) : 0u, pad, pad ? (int)(u.pad.size() / 2) : 0));
     return unit_tail(c, u);
 }
 
 // The unit's one sync: checks the compressor's convergence (a rare unconverged
 // solve is extended and the tail re-run) and reads the results.
 static int unit_complete(mm_ctx *c, const Unit &u, mm_result *res) {
-    RbKeep keep;
-    for (;;) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        bool converged;
-        RET(evaluate_chain(c, &converged));
-        if (converged) break;
-        rb_keep(c, keep);
-        RET(comp_sweeps(c, 8));
-        RET(comp_back(c));
-        RET(unit_tail(c, u));
-    }
-    rb_finish(c, keep);
+    RET(solve_to_convergence(c, [&] { return unit_tail(c, u); }));
     if (!res) return MM_OK;
     const mm_job &j0 = u.J[0];
     const bool fused = u.n > 1, lufs = j0.lufs_on && c->G > 0;
-    const double *lg = reinterpret_cast<const double *>(c->rb + RB_LG);
+    const RbHead &rb = c->ctl.head();
+    const Solve &sv = c->comp;
+    const double *lg = rb.lg;
     std::vector<double> l2;
     if (fused && lufs) {  // (only a timeline's L and gains lie outside the readback area)
         double *d;
@@ -1423,24 +1324,21 @@ static int unit_complete(mm_ctx *c, const Unit &u, mm_result *res) {
         HIPCHK(c, hipMemcpy(l2.data(), d, l2.size() * sizeof(double), hipMemcpyDeviceToHost));
         lg = l2.data();
     }
-    const int64_t nchk = comp_chunks(c), CF = (int64_t)j0.tile * j0.tiles_per_chunk;
-    const int32_t *tot = reinterpret_cast<const int32_t *>(c->rb + RB_TOTALS);
-    const int64_t walked = c->comp_on ? (int64_t) * reinterpret_cast<const unsigned long long *>(c->rb + RB_WALKED) : 0;
-    const int64_t jumped = c->comp_on ? (int64_t) * reinterpret_cast<const unsigned long long *>(c->rb + RB_WALKED + 8) : 0;
+    const int64_t nchk = c->ctl.lay.chunks, CF = (int64_t)j0.tile * j0.tiles_per_chunk;
     for (int i = 0; i < u.n; ++i) {
         mm_result &r = res[i];
         r.loudness = j0.lufs_on ? (lufs ? lg[2 * i] : -INFINITY) : NAN;  // no frames: pyloudnorm raised earlier
         r.gain_linear = j0.lufs_on ? (lufs ? lg[2 * i + 1] : INFINITY) : 1.0;
         r.frames_out = u.J[i].frames_proc;
-        r.comp_iters = c->comp_iters;  // one solve for the whole unit
+        r.comp_iters = sv.iters;  // one solve for the whole unit
         r.comp_active = 0;             // summed over the track's own chunks (no compressor: no counts)
-        for (int b = 0; b < 3 && c->comp_on; ++b)
+        for (int b = 0; b < 3 && sv.on; ++b)
             for (int64_t k = fused ? u.off[i] / CF : 0; k < (fused ? u.off[i + 1] / CF : nchk); ++k)
-                r.comp_active += tot[b * nchk + k];
+                r.comp_active += c->ctl.totals(b, k);
         // the unit's solve statistics are reported once, on its first track (sums over
         // a batch's results then count every unit once)
-        r.comp_walked = i == 0 ? walked : 0;
-        r.comp_jumped = i == 0 ? jumped : 0;
+        r.comp_walked = i == 0 && sv.on ? (int64_t)rb.walked[0] : 0;
+        r.comp_jumped = i == 0 && sv.on ? (int64_t)rb.walked[1] : 0;
     }
     return MM_OK;
 }
@@ -1581,7 +1479,7 @@ int mm_destroy(mm_ctx *c) {
         if (c->pin[b]) hipHostFree(c->pin[b]);
         if (c->pin_ev[b]) hipEventDestroy(c->pin_ev[b]);
     }
-    if (c->rb) hipHostFree(c->rb);
+    c->ctl.free();
     for (mm_ctx *k : c->children) mm_destroy(k);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
@@ -1704,14 +1602,6 @@ int mm_hop_energies(mm_ctx *c, const double *carry_in_host, double *seg_energy_h
     return kweight_energies(c, carry_in_host, seg_energy_host, nullptr);
 }
 
-// Time-sharded loudness without a host round trip for the energies (VERDICT r03
-// item 7): this rank's per-segment K-weighted energies go straight into a zeroed
-// device vector of the whole track's segments at seg_offset (a rank's segments are
-// consecutive global segments), ONE RCCL sum all-reduce runs in place on the
-// context's stream (when a communicator is set up), the whole track's gating runs
-// on the device (gate_kernel over the given block -> segment ranges), and finalize
-// reads the gain from device memory.  One host synchronisation before (the
-// envelope solve's convergence check, as mm_hop_energies) and one after (L).
 // Time-sharded loudness with the energy vector in HBM, in three steps a caller can
 // compose with any collective between them (the library's communicator, or
 // torch.distributed over the same device buffer):
@@ -1736,9 +1626,7 @@ int mm_shard_energies_device(mm_ctx *c, const double *carry_in_host, int64_t n_g
         HIPCHK(c, hipMemcpyAsync(d_full + seg_offset, seg, (size_t)nl * sizeof(double), hipMemcpyDeviceToDevice,
                                  c->stream));
     }
-    bool conv;
-    RET(chain_check(c, &conv));  // (synchronises the stream: d_full is complete on return)
-    return MM_OK;
+    return chain_check(c);  // (synchronises the stream: d_full is complete on return)
 }
 
 int mm_gate_finalize_device(mm_ctx *c, const double *d_full, int64_t n_global_segs, int64_t n_blocks,

@@ -576,9 +576,9 @@ int mm_op_compress_bands(mm_ctx *c, const mm_job *j, const int16_t *lo, const in
     c->G = G;
     c->job = *j;
     c->staged = false;
-    mm_solve_geom sg;
+    mm_solve_geom sg{};
     solve_geometry(j, &sg);  // (checked by stage_compress)
-    RET(setup_control(c, blocks_for(G, LB_THREADS / ch), sg.chunks, 3 * sg.chunks * sg.cols_per_chunk * 65 / 64));
+    RET(begin_chain(c, blocks_for(G, LB_THREADS / ch), 0, &sg));
     const size_t bytes = (size_t)N * ch * 2;
     char *din;
     RET(get_buf(c, "host_in", 3 * bytes, &din));
@@ -607,13 +607,7 @@ int mm_op_compress_bands(mm_ctx *c, const mm_job *j, const int16_t *lo, const in
     RET(stage_compress(c, j, bands, tile_e, &q2));
     c->mix = q2;
     c->staged = true;
-    for (;;) {
-        bool converged;
-        RET(chain_check(c, &converged));
-        if (converged) break;
-        RET(comp_sweeps(c, 8));
-        RET(comp_back(c));
-    }
+    RET(chain_check(c));
     return mm_read_mix(c, out);
 }
 
