@@ -444,7 +444,9 @@ int mm_master_wav(mm_ctx *ctx, const mm_job *job, const char *in_path, const cha
 
 /* ---- staged entry points (time-sharded multi-GPU, parity probes) -------- */
 /* Run AME:48-80 for this job's chunks into the context's int16 mix buffer and
- * the K-weighting per-tile aggregates (state carry-in assumed 0). */
+ * the K-weighting per-tile aggregates (state carry-in assumed 0).  The context
+ * copies the job's seg_bounds, block_lo and block_hi: the later staged calls read
+ * the copies, so the job's arrays need not outlive this call. */
 int mm_stage_chunks(mm_ctx *ctx, const mm_job *job, const void *d_in);
 /* K-weighting end state of this job's range from a zero start: dim doubles. */
 int mm_kweight_range_end(mm_ctx *ctx, double *end_state_host);

@@ -1,7 +1,7 @@
 // context.h — the library's context (mm_ctx: stream, device buffers, the chain's
-// control block (control.h) and cached tables) and the helpers every host file uses:
-// errors, device buffers, the timed launch.  Included by mastering.hip after the
-// kernels and control.h.
+// control block (control.h), the loudness tail's state (loudness.h) and cached
+// tables) and the helpers every host file uses: errors, device buffers, the timed
+// launch.  Included by mastering.hip after the kernels, control.h and loudness.h.
 #pragma once
 
 namespace {
@@ -40,19 +40,15 @@ struct mm_ctx {
     hipStream_t stream = nullptr;
     char err[512] = {0};
     std::map<std::string, DevBuf> bufs;
-    // staged job geometry (mm_stage_chunks -> mm_hop_energies / mm_finalize)
+    // staged job geometry (mm_stage_chunks -> mm_hop_energies / mm_finalize; the job's
+    // loudness arrays are then loud's copies)
     bool staged = false;
     mm_job job{};
     int64_t G = 0;
     short2 *mix = nullptr;
     ChainCtl ctl;  // the chain's control block and its readback (control.h)
     Solve comp;    // the envelope solve queued on it
-    std::vector<int64_t> geom_cache;    // loudness geometry already on the device (upload_geometry)
-    // exact block energies (kw_blocks_kernel): per block its first frame and program
-    int64_t *kb_lo = nullptr;
-    int32_t *kb_n = nullptr, *kb_prog_of = nullptr, *kb_prog = nullptr;
-    std::vector<int64_t> kb_cache;      // block geometry the programs on the device were built for
-    int kb_nvals = 0, kb_pints = 0;     // the largest program's values and ints (kw_blocks' LDS)
+    Loudness loud;  // what the loudness tail keeps: block programs, segment geometry, the staged job's (loudness.h)
     // timing
     bool timing = false;
     std::vector<PendingEvent> pending;

@@ -15,6 +15,7 @@
 // The reductions over blocks are tree-ordered (the result differs from numpy's
 // pairwise mean in the last bits only: ~1e-16 of the gain).
 #include "common.h"
+#include "loudness.h"
 
 namespace mm {
 
@@ -42,7 +43,7 @@ constexpr int GATE_THREADS = 1024;
 // r[j] over elements j, j+8, ... combined ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then
 // the m % 8 tail in order; else pairwise(n2) + pairwise(m - n2), n2 = m/2 - (m/2)%8.
 // The host turns that recursion into a program per distinct block length
-// (mastering.hip pw_build, checked against np.sum on the CPU through mm_np_sum_f32):
+// (loudness.h pw_build, checked against np.sum on the CPU through mm_np_sum_f32):
 //   ints [0..4]  nleaves, nnodes, nlevels, nchunks, root value (-1: empty sum)
 //   then chunk_leaf[nchunks + 1], leaf_off[nleaves], leaf_len[nleaves],
 //   node_a[nnodes], node_b[nnodes], level_node[nlevels + 1]
@@ -60,9 +61,7 @@ struct KbArgs {
     double *zl;               // [2 n_blocks]: z_j, then l_j (read by gate_kernel)
     int stage_floats, nvals, pints;  // dynamic LDS layout (kb_lds_bytes: nvals = both value buffers), pints % 4 == 0
 };
-constexpr int KB_CHUNK = 8192;   // numpy's reduction buffer (elements)
-constexpr int KB_VMAX = 1536;    // leaves + nodes of one block (76 800 frames at 192 kHz: 1199)
-constexpr int KB_PMAX = 2560;    // ints of one program (192 kHz: 2430); programs start 16-byte aligned
+// (KB_CHUNK, KB_VMAX, KB_PMAX: loudness.h, with the program's builder)
 constexpr int KB_THREADS = 256;
 constexpr int KB_LD = 9;         // 16-byte loads per thread per chunk: padded tile quads of the tiles a
                                  // chunk spans, (8191 / T + 2) * ceil(T / 4) <= 2304 (host-checked)

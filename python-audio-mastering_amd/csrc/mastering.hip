@@ -1,10 +1,12 @@
 // mastering.hip — host side of the C-ABI (include/mastering.h), one translation
 // unit: the launch sequence of the chain (a unit of n >= 1 tracks between two
-// syncs), loudness gating, the batch scheduler and the staged / time-sharded entry
-// points.  The chain's control block is control.h, the context that holds it
-// context.h, followed by decode.hip (24/32-bit PCM input);
-// wav.hip, comm.hip, ops.hip, then pcm16.h, meter.hip, ceiling.hip and resample.hip (with
-// mm_master* / mm_deliver*: a master call with or without a delivery) come at the end.
+// syncs), the batch scheduler and the context entry points.  The chain's control
+// block is control.h, the loudness tail's state loudness.h, the context that holds
+// both context.h, followed by decode.hip (24/32-bit PCM input).  ops.hip (the
+// per-stage operators) and loudness.hip (the loudness tail, its operator and the
+// time-sharded entry points) follow the chain, before the units that call
+// line_loudness; wav.hip, comm.hip, then pcm16.h, meter.hip, ceiling.hip and resample.hip
+// (with mm_master* / mm_deliver*: a master call with or without a delivery) come at the end.
 #include <rccl/rccl.h>
 
 #include <algorithm>
@@ -25,6 +27,7 @@
 using namespace mm;
 
 #include "control.h"
+#include "loudness.h"
 #include "context.h"
 #include "decode.hip"
 
@@ -661,400 +664,6 @@ static int stage_front(mm_ctx *c, const mm_job *j, const void *d_in, unsigned nb
     return MM_OK;
 }
 
-// ------------------------------------------------------------ K-weighting
-// Loudness geometry of a line on the device: segment bounds, every gating block as a
-// segment range, and for a timeline of several tracks (n_trk > 0) each track's
-// first tile, the end of its real frames and its first gating block.
-struct LineGeom {
-    int n_trk = 0;
-    int64_t n_segs = 0, n_blocks = 0;
-    int64_t *bounds = nullptr, *trk_blk = nullptr, *trk_tile0 = nullptr, *trk_end = nullptr;
-    int32_t *s0 = nullptr, *s1 = nullptr;
-};
-
-// Frames [lo, hi) of a gating block as the range of the S segments (bounds B[0..S])
-// that begin in it.
-static std::pair<int64_t, int64_t> seg_range(const int64_t *B, int64_t S, int64_t lo, int64_t hi) {
-    return {std::min<int64_t>(std::lower_bound(B, B + S + 1, lo) - B, S),
-            std::min<int64_t>(std::lower_bound(B, B + S + 1, hi) - B, S)};
-}
-
-// A single track's geometry (kept on the context, uploaded only when it changes).
-static int upload_geometry(mm_ctx *c, const mm_job *j, LineGeom *g) {
-    std::vector<int64_t> key;
-    key.reserve((size_t)(j->n_segs + 3 + 2 * j->n_blocks));
-    key.push_back(j->n_segs);
-    key.insert(key.end(), j->seg_bounds, j->seg_bounds + j->n_segs + 1);
-    key.push_back(j->n_blocks);
-    key.insert(key.end(), j->block_lo, j->block_lo + j->n_blocks);
-    key.insert(key.end(), j->block_hi, j->block_hi + j->n_blocks);
-    *g = LineGeom{};
-    g->n_segs = j->n_segs;
-    g->n_blocks = j->n_blocks;
-    RET(get_buf(c, "kw_bounds", (size_t)j->n_segs + 1, &g->bounds));
-    RET(get_buf(c, "gate_s0", (size_t)j->n_blocks, &g->s0));
-    RET(get_buf(c, "gate_s1", (size_t)j->n_blocks, &g->s1));
-    if (key == c->geom_cache) return MM_OK;
-    std::vector<int32_t> s0((size_t)j->n_blocks), s1((size_t)j->n_blocks);
-    const int64_t S = j->n_segs;
-    for (int64_t b = 0; b < j->n_blocks; ++b) {
-        const auto r = seg_range(j->seg_bounds, S, j->block_lo[b], j->block_hi[b]);
-        s0[b] = (int32_t)r.first;
-        s1[b] = (int32_t)r.second;
-    }
-    HIPCHK(c, hipMemcpyAsync(g->bounds, j->seg_bounds, (S + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(g->s0, s0.data(), s0.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(g->s1, s1.data(), s1.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // host vectors are transient
-    c->geom_cache = key;
-    return MM_OK;
-}
-
-// ---- numpy's float32 np.sum as a program (gate.hip kw_blocks_kernel) ----------
-// The reduction tree of np.sum over n contiguous float32 values: 8192-element
-// buffer chunks summed in order, each chunk numpy's pairwise recursion (leaves of
-// <= 128 elements).  Serialised as gate.hip's program layout.
-struct PwBuild {
-    std::vector<int32_t> loff, llen;        // leaves in order
-    std::vector<int32_t> na, nb, nh;        // nodes: operands (>= 0 leaf, < 0 node ~k) and height
-    std::vector<int32_t> chunk_leaf;
-};
-static int32_t pw_node(PwBuild &b, int32_t va, int32_t vb, int32_t ha, int32_t hb, int32_t *h) {
-    b.na.push_back(va);
-    b.nb.push_back(vb);
-    *h = std::max(ha, hb) + 1;
-    b.nh.push_back(*h);
-    return ~(int32_t)(b.na.size() - 1);
-}
-static int32_t pw_rec(PwBuild &b, int32_t off, int32_t m, int32_t *h) {
-    if (m <= 128) {  // numpy: m < 8 sequential, else eight accumulators + tail
-        b.loff.push_back(off);
-        b.llen.push_back(m);
-        *h = 0;
-        return (int32_t)b.loff.size() - 1;
-    }
-    int32_t n2 = m / 2;
-    n2 -= n2 % 8;
-    int32_t ha, hb;
-    const int32_t va = pw_rec(b, off, n2, &ha);
-    const int32_t vb = pw_rec(b, off + n2, m - n2, &hb);
-    return pw_node(b, va, vb, ha, hb, h);
-}
-// appends the program of np.sum over n elements to `out`
-static void pw_build(int64_t n, std::vector<int32_t> &out) {
-    PwBuild b;
-    int32_t acc = 0, hacc = 0;
-    const int64_t nch = (n + KB_CHUNK - 1) / KB_CHUNK;
-    for (int64_t c = 0; c < nch; ++c) {
-        b.chunk_leaf.push_back((int32_t)b.loff.size());
-        int32_t h;
-        const int32_t v = pw_rec(b, (int32_t)(c * KB_CHUNK), (int32_t)std::min<int64_t>(KB_CHUNK, n - c * KB_CHUNK), &h);
-        if (c == 0) {  // res = 0 + pairwise(chunk 0): exact (sums of squares are >= +0)
-            acc = v;
-            hacc = h;
-        } else {
-            acc = pw_node(b, acc, v, hacc, h, &hacc);
-        }
-    }
-    b.chunk_leaf.push_back((int32_t)b.loff.size());
-    const int32_t nl = (int32_t)b.loff.size(), nn = (int32_t)b.na.size();
-    // nodes sorted by height (stable): a level reads only lower ones
-    std::vector<int32_t> order(nn), pos(nn);
-    for (int32_t k = 0; k < nn; ++k) order[k] = k;
-    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return b.nh[x] < b.nh[y]; });
-    for (int32_t k = 0; k < nn; ++k) pos[order[k]] = k;
-    auto vidx = [&](int32_t v) { return v >= 0 ? v : nl + pos[~v]; };
-    const int32_t nlev = nn ? b.nh[order[nn - 1]] : 0;
-    out.push_back(nl);
-    out.push_back(nn);
-    out.push_back(nlev);
-    out.push_back((int32_t)nch);
-    out.push_back(n == 0 ? -1 : vidx(acc));
-    out.insert(out.end(), b.chunk_leaf.begin(), b.chunk_leaf.end());
-    out.insert(out.end(), b.loff.begin(), b.loff.end());
-    out.insert(out.end(), b.llen.begin(), b.llen.end());
-    for (int32_t k = 0; k < nn; ++k) out.push_back(vidx(b.na[order[k]]));
-    for (int32_t k = 0; k < nn; ++k) out.push_back(vidx(b.nb[order[k]]));
-    for (int32_t L = 0, k = 0; L <= nlev; ++L) {  // level L: nodes of height L + 1
-        while (k < nn && b.nh[order[k]] <= L) ++k;
-        out.push_back(k);
-    }
-}
-// The program evaluated on the host with the device's operation order (CPU check
-// against np.sum: mm_np_sum_f32).
-static float pw_eval(const int32_t *P, const float *x) {
-    const int nl = P[0], nn = P[1], nch = P[3], root = P[4];
-    const int32_t *loff = P + 5 + nch + 1, *llen = loff + nl, *na = llen + nl, *nb = na + nn;
-    std::vector<float> val((size_t)nl + nn);
-    for (int li = 0; li < nl; ++li) {
-        const float *e = x + loff[li];
-        const int len = llen[li];
-        float res;
-        if (len < 8) {
-            res = e[0];
-            for (int i = 1; i < len; ++i) res = res + e[i];
-        } else {
-            float r[8];
-            for (int q = 0; q < 8; ++q) r[q] = e[q];
-            int i = 8;
-            for (; i < len - (len & 7); i += 8)
-                for (int q = 0; q < 8; ++q) r[q] = r[q] + e[i + q];
-            res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-            for (; i < len; ++i) res = res + e[i];
-        }
-        val[li] = res;
-    }
-    for (int k = 0; k < nn; ++k) val[nl + k] = val[na[k]] + val[nb[k]];
-    return root < 0 ? 0.0f : val[root];
-}
-
-// Per-block programs on the device: blocks [lo_b, hi_b) of the line; one program
-// per distinct length (the clamped last blocks of a track differ).  The blocks the
-// device already holds are recognised without building anything: a unit calls this
-// before its first launch, on the step's critical path.
-static int kb_upload(mm_ctx *c, const int64_t *lo, const int64_t *hi, size_t nb) {
-    if (c->kb_prog && c->kb_cache.size() == 2 * nb && std::equal(lo, lo + nb, c->kb_cache.begin()) &&
-        std::equal(hi, hi + nb, c->kb_cache.begin() + nb))
-        return MM_OK;
-    std::vector<int64_t> key(lo, lo + nb), n(nb);
-    key.insert(key.end(), hi, hi + nb);
-    for (size_t b = 0; b < nb; ++b) n[b] = hi[b] - lo[b];
-    RET(get_buf(c, "kb_lo", std::max<size_t>(nb, 1), &c->kb_lo));
-    RET(get_buf(c, "kb_prog_of", std::max<size_t>(nb, 1), &c->kb_prog_of));
-    RET(get_buf(c, "kb_n", std::max<size_t>(nb, 1), &c->kb_n));
-    std::map<int64_t, int32_t> at;
-    std::vector<int32_t> prog, of(nb), n32(nb);
-    int nvals = 1, pints = 4;
-    for (size_t b = 0; b < nb; ++b) {
-        if (n[b] < 0 || n[b] > 16 * KB_CHUNK) return set_err(c, MM_ERR_ARG, "loudness block of %lld frames", (long long)n[b]);
-        auto it = at.find(n[b]);
-        if (it == at.end()) {
-            const int32_t o = (int32_t)prog.size();
-            pw_build(n[b], prog);
-            if (prog[o] + prog[o + 1] > KB_VMAX || (int64_t)prog.size() - o > KB_PMAX)
-                return set_err(c, MM_ERR_ARG, "loudness block program too large");
-            while (prog.size() % 4) prog.push_back(0);  // (16-byte aligned programs: int4 copies)
-            nvals = std::max(nvals, prog[o] + prog[o + 1]);
-            pints = std::max(pints, (int)(prog.size() - o));
-            it = at.emplace(n[b], o).first;
-        }
-        of[b] = it->second;
-        n32[b] = (int32_t)n[b];
-    }
-    c->kb_prog = nullptr;  // (get_buf may move it: re-fetched below)
-    prog.resize(prog.size() + pints, 0);  // every block copies the largest program's length
-    RET(get_buf(c, "kb_prog", prog.size(), &c->kb_prog));
-    if (nb) {
-        HIPCHK(c, hipMemcpyAsync(c->kb_lo, lo, nb * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->kb_prog_of, of.data(), nb * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->kb_n, n32.data(), nb * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->kb_prog, prog.data(), prog.size() * 4, hipMemcpyHostToDevice, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // host vectors are transient
-    c->kb_cache = key;
-    c->kb_nvals = nvals;
-    c->kb_pints = pints;
-    return MM_OK;
-}
-
-// The K-weighting kernel's arguments for the staged mix of G tiles holding `frames`
-// frames: one lane per sub-tile of kweight.tile frames (design.kweight_sub), `sub`
-// per tile.  The caller adds its mode's outputs and, for a timeline, the track tables.
-static KwArgs kw_args(const mm_ctx *c, const mm_job *j, int64_t frames, int64_t G) {
-    KwArgs ka{};
-    ka.sub = j->tile / j->kweight.tile;
-    ka.N_proc = frames;
-    ka.G = G * ka.sub;
-    ka.T = j->kweight.tile;
-    ka.Gt = G;
-    ka.ch = j->channels;
-    for (int s_ = 0; s_ < 2; ++s_)
-        for (int k = 0; k < 5; ++k) ka.sos[s_][k] = j->kweight.sos[s_][k];
-    ka.mix = reinterpret_cast<const int16_t *>(c->mix);
-    return ka;
-}
-
-// Queue the K-weighting of the staged line (SQ: pass 2 writes the f32 squares, else
-// the segment partials); a time-sharded range starts from `carry_in_host`.
-template <bool SQ>
-static int kweight_run(mm_ctx *c, const mm_job *j, const KwArgs &ka, const double *carry_in_host = nullptr) {
-    LbArgs lb{};
-    RET(upload_tables(c, "kweight", j->kweight, lb));
-    const unsigned nblk = blocks_for(ka.G, LB_THREADS);
-    RET(lb_prepare(c, nblk, 1, lb, 2));
-    if (carry_in_host) {
-        double *init;
-        RET(get_buf(c, "kw_init", 8, &init));
-        HIPCHK(c, hipMemcpyAsync(init, carry_in_host, 4 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));  // pageable source
-        lb.init = init;
-    }
-    return launch(c, "kweight", kweight_kernel<SQ>, dim3(nblk), dim3(LB_THREADS), lb_lds_bytes<4, 1>(), ka, lb);
-}
-
-// Segment energies of a line (round 5's loudness, and the time-sharded ranks'):
-// K-weighting + f64 energies per segment of `g`.  Returns the device segment-energy
-// vector; `line_end` receives the state after the last frame when requested.
-static int kweight_segments(mm_ctx *c, const mm_job *j, int64_t frames, const LineGeom &g,
-                            const double *carry_in_host, double *line_end, double **seg_out) {
-    KwArgs ka = kw_args(c, j, frames, c->G);
-    double *seg;
-    RET(get_buf(c, "kw_part", (size_t)std::max<int64_t>(ka.G, 1) * 2, &ka.part));
-    RET(get_buf(c, "kw_part_seg", (size_t)std::max<int64_t>(ka.G, 1), &ka.part_seg));
-    RET(get_buf(c, "kw_seg", (size_t)g.n_segs, &seg));
-    ka.n_segs = g.n_segs;
-    ka.seg_bounds = g.bounds;
-    ka.line_end = line_end;
-    ka.n_trk = g.n_trk;
-    ka.trk_tile0 = g.trk_tile0;
-    ka.trk_end = g.trk_end;
-    RET(kweight_run<false>(c, j, ka, carry_in_host));
-    RET(launch(c, "seg_reduce", seg_reduce_kernel, dim3(blocks_for(g.n_segs, 4)), dim3(256), 0, ka, seg));  // wave per segment
-    *seg_out = seg;
-    return MM_OK;
-}
-
-// The staged job's segment energies (time-sharded ranks: carry-in state, range end state).
-static int kweight_staged(mm_ctx *c, const double *carry_in_host, double *line_end, double **seg_out) {
-    LineGeom g;
-    RET(upload_geometry(c, &c->job, &g));
-    return kweight_segments(c, &c->job, c->job.frames_proc, g, carry_in_host, line_end, seg_out);
-}
-
-// The exact loudness of a line (single track or fused timeline, AME:212-218): the
-// K-weighting in lfilter's order writing np.square's f32 values, then pyloudnorm's
-// block energies in numpy's reduction order (kw_blocks_kernel) into zl [2 nb].
-// The block programs must be on the device (kb_upload) before this is queued.
-static int kweight_exact(mm_ctx *c, const mm_job *j, int64_t frames, const LineGeom &g, double **zl_out) {
-    const int64_t G = c->G, nb = g.n_blocks;
-    float *sq;
-    double *zl;
-    const int Tt = j->tile, TP = (Tt + 3) / 4 * 4;  // padded tile stride (16-byte stores and loads)
-    if (((KB_CHUNK - 1) / Tt + 2) * (TP / 4) > KB_LD * KB_THREADS)
-        return set_err(c, MM_ERR_ARG, "tile of %d frames: the loudness block loads do not cover a chunk", Tt);
-    RET(get_buf(c, "kw_sq", (size_t)(G * TP), &sq));
-    RET(get_buf(c, "gate_zl", (size_t)std::max<int64_t>(2 * nb, 2), &zl));
-    KwArgs ka = kw_args(c, j, frames, G);
-    ka.n_trk = g.n_trk;
-    ka.trk_tile0 = g.trk_tile0;
-    ka.trk_end = g.trk_end;
-    ka.sq = sq;
-    ka.sq_tp = TP;
-    RET(kweight_run<true>(c, j, ka));
-    if (nb > 0) {
-        KbArgs kb{};
-        kb.sq = sq;
-        kb.T = Tt;
-        kb.TP = TP;
-        kb.n_blocks = nb;
-        kb.blk_lo = c->kb_lo;
-        kb.blk_prog = c->kb_prog_of;
-        kb.blk_n = c->kb_n;
-        kb.prog = c->kb_prog;
-        kb.scale = (float)j->block_scale;  // Python float * np.float32: the constant rounded to f32 (NEP 50)
-        kb.zl = zl;
-        kb.stage_floats = ((KB_CHUNK - 1) / Tt + 2) * TP;  // the padded tile runs a chunk can span
-        kb.nvals = 2 * c->kb_nvals;  // (two value buffers)
-        kb.pints = c->kb_pints;
-        const size_t lds = (size_t)kb_lds_bytes(kb.stage_floats, kb.nvals, kb.pints);
-        // persistent: as many workgroups as fit at once (a multiple of 8: the XCD-aware block mapping)
-        const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(4, (160 * 1024) / (int64_t)(lds + 64)));  // (and VGPRs)
-        const unsigned grid = (unsigned)std::min<int64_t>((nb + 7) / 8 * 8, (int64_t)c->n_cus * per_cu / 8 * 8);
-        RET(launch(c, "kw_blocks", kw_blocks_kernel, dim3(std::max(grid, 8u)), dim3(KB_THREADS), lds, kb));
-    }
-    *zl_out = zl;
-    return MM_OK;
-}
-
-// Host-returning variant (time-sharded ranks: carry-in state, range end state).
-static int kweight_energies(mm_ctx *c, const double *carry_in_host, double *seg_host, double *range_end_host) {
-    double *lend, *seg;
-    RET(get_buf(c, "kw_lend", 8, &lend));
-    RET(kweight_staged(c, carry_in_host, range_end_host ? lend : nullptr, &seg));
-    if (range_end_host)
-        HIPCHK(c, hipMemcpyAsync(range_end_host, lend, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (seg_host)
-        HIPCHK(c, hipMemcpyAsync(seg_host, seg, c->job.n_segs * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    return chain_check(c);
-}
-
-// the gate: block energies and levels from the segment energies in parallel (unless
-// ga.zl already holds them: the exact path), then one workgroup per track
-static int gate_launch(mm_ctx *c, GateArgs ga, unsigned n_tracks) {
-    if (!ga.zl) {
-        RET(get_buf(c, "gate_zl", (size_t)(2 * ga.n_blocks), &ga.zl));
-        RET(launch(c, "gate_blocks", gate_blocks_kernel, dim3(blocks_for(ga.n_blocks, GATE_BLK_THREADS)),
-                   dim3(GATE_BLK_THREADS), 0, ga));
-    }
-    return launch(c, "gate", gate_kernel, dim3(n_tracks), dim3(GATE_THREADS), 0, ga);
-}
-
-// Loudness and gain of every track of the staged line on the device (no host round
-// trip) into out[2i] = L, out[2i+1] = gain: exactly pyloudnorm's block energies, or
-// with MM_LOUDNESS_SEGMENTS round 5's f64 segment energies (A/B builds).  The
-// line's geometry must be on the device (unit_geometry) before this is queued.
-static int line_loudness(mm_ctx *c, const mm_job *j, int64_t frames, const LineGeom &g, double *out) {
-    GateArgs ga{};
-    ga.n_blocks = g.n_blocks;
-    ga.target = j->lufs_target;
-    ga.out = out;
-    ga.trk_blk = g.trk_blk;
-    if (getenv("MM_LOUDNESS_SEGMENTS")) {
-        double *seg;
-        RET(kweight_segments(c, j, frames, g, nullptr, nullptr, &seg));
-        ga.blk_s0 = g.s0;
-        ga.blk_s1 = g.s1;
-        ga.seg = seg;
-        ga.scale = j->block_scale;
-    } else {
-        RET(kweight_exact(c, j, frames, g, &ga.zl));
-    }
-    return gate_launch(c, ga, (unsigned)std::max(g.n_trk, 1));
-}
-
-// numpy's float32 np.sum over x[0..n) evaluated on the host through the same
-// program the device runs for pyloudnorm's block energies (CPU check of pw_build).
-extern "C" int mm_np_sum_f32(const float *x, int64_t n, float *out) {
-    if (!out || n < 0 || (n > 0 && !x) || n > 16 * KB_CHUNK) return MM_ERR_ARG;
-    std::vector<int32_t> prog;
-    pw_build(n, prog);
-    *out = pw_eval(prog.data(), x);
-    return MM_OK;
-}
-
-// pyloudnorm 0.1.1 integrated_loudness gating (mono, G=1), restated.
-extern "C" int mm_gate_loudness(const mm_job *j, const double *seg_energy, double *loudness) {
-    if (!j || !seg_energy || !loudness) return MM_ERR_ARG;
-    const int64_t nb = j->n_blocks;
-    std::vector<double> z((size_t)nb), l((size_t)nb);
-    for (int64_t b = 0; b < nb; ++b) {
-        const auto r = seg_range(j->seg_bounds, j->n_segs, j->block_lo[b], j->block_hi[b]);
-        double acc = 0.0;
-        for (int64_t s = r.first; s < r.second; ++s) acc += seg_energy[s];
-        z[b] = j->block_scale * acc;
-        l[b] = -0.691 + 10.0 * std::log10(z[b]);
-    }
-    double sum = 0.0;
-    int64_t cnt = 0;
-    for (int64_t b = 0; b < nb; ++b)
-        if (l[b] >= -70.0) {
-            sum += z[b];
-            ++cnt;
-        }
-    double mean_abs = cnt ? sum / (double)cnt : NAN;
-    double gamma_r = -0.691 + 10.0 * std::log10(mean_abs) - 10.0;
-    sum = 0.0;
-    cnt = 0;
-    for (int64_t b = 0; b < nb; ++b)
-        if (l[b] > gamma_r && l[b] > -70.0) {
-            sum += z[b];
-            ++cnt;
-        }
-    double zavg = cnt ? sum / (double)cnt : 0.0;  // np.nan_to_num(mean([])) == 0
-    *loudness = -0.691 + 10.0 * std::log10(zavg);
-    return MM_OK;
-}
-
 // One track of the staged mix to its output: G tiles from tile g_off on.  `tail`:
 // the chain's last finalize launch, which hands the readback area over.
 static int finalize(mm_ctx *c, const mm_job *j, int64_t G, int64_t g_off, double gain, const double *gain_dev,
@@ -1080,12 +689,18 @@ static int finalize(mm_ctx *c, const mm_job *j, int64_t G, int64_t g_off, double
     return launch(c, "finalize", finalize_kernel<1>, dim3(blocks_for(G, FIN_TILES)), dim3(256), lds, fa);
 }
 
-// Stage the chunk chain of a range (time-sharded ranks) to convergence.
+// Stage the chunk chain of a range (time-sharded ranks) to convergence.  The staged
+// job outlives this call, so its loudness arrays become the library's copies.
 static int stage_chunks(mm_ctx *c, const mm_job *j, const void *d_in) {
     RET(validate(c, j));
     RET(stage_front(c, j, d_in, j->lufs_on ? kw_nblk(j, (j->frames_proc + j->tile - 1) / j->tile) : 0u));
+    c->loud.own_job(&c->job);
     return chain_check(c);
 }
+
+// the per-stage operators (AME:117-227 one at a time), then the loudness tail
+#include "ops.hip"
+#include "loudness.hip"
 
 // ------------------------------------------------------------------ units
 // What a context runs between two syncs: n >= 1 tracks with the same settings,
@@ -1112,7 +727,7 @@ struct Unit {
     std::vector<int64_t> off;  // [n + 1] first timeline frame of each track (and the end)
     std::vector<int64_t> nch;  // [n] chunks of each track
     int64_t P = 0;             // timeline frames
-    LineGeom geom;             // loudness geometry on the device (unit_geometry)
+    TrackTable geom;           // gating blocks and track table on the device (unit_geometry)
     std::vector<int64_t> pad;  // {track end, end of its last chunk} of the tracks that end inside a chunk
 };
 
@@ -1168,71 +783,39 @@ static bool unit_layout(Unit *p) {
 
 // Loudness geometry of the unit's line, uploaded before anything is queued (its one
 // sync then waits on nothing).  A unit of one: the block programs of the track's
-// own blocks (or its segment tables), cached on the context.  A timeline: every
-// track's segment bounds shifted to its offset (a bound shared with the previous
-// track's end is not repeated; the gap between a track's last bound and the next
-// track start is a padding segment no gating block reads), every track's blocks as
-// segment ranges of that list, and the block programs at the timeline offsets.
+// own blocks, cached on the context.  A timeline: every track's first gating block,
+// first tile and the end of its real frames, and the block programs of every
+// track's own blocks at its timeline offset.
 static int unit_geometry(mm_ctx *c, Unit *p) {
     const mm_job *J = p->J;
     const int n = p->n;
+    p->geom = TrackTable{};
     if (n == 1) {
-        if (getenv("MM_LOUDNESS_SEGMENTS")) return upload_geometry(c, J, &p->geom);
-        p->geom = LineGeom{};
         p->geom.n_blocks = J->n_blocks;
-        return kb_upload(c, J->block_lo, J->block_hi, (size_t)J->n_blocks);
+        return c->loud.kb_upload(c, J->block_lo, J->block_hi, (size_t)J->n_blocks);
     }
     const int T = J[0].tile;
-    std::vector<int64_t> bounds, tblk((size_t)n + 1), tt0((size_t)n), tend((size_t)n);
-    std::vector<int32_t> s0, s1;
+    std::vector<int64_t> tblk((size_t)n + 1), tt0((size_t)n), tend((size_t)n), lo, hi;
     for (int i = 0; i < n; ++i) {
-        const mm_job &j = J[i];
         const int64_t o = p->off[i];
-        int64_t base;
-        if (!bounds.empty() && bounds.back() == o + j.seg_bounds[0]) {
-            base = (int64_t)bounds.size() - 1;
-        } else {
-            base = (int64_t)bounds.size();
-            bounds.push_back(o + j.seg_bounds[0]);
-        }
-        for (int64_t s = 1; s <= j.n_segs; ++s) bounds.push_back(o + j.seg_bounds[s]);
-        tblk[i] = (int64_t)s0.size();
-        for (int64_t b = 0; b < j.n_blocks; ++b) {
-            const auto r = seg_range(j.seg_bounds, j.n_segs, j.block_lo[b], j.block_hi[b]);
-            s0.push_back((int32_t)(base + r.first));
-            s1.push_back((int32_t)(base + r.second));
+        tblk[i] = (int64_t)lo.size();
+        for (int64_t b = 0; b < J[i].n_blocks; ++b) {
+            lo.push_back(o + J[i].block_lo[b]);
+            hi.push_back(o + J[i].block_hi[b]);
         }
         tt0[i] = o / T;
-        tend[i] = o + j.frames_proc;
+        tend[i] = o + J[i].frames_proc;
     }
-    tblk[n] = (int64_t)s0.size();
-    {  // the exact path's blocks: every track's own blocks at its timeline offset
-        std::vector<int64_t> lo, hi;
-        for (int i = 0; i < n; ++i)
-            for (int64_t b = 0; b < J[i].n_blocks; ++b) {
-                lo.push_back(p->off[i] + J[i].block_lo[b]);
-                hi.push_back(p->off[i] + J[i].block_hi[b]);
-            }
-        RET(kb_upload(c, lo.data(), hi.data(), lo.size()));
-    }
-    if (bounds.back() < p->P) bounds.push_back(p->P);  // the last track's padding
-    p->geom.n_segs = (int64_t)bounds.size() - 1;
-    p->geom.n_blocks = (int64_t)s0.size();
+    tblk[n] = (int64_t)lo.size();
+    RET(c->loud.kb_upload(c, lo.data(), hi.data(), lo.size()));
+    p->geom.n_blocks = (int64_t)lo.size();
     p->geom.n_trk = n;
-    RET(get_buf(c, "fz_bounds", bounds.size(), &p->geom.bounds));
     RET(get_buf(c, "fz_trk_blk", tblk.size(), &p->geom.trk_blk));
     RET(get_buf(c, "fz_trk_tile0", tt0.size(), &p->geom.trk_tile0));
     RET(get_buf(c, "fz_trk_end", tend.size(), &p->geom.trk_end));
-    RET(get_buf(c, "fz_s0", std::max<size_t>(s0.size(), 1), &p->geom.s0));
-    RET(get_buf(c, "fz_s1", std::max<size_t>(s1.size(), 1), &p->geom.s1));
-    HIPCHK(c, hipMemcpyAsync(p->geom.bounds, bounds.data(), bounds.size() * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(p->geom.trk_blk, tblk.data(), tblk.size() * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(p->geom.trk_tile0, tt0.data(), tt0.size() * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(p->geom.trk_end, tend.data(), tend.size() * 8, hipMemcpyHostToDevice, c->stream));
-    if (!s0.empty()) {
-        HIPCHK(c, hipMemcpyAsync(p->geom.s0, s0.data(), s0.size() * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(p->geom.s1, s1.data(), s1.size() * 4, hipMemcpyHostToDevice, c->stream));
-    }
     HIPCHK(c, hipStreamSynchronize(c->stream));  // host vectors are transient
     return MM_OK;
 }
@@ -1584,105 +1167,6 @@ int mm_stage_chunks(mm_ctx *c, const mm_job *j, const void *d_in) {
     return stage_chunks(c, j, d_in);
 }
 
-int mm_kweight_range_end(mm_ctx *c, double *end_state_host) {
-    if (!c || !c->staged) return set_err(c, MM_ERR_STATE, "no staged job");
-    if (c->G == 0) {
-        for (int k = 0; k < 4; ++k) end_state_host[k] = 0.0;
-        return MM_OK;
-    }
-    return kweight_energies(c, nullptr, nullptr, end_state_host);
-}
-
-int mm_hop_energies(mm_ctx *c, const double *carry_in_host, double *seg_energy_host) {
-    if (!c || !c->staged) return set_err(c, MM_ERR_STATE, "no staged job");
-    if (c->G == 0) {
-        for (int64_t s = 0; s < c->job.n_segs; ++s) seg_energy_host[s] = 0.0;
-        return MM_OK;
-    }
-    return kweight_energies(c, carry_in_host, seg_energy_host, nullptr);
-}
-
-// Time-sharded loudness with the energy vector in HBM, in three steps a caller can
-// compose with any collective between them (the library's communicator, or
-// torch.distributed over the same device buffer):
-//  1. mm_shard_energies_device: zero the caller's whole-track vector d_full and write
-//     this rank's segment energies at seg_offset (a rank's segments are consecutive
-//     global ones);
-//  2. a sum all-reduce of d_full over the ranks (mm_allreduce_sum_f64_device);
-//  3. mm_gate_finalize_device: pyloudnorm's gating of the whole track on the device,
-//     the gain towards `target` applied by finalize straight from device memory;
-//     returns L and the gain it applied.
-int mm_shard_energies_device(mm_ctx *c, const double *carry_in_host, int64_t n_global_segs, int64_t seg_offset,
-                             double *d_full) {
-    if (!c || !c->staged) return set_err(c, MM_ERR_STATE, "no staged job");
-    const int64_t nl = c->job.n_segs;
-    if (!d_full || n_global_segs < 1 || seg_offset < 0 || seg_offset + nl > n_global_segs)
-        return set_err(c, MM_ERR_ARG, "shard energies: segments [%lld, %lld) outside [0, %lld)",
-                       (long long)seg_offset, (long long)(seg_offset + nl), (long long)n_global_segs);
-    HIPCHK(c, hipMemsetAsync(d_full, 0, (size_t)n_global_segs * sizeof(double), c->stream));
-    if (c->G > 0 && nl > 0) {
-        double *seg;
-        RET(kweight_staged(c, carry_in_host, nullptr, &seg));
-        HIPCHK(c, hipMemcpyAsync(d_full + seg_offset, seg, (size_t)nl * sizeof(double), hipMemcpyDeviceToDevice,
-                                 c->stream));
-    }
-    return chain_check(c);  // (synchronises the stream: d_full is complete on return)
-}
-
-int mm_gate_finalize_device(mm_ctx *c, const double *d_full, int64_t n_global_segs, int64_t n_blocks,
-                            const int32_t *blk_s0_host, const int32_t *blk_s1_host, double block_scale,
-                            double target, void *d_out, double *loudness_gain_host) {
-    if (!c || !c->staged) return set_err(c, MM_ERR_STATE, "no staged job");
-    if (!d_full || n_global_segs < 1 || n_blocks < 1 || !blk_s0_host || !blk_s1_host || !loudness_gain_host)
-        return set_err(c, MM_ERR_ARG, "gate: bad segment or block geometry");
-    for (int64_t b = 0; b < n_blocks; ++b)
-        if (blk_s0_host[b] < 0 || blk_s1_host[b] < blk_s0_host[b] || blk_s1_host[b] > n_global_segs)
-            return set_err(c, MM_ERR_ARG, "gate: block %lld has segments [%d, %d) outside [0, %lld)",
-                           (long long)b, blk_s0_host[b], blk_s1_host[b], (long long)n_global_segs);
-    double *gout;
-    int32_t *s0, *s1;
-    RET(get_buf(c, "shard_gate", 2, &gout));
-    RET(get_buf(c, "shard_blk0", (size_t)n_blocks, &s0));
-    RET(get_buf(c, "shard_blk1", (size_t)n_blocks, &s1));
-    HIPCHK(c, hipMemcpyAsync(s0, blk_s0_host, (size_t)n_blocks * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(s1, blk_s1_host, (size_t)n_blocks * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    GateArgs ga{};
-    ga.n_blocks = n_blocks;
-    ga.blk_s0 = s0;
-    ga.blk_s1 = s1;
-    ga.seg = d_full;
-    ga.scale = block_scale;
-    ga.target = target;
-    ga.out = gout;
-    RET(gate_launch(c, ga, 1));
-    RET(finalize(c, &c->job, c->G, 0, 1.0, gout + 1, 1, d_out));
-    // L and the gain finalize applied (gate.hip's device expression, not a host recomputation)
-    HIPCHK(c, hipMemcpyAsync(loudness_gain_host, gout, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return MM_OK;
-}
-
-// Steps 1-3 with the library's own communicator.  `world` is the plan's rank count:
-// a multi-rank plan needs this context's RCCL communicator over exactly that many
-// ranks, or every rank would gate only its own part of the vector (and return a
-// different, wrong loudness) — refused instead.
-int mm_shard_loudness_device(mm_ctx *c, const double *carry_in_host, int64_t n_global_segs, int64_t seg_offset,
-                             int64_t n_blocks, const int32_t *blk_s0_host, const int32_t *blk_s1_host,
-                             double block_scale, double target, int32_t world, void *d_out,
-                             double *loudness_gain_host) {
-    if (!c) return MM_ERR_ARG;
-    if (world < 1) return set_err(c, MM_ERR_ARG, "shard loudness: world %d", world);
-    if (world > 1 && (!c->comm || c->nranks != world))
-        return set_err(c, MM_ERR_STATE, "shard loudness: a %d-rank plan needs this context's communicator over %d "
-                       "ranks (have %d)", world, world, c->comm ? c->nranks : 0);
-    double *full;
-    RET(get_buf(c, "shard_seg", (size_t)std::max<int64_t>(n_global_segs, 1), &full));
-    RET(mm_shard_energies_device(c, carry_in_host, n_global_segs, seg_offset, full));
-    if (world > 1) RET(mm_allreduce_sum_f64_device(c, full, n_global_segs));
-    return mm_gate_finalize_device(c, full, n_global_segs, n_blocks, blk_s0_host, blk_s1_host, block_scale, target,
-                                   d_out, loudness_gain_host);
-}
-
 int mm_finalize(mm_ctx *c, double gain_linear, int use_gain, void *d_out) {
     if (!c || !c->staged) return set_err(c, MM_ERR_STATE, "no staged job");
     return finalize(c, &c->job, c->G, 0, gain_linear, nullptr, use_gain, d_out);
@@ -1736,10 +1220,9 @@ int mm_kernel_stats(mm_ctx *c, char *names, int names_cap, double *total_ms, int
 
 }  // extern "C"
 
-// the WAV file path, the collectives, per-stage operators (AME:117-227 one at a time), metering
+// the WAV file path, the collectives, metering
 #include "wav.hip"
 #include "comm.hip"
-#include "ops.hip"
 #include "pcm16.h"
 #include "meter.hip"
 #include "ceiling.hip"

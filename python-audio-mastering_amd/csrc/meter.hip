@@ -12,8 +12,9 @@
 // This file owns the taps and the oversampler, on the device (tp_stage, tp_window, tp_frame)
 // and on the host (tp_host): ceil_need and mm_ceiling_host in ceiling.hip run the same.
 //
-// Included at the end of mastering.hip (one translation unit), after ops.hip (the
-// host entry points use its context helpers and loudness_device) and pcm16.h.
+// Included at the end of mastering.hip (one translation unit), after ops.hip and
+// loudness.hip (the host entry points use the context helpers, the operators' pointwise
+// kernels and loudness_device) and pcm16.h.
 
 namespace mm {
 

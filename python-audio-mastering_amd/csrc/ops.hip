@@ -8,8 +8,10 @@
 // computes in f32 with the Python-float constants rounded to f32 (NEP 50 weak
 // scalars), an f64 input in f64; scipy's sosfilt/lfilter run in f64.
 //
-// Included at the end of mastering.hip (one translation unit): the host entry
-// points use its context helpers (get_buf, launch, lb_prepare, upload_tables).
+// Included by mastering.hip (one translation unit) after the chain: the host entry
+// points use its context helpers (get_buf, launch, lb_prepare, upload_tables) and
+// stage_chunks.  The loudness operator (mm_op_loudness) is in loudness.hip, which
+// follows and uses the tile-major kernels and iir_in_place from here.
 
 namespace mm {
 
@@ -363,8 +365,6 @@ int launch_iir_op(mm_ctx *c, int nsec, bool r32, unsigned nblk, const IirOpArgs 
     }
 }
 
-int loudness_device(mm_ctx *c, const mm_job *j, int dtype, const void *din, double *out);
-
 // cascade f over a tile-major array in place (zero initial state, one line per channel)
 int iir_in_place(mm_ctx *c, const mm_iir *f, int64_t N, int ch, int64_t G, double *tm, int round_f32,
                  const double *mix = nullptr, int mix_a_f32 = 0) {
@@ -615,110 +615,6 @@ int mm_op_sosfilt(mm_ctx *c, int dtype, const void *in, int64_t frames, int chan
                   int round_f32, double *out) {
     return sosfilt_common(c, dtype, in, frames, channels, f, round_f32, nullptr, out);
 }
-
-// pyloudnorm Meter(rate).integrated_loudness of samples.mean(axis=1) (AME:213-218):
-// mono in the input's dtype, K-weighting (f32 write-backs for an f32 input), segment
-// energies, gating; out[0] = L, out[1] = 10 ** ((job->lufs_target - L) / 20).
-int mm_op_loudness(mm_ctx *c, const mm_job *j, int dtype, const void *in, double *out) {
-    if (!c || !j || !out || (j->frames_proc > 0 && !in)) return set_err(c, MM_ERR_ARG, "bad arguments");
-    RET(check_dtype(c, dtype));
-    const int ch = j->channels;
-    const int64_t N = j->frames_proc;
-    if (ch != 1 && ch != 2) return set_err(c, MM_ERR_ARG, "channels must be 1 or 2");
-    if (N < 1 || N >= (int64_t)1 << 31) return set_err(c, MM_ERR_ARG, "frames %lld out of range", (long long)N);
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t in_bytes = (size_t)N * ch * dtype_size(dtype);
-    char *din;
-    RET(get_buf(c, "op_in", in_bytes, &din));
-    HIPCHK(c, hipMemcpyAsync(din, in, in_bytes, hipMemcpyHostToDevice, c->stream));
-    return loudness_device(c, j, dtype, din, out);
-}
-
-}  // extern "C"
-
-namespace {
-
-// The device part of mm_op_loudness: din = the job's [frames_proc][channels] samples
-// of `dtype` in device memory (left unchanged); out (host) as mm_op_loudness.
-// Synchronous on return.
-int loudness_device(mm_ctx *c, const mm_job *j, int dtype, const void *din, double *out) {
-    RET(check_dtype(c, dtype));
-    const int ch = j->channels;
-    const int64_t N = j->frames_proc;
-    if (ch != 1 && ch != 2) return set_err(c, MM_ERR_ARG, "channels must be 1 or 2");
-    if (N < 1 || N >= (int64_t)1 << 31) return set_err(c, MM_ERR_ARG, "frames %lld out of range", (long long)N);
-    if (j->kweight.nsec != 2 || j->kweight.tpb != LB_THREADS) return set_err(c, MM_ERR_ARG, "K-weighting tables");
-    if (j->n_segs < 1 || !j->seg_bounds || !j->block_lo || !j->block_hi || j->n_blocks < 1)
-        return set_err(c, MM_ERR_ARG, "missing loudness geometry");
-    const int T = j->kweight.tile;  // the K-weighting tables' (sub-)tile
-    if (T < 1 || T > 512) return set_err(c, MM_ERR_ARG, "K-weighting tables built for %d-frame tiles", T);
-    for (int64_t s = 0; s + 1 < j->n_segs; ++s)
-        if (std::min<int64_t>(j->seg_bounds[s + 1], N) - j->seg_bounds[s] < T)
-            return set_err(c, MM_ERR_ARG, "loudness segment shorter than a tile");
-    const int64_t G = (N + T - 1) / T;
-    const size_t esz = dtype_size(dtype);
-    const void *mono = din;
-    if (ch == 2) {  // mean(axis=1) on the device, then the mono line
-        char *dmono;
-        RET(get_buf(c, "op_mono", (size_t)N * esz, &dmono));
-        PwArgs pa{};
-        pa.n = N;
-        pa.in = din;
-        pa.out = dmono;
-        if (dtype == MM_F32) RET(launch(c, "op_mono", pointwise_kernel<PW_MONO, float>, dim3(pw_blocks(N)), dim3(256), 0, pa));
-        else RET(launch(c, "op_mono", pointwise_kernel<PW_MONO, double>, dim3(pw_blocks(N)), dim3(256), 0, pa));
-        mono = dmono;
-    }
-    double *tm;
-    RET(get_buf(c, "op_tm", (size_t)G * T, &tm));
-    const unsigned nb = blocks_for(G, OPS_TILES);
-    const size_t lds = ((size_t)OPS_TILES * (T + 1)) * sizeof(double);
-    if (dtype == MM_F32)
-        RET(launch(c, "to_tile_major", to_tile_major_kernel<float, 1>, dim3(nb), dim3(256), lds, (const float *)mono, tm,
-                   N, G, T));
-    else
-        RET(launch(c, "to_tile_major", to_tile_major_kernel<double, 1>, dim3(nb), dim3(256), lds, (const double *)mono,
-                   tm, N, G, T));
-    RET(iir_in_place(c, &j->kweight, N, 1, G, tm, dtype == MM_F32));
-    // segment energies -> gating on the device (gate.hip)
-    double *part, *seg, *gout;
-    int64_t *part_seg;
-    RET(get_buf(c, "op_part", (size_t)G * 2, &part));
-    RET(get_buf(c, "op_part_seg", (size_t)G, &part_seg));
-    RET(get_buf(c, "op_seg", (size_t)j->n_segs, &seg));
-    RET(get_buf(c, "op_gate", 2, &gout));
-    LineGeom lg;
-    RET(upload_geometry(c, j, &lg));
-    KwArgs ka = kw_args(c, j, N, G);
-    // the line is already mono f64 and tiled by the K-weighting tile itself (one lane per
-    // tile); tile_energy / seg_reduce read neither kw_args' mix nor its sos
-    ka.G = ka.Gt = G;
-    ka.sub = 1;
-    ka.ch = 1;
-    ka.n_segs = j->n_segs;
-    ka.seg_bounds = lg.bounds;
-    ka.part = part;
-    ka.part_seg = part_seg;
-    RET(launch(c, "op_tile_energy", tile_energy_kernel, dim3(blocks_for(G, 256)), dim3(256), 0, ka, (const double *)tm));
-    RET(launch(c, "op_seg_reduce", seg_reduce_kernel, dim3(blocks_for(j->n_segs, 4)), dim3(256), 0, ka, seg));
-    GateArgs ga{};
-    ga.n_blocks = j->n_blocks;
-    ga.blk_s0 = lg.s0;
-    ga.blk_s1 = lg.s1;
-    ga.seg = seg;
-    ga.scale = j->block_scale;
-    ga.target = j->lufs_target;
-    ga.out = gout;
-    RET(gate_launch(c, ga, 1));
-    HIPCHK(c, hipMemcpyAsync(out, gout, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    resolve_events(c);
-    return MM_OK;
-}
-
-}  // namespace
-
-extern "C" {
 
 // apply_multiband_compressor (AME:196-210) on int16 PCM [frames][channels]: the
 // chain's crossover + compressor + overlay stages on ONE line (the job's chunk

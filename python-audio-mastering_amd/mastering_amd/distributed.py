@@ -132,7 +132,7 @@ def block_segments(plan: RankPlan):
 
 def gate_loudness(seg_energy: np.ndarray, plan: RankPlan) -> float:
     """pyloudnorm 0.1.1 integrated_loudness gating on whole-track segment energies
-    (same restatement as mm_gate_loudness in csrc/mastering.hip)."""
+    (same restatement as mm_gate_loudness in csrc/loudness.hip)."""
     cs = np.concatenate([[0.0], np.cumsum(seg_energy)])
     s0 = np.searchsorted(plan.seg_bounds, plan.block_lo)
     s1 = np.searchsorted(plan.seg_bounds, plan.block_hi)

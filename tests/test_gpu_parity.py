@@ -208,6 +208,41 @@ def test_time_sharded_on_one_gpu(oracle):
     _check(np.concatenate(outs), infos[0], ref, Lref)
 
 
+def test_staged_job_owns_its_loudness_geometry():
+    """mm_stage_chunks keeps its own copy of the job's loudness arrays (seg_bounds,
+    block_lo, block_hi): zeroing the caller's arrays after staging changes neither the
+    range's end state nor its segment energies, bit for bit.  1 s of mono 44.1 kHz is
+    the smallest input the staged path accepts (the 0.4 s block must fit)."""
+    import torch
+
+    from mastering_amd import distributed as D
+    from mastering_amd import native
+    from mastering_amd.synth import pink_noise_pcm16
+    rate = 44100
+    pcm = pink_noise_pcm16(rate, rate, 1, 5)
+    plan = D.plan_time_shards(pcm.shape[0], rate, 1, 1, 0)
+    x = torch.from_numpy(pcm[plan.in_lo:plan.in_hi].astype(np.float32) / 32768).cuda()
+
+    def run(overwrite):
+        be = D.GpuBackend(native.Context(0))
+        job = be.make_job(plan, {"lufs": -14.0}, native.MM_OUT_I16)
+        be.stage(job, x.data_ptr())
+        if overwrite:
+            assert job._segb.any() and job._hi.any()  # (the overwrite changes them)
+            for a in (job._segb, job._lo, job._hi):
+                a[...] = 0
+        z = be.kweight_range_end()
+        e = be.hop_energies(np.zeros(4))
+        be.ctx.close()
+        return z, e
+
+    z0, e0 = run(False)
+    z1, e1 = run(True)
+    assert e0.size == len(plan.local_bounds) - 1 and np.any(e0 > 0) and np.any(z0 != 0)
+    assert z1.tobytes() == z0.tobytes()
+    assert e1.tobytes() == e0.tobytes()
+
+
 @pytest.mark.parametrize("warmup", [0, 1])
 def test_compressor_resume_path(oracle, monkeypatch, warmup):
     """With little or no speculative warm-up and ONE queued fix-up sweep, the
