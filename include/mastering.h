@@ -140,7 +140,9 @@ typedef struct mm_job {
     /* mastering report (ABI 5): meter the delivered output at the end of the chain,
        before any copy-out (mm_last_meters).  The loudness of the output is included
        when the job carries loudness geometry (kweight, blocks, segments), whether or
-       not lufs_on is set.  0: the chain queues exactly what it queued before. */
+       not lufs_on is set.  0: the chain queues exactly what it queued before.  Bit 1
+       (MM_REPORT_R128; a new value of this field, the struct is unchanged) adds the R 128
+       report of the delivered output (mm_last_r128), which needs kweight.sos and rate. */
     int32_t meter_on;
     /* true-peak ceiling (ABI 5, the former trailing pad): 0 = off, the chain queues exactly
        what it queued before; else the ceiling C as linear * 2^28, 2^24 <= C <= 2^28
@@ -242,18 +244,70 @@ typedef struct mm_resample {
     int32_t peak[2];         /* max |delivered sample|, 0..32768                     */
 } mm_resample;
 
+/* The EBU R 128 report of a delivered signal (no reference counterpart): what an ITU-R
+ * BS.1770-4 meter reads.  mm_meter.loudness is the reference's own measure (pyloudnorm on
+ * the channel mean through float32 write-backs), which the chain normalises to; here every
+ * channel is K-weighted and the channel energies are summed, so a centred (L = R) stereo
+ * signal reads 10 log10 2 = 3.01 LU higher than there.
+ * Signal s[c][n] on the int16 grid, x = s / 32768 in f64 (MM_OUT_F32 carries the same PCM
+ * / 32768), R = rate, N = frames, 1 or 2 channels, each of channel weight 1.
+ *   1. y_c = K-weighting of x_c in f64: the caller's two DF2T sections sos[2][5]
+ *      (design.kweight_sections(R), the chain's design) in scipy.signal.lfilter's
+ *      operation order from a zero state, nothing rounded to float32.
+ *   2. Hops: B[i] = floor(i * R / 10) (int64), H = floor(10 * N / R) complete hops,
+ *      e[i] = sum_c sum_{n in [B[i], B[i+1])} y_c[n]^2 for i < H; frames from B[H] on
+ *      belong to no hop.
+ *   3. A window of w hops at hop j (j + w <= H): z_w[j] = (e[j] + ... + e[j+w-1]) /
+ *      (B[j+w] - B[j]), level l_w[j] = -0.691 + 10 log10 z_w[j].  Momentary: w = 4 (400 ms),
+ *      short-term: w = 30 (3 s).
+ *   4. momentary_max = max l_4, short_term_max = max l_30.
+ *   5. Integrated loudness: J_a = {j : l_4[j] > -70}; relative_gate = -0.691 + 10 log10(
+ *      mean_{J_a} z_4) - 10; J_g = {j in J_a : l_4[j] > relative_gate}; integrated =
+ *      -0.691 + 10 log10(mean_{J_g} z_4).
+ *   6. Loudness range (EBU Tech 3342): S_a = {j : l_30[j] > -70}; G_s = -0.691 + 10 log10(
+ *      mean_{S_a} z_30) - 20; k[0..n) = {l_30[j] : j in S_a, l_30[j] > G_s} ascending;
+ *      lra_low = k[((n-1) * 10 + 50) / 100], lra_high = k[((n-1) * 95 + 50) / 100] (integer
+ *      division), lra = lra_high - lra_low, lra_blocks = n.
+ *   7. H < 4: every figure is NaN.  H < 30: short_term_max, lra, lra_low, lra_high are NaN.
+ *      J_a empty (silence): integrated = -inf, relative_gate NaN.  No gated short-term
+ *      level: lra = 0, lra_blocks = 0, lra_low and lra_high NaN.
+ * Sums run in index order; both gates are strict. */
+typedef struct mm_r128 {
+    int64_t frames;
+    int32_t channels;
+    int32_t rate;
+    int64_t hops;              /* H                                                    */
+    int64_t momentary_blocks;  /* windows of 4 hops: max(H - 3, 0)                     */
+    int64_t short_term_blocks; /* windows of 30 hops: max(H - 29, 0)                   */
+    int64_t lra_blocks;        /* n of step 6                                          */
+    double integrated;         /* LUFS                                                 */
+    double relative_gate;      /* LUFS, step 5                                         */
+    double momentary_max;      /* LUFS                                                 */
+    double short_term_max;     /* LUFS                                                 */
+    double lra;                /* LU                                                   */
+    double lra_low, lra_high;  /* LUFS: the 10th and 95th percentile levels of step 6  */
+} mm_r128;
+
+/* Bits of mm_job.meter_on and mm_delivery.meter_on: which reports of the delivered output
+ * the master call makes (0 and 1 mean what they meant before the second bit). */
+#define MM_REPORT_METER 1 /* mm_meter (mm_last_meters)                                  */
+#define MM_REPORT_R128 2  /* mm_r128 (mm_last_r128), from the kweight.sos and the rate of
+                             the job (a delivery: of its `loud` job, which must be set)  */
+
 /* What mm_job cannot carry for a delivery at another rate (mm_deliver*): the converter
  * and, acting on the converted signal, the ceiling and the report. */
 typedef struct mm_delivery {
     const mm_resampler *rs;
     int32_t ceiling_q28;     /* 0 = off; else as mm_job.ceiling_q28                  */
     int32_t window;          /* the ceiling's look-ahead at rate_out (frames)        */
-    int32_t meter_on;        /* meter the delivered output (mm_last_meters)          */
+    int32_t meter_on;        /* MM_REPORT_METER: meter the delivered output (mm_last_meters);
+                                MM_REPORT_R128: its R 128 report (mm_last_r128)       */
     int32_t _pad;
     const struct mm_job *loud; /* a job carrying the loudness geometry of the OUTPUT
                                 (frames_proc = frames_out, channels, rate = rate_out,
                                 kweight with tpb 256, blocks, segments), as for
-                                mm_meter_device; NULL: peaks only                    */
+                                mm_meter_device; NULL: peaks only.  The R 128 report
+                                reads its kweight.sos and rate alone                 */
 } mm_delivery;
 
 /* Geometry of the compressor's envelope solve for a job (mm_solve_geometry: the
@@ -295,7 +349,10 @@ int mm_sync(mm_ctx *ctx);
    points only (mm_job is unchanged): mm_resampler, mm_resample, mm_delivery, the converter
    (mm_resample_device, mm_resample_pcm, mm_resample_host, mm_resample_frames,
    mm_resample_span, mm_last_resample) and the delivery path (mm_deliver_device, mm_deliver,
-   mm_deliver_wav).  A caller built against an older header must
+   mm_deliver_wav); and, again as new structs and entry points only and a new value of an
+   existing field (bit 1 of mm_job.meter_on and mm_delivery.meter_on): mm_r128 and the R 128
+   report (mm_r128_from_hops, mm_r128_host, mm_r128_device, mm_r128_pcm, mm_op_r128_hops,
+   mm_r128_span, mm_last_r128).  A caller built against an older header must
    refuse a library whose version differs from its own MM_ABI_VERSION. */
 #define MM_ABI_VERSION 5
 int mm_version(void);
@@ -345,6 +402,40 @@ int mm_last_meters(mm_ctx *ctx, int cap, mm_meter *out);
 int mm_true_peak_host(const int16_t *pcm, int64_t frames, int channels, mm_meter *out);
 /* Frames of m per workgroup of the meter kernel (where its seams lie). */
 int mm_meter_span(void);
+
+/* ---- EBU R 128 report ------------------------------------------------------- */
+/* Steps 3-7 of mm_r128 on the hop energies e[0, hops) in plain C++ (no context, no GPU):
+ * the one tail every path below ends in.  Fills every field but frames and channels (the
+ * hop energies carry neither: 0).  MM_ERR_ARG for a null pointer or rate < 2000. */
+int mm_r128_from_hops(const double *e, int64_t hops, int32_t rate, mm_r128 *out);
+/* The definition restated sequentially on the host (no context, no GPU), interleaved
+ * int16: its filter outputs are scipy.signal.lfilter's bit for bit.  hops_out (may be
+ * NULL) receives the first min(H, hops_cap) hop energies.  MM_ERR_ARG as below. */
+int mm_r128_host(const int16_t *pcm, int64_t frames, int channels, int32_t rate, const double sos[2][5],
+                 double *hops_out, int64_t hops_cap, mm_r128 *out);
+/* The report of a device-resident signal, interleaved [frames][channels] of `kind`
+ * (MM_OUT_I16, or MM_OUT_F32 = the same PCM / 32768: both give the same mm_r128), with the
+ * K-weighting sections sos of its rate.  MM_ERR_ARG, with words in mm_last_error, for
+ * channels other than 1 or 2, a bad kind, rate < 2000 (the library's floor: a hop then has
+ * at least 200 frames), frames >= 2^31 or a null pointer; frames == 0 gives a cleared
+ * struct with NaN figures.  The audio is never altered.  Synchronous on return.  The sections
+ * are not checked: design.kweight_sections(R) is a K-weighting only for R above ~3.1 kHz
+ * (its shelf lies at 1500 Hz; at or below 3 kHz its poles leave the unit circle). */
+int mm_r128_device(mm_ctx *ctx, const void *d_pcm, int kind, int64_t frames, int channels, int32_t rate,
+                   const double sos[2][5], mm_r128 *out);
+/* The same on a host buffer. */
+int mm_r128_pcm(mm_ctx *ctx, const void *pcm, int kind, int64_t frames, int channels, int32_t rate,
+                const double sos[2][5], mm_r128 *out);
+/* The GPU pass's hop energies themselves for a host buffer (a per-stage operator, for
+ * parity checks): copies the first min(H, cap) to hops_host and returns H. */
+int mm_op_r128_hops(mm_ctx *ctx, const void *pcm, int kind, int64_t frames, int channels, int32_t rate,
+                    const double sos[2][5], double *hops_host, int64_t cap);
+/* Frames one workgroup of the K-weighting pass covers (256 lanes of one tile each). */
+int mm_r128_span(void);
+/* The R 128 reports of the last master call on this context, as mm_last_meters: 1, or n
+ * for a batch in job order (frames 0 and NaN figures for a job without MM_REPORT_R128);
+ * copies min(cap, n) and returns n.  MM_ERR_STATE if no job of that call asked for one. */
+int mm_last_r128(mm_ctx *ctx, int cap, mm_r128 *out);
 
 /* ---- true-peak ceiling ----------------------------------------------------- */
 /* Hold a device-resident signal, interleaved [frames][channels] of `kind` (MM_OUT_I16,

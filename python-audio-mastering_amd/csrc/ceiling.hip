@@ -330,14 +330,23 @@ static int ceiling_device(mm_ctx *c, void *d_pcm, int kind, int64_t frames, int 
 }
 
 // The end of a master call for delivered buffer i (results_reset sized the call's results):
-// the ceiling, then the report, which so measures what is delivered.  A track that did not
-// ask for what another track of the call asked for leaves a cleared entry.
+// the ceiling, then the reports, which so measure what is delivered: bit 0 of meter_on the
+// meter, bit 1 the R 128 report (r128.hip) with the K-weighting sections and the rate of
+// `loud`.  A track that did not ask for what another track of the call asked for leaves a
+// cleared entry.
 static int finish_delivered(mm_ctx *c, void *d_out, int kind, int64_t frames, int channels, int i, int32_t ceiling_q28,
                             int32_t window, int meter_on, const mm_job *loud) {
     if (ceiling_q28) RET(ceiling_device(c, d_out, kind, frames, channels, ceiling_q28, window, &c->ceilings[(size_t)i]));
     else if (!c->ceilings.empty()) c->ceilings[(size_t)i].channels = channels;
-    if (meter_on) RET(meter_device(c, d_out, kind, frames, channels, loud, &c->meters[(size_t)i]));
+    if (meter_on & MM_REPORT_METER) RET(meter_device(c, d_out, kind, frames, channels, loud, &c->meters[(size_t)i]));
     else if (!c->meters.empty()) meter_clear(&c->meters[(size_t)i], 0, channels);
+    if (meter_on & MM_REPORT_R128) {
+        if (!loud || loud->kweight.nsec != 2)
+            return set_err(c, MM_ERR_ARG, "the R 128 report needs a job with the K-weighting sections (kweight.sos)");
+        RET(r128_device(c, d_out, kind, frames, channels, loud->rate, loud->kweight.sos, &c->r128s[(size_t)i]));
+    } else if (!c->r128s.empty()) {
+        r128_clear(&c->r128s[(size_t)i], 0, channels, 0);
+    }
     return MM_OK;
 }
 

@@ -67,6 +67,8 @@ struct mm_ctx {
     std::vector<mm_ctx *> children;
     // mastering report of the last master call (mm_last_meters; empty: it did not meter)
     std::vector<mm_meter> meters;
+    // R 128 reports of the last master call (mm_last_r128; empty: no job asked for one)
+    std::vector<mm_r128> r128s;
     // ceilings of the last master call (mm_last_ceilings; empty: no job set one)
     std::vector<mm_ceiling> ceilings;
     // the converter's taps on the device ("rs_taps": content key and geometry; key 0: none)

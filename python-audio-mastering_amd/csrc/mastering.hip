@@ -5,7 +5,7 @@
 // both context.h, followed by decode.hip (24/32-bit PCM input).  ops.hip (the
 // per-stage operators) and loudness.hip (the loudness tail, its operator and the
 // time-sharded entry points) follow the chain, before the units that call
-// line_loudness; wav.hip, comm.hip, then pcm16.h, meter.hip, ceiling.hip and resample.hip
+// line_loudness; wav.hip, comm.hip, then pcm16.h, meter.hip, r128.hip, ceiling.hip and resample.hip
 // (with mm_master* / mm_deliver*: a master call with or without a delivery) come at the end.
 #include <rccl/rccl.h>
 
@@ -926,11 +926,12 @@ static int unit_complete(mm_ctx *c, const Unit &u, mm_result *res) {
     return MM_OK;
 }
 
-// The per-call results of a master call (mm_last_meters, mm_last_ceilings, mm_last_resample):
-// none at its start; before its end one entry for each of the n delivered buffers of what
-// any of them asked for.
-static void results_reset(mm_ctx *c, int n = 0, bool ceiling = false, bool meter = false) {
-    c->meters.assign(meter ? (size_t)n : 0, mm_meter{});
+// The per-call results of a master call (mm_last_meters, mm_last_r128, mm_last_ceilings,
+// mm_last_resample): none at its start; before its end one entry for each of the n delivered
+// buffers of what any of them asked for (meter_on: the reports asked for, bits or-ed).
+static void results_reset(mm_ctx *c, int n = 0, bool ceiling = false, int meter_on = 0) {
+    c->meters.assign(meter_on & MM_REPORT_METER ? (size_t)n : 0, mm_meter{});
+    c->r128s.assign(meter_on & MM_REPORT_R128 ? (size_t)n : 0, mm_r128{});
     c->ceilings.assign(ceiling ? (size_t)n : 0, mm_ceiling{});
     c->resample_valid = false;
 }
@@ -1149,8 +1150,9 @@ int mm_master_batch(mm_ctx *c, int n, const mm_job *jobs, const void *const *d_i
         k->stats.clear();
         k->stat_order.clear();
     }
-    bool meter = false, ceiling = false;
-    for (int i = 0; i < n; ++i) meter = meter || jobs[i].meter_on;
+    int meter = 0;
+    bool ceiling = false;
+    for (int i = 0; i < n; ++i) meter |= jobs[i].meter_on;
     for (int i = 0; i < n; ++i) ceiling = ceiling || jobs[i].ceiling_q28;
     results_reset(c, n, ceiling, meter);
     for (int i = 0; i < n; ++i) {
@@ -1225,5 +1227,6 @@ int mm_kernel_stats(mm_ctx *c, char *names, int names_cap, double *total_ms, int
 #include "comm.hip"
 #include "pcm16.h"
 #include "meter.hip"
+#include "r128.hip"
 #include "ceiling.hip"
 #include "resample.hip"

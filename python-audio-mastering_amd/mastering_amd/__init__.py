@@ -16,6 +16,10 @@ Public surface (mirrors worker/audio_mastering_engine.py):
   params["report"], meter_pcm(pcm, rate), meters(ctx), true_peak(samples)
                                the mastering report (no reference counterpart): sample peak,
                                BS.1770-4 true peak and the loudness of the delivered output
+  params["r128"], r128_pcm(pcm, rate), r128s(ctx)
+                               the EBU R 128 report (no reference counterpart): integrated
+                               loudness as a BS.1770 meter reads it, maximum momentary and
+                               short-term loudness and the loudness range of the delivered output
   params["ceiling_dbtp"], ceiling_pcm(pcm, rate, db), ceilings(ctx)
                                the true-peak ceiling (no reference counterpart): an exact
                                look-ahead limiter on the delivered output
@@ -27,7 +31,7 @@ Public surface (mirrors worker/audio_mastering_engine.py):
                                alternate DSP profile on the same HIP operators
 """
 from .engine import (EQ_PRESETS, Job, ceiling_pcm, ceilings, master_batch, master_device, master_pcm,  # noqa: F401
-                     meter_pcm, meters, process, resample_pcm)
+                     meter_pcm, meters, process, r128_pcm, r128s, resample_pcm)
 from . import legacy  # noqa: F401
 from .gui_compat import batch_process_audio, process_audio  # noqa: F401
 from .ops import (apply_eq_to_samples, apply_multiband_compressor, apply_peak_filter, apply_saturation,  # noqa: F401
@@ -38,4 +42,4 @@ __all__ = ["legacy", "EQ_PRESETS", "Job", "master_pcm", "master_device", "master
            "apply_saturation", "apply_eq_to_samples", "apply_shelf_filter", "apply_peak_filter", "apply_stereo_width",
            "apply_multiband_compressor", "normalize_to_lufs", "soft_limiter", "audio_segment_to_float_array",
            "float_array_to_audio_segment", "integrated_loudness", "true_peak", "meter_pcm", "meters", "ceiling_pcm",
-           "ceilings", "resample_pcm"]
+           "ceilings", "resample_pcm", "r128_pcm", "r128s"]

@@ -68,7 +68,7 @@ class Job:
     def __init__(self, frames_in: int, rate: int, channels: int, params: dict, out_kind: int = native.MM_OUT_I16,
                  seg_bounds=None, check_length: bool = True, single_chunk: bool = False,
                  crossover=(design.LOW_CROSSOVER, design.HIGH_CROSSOVER), report: bool = False,
-                 ceiling_dbtp: float | None = None, output_rate: int | None = None):
+                 ceiling_dbtp: float | None = None, output_rate: int | None = None, r128: bool = False):
         """`seg_bounds` (time-sharded ranks, distributed.py): this range's loudness
         segment bounds relative to its first frame; the whole-track gating then
         happens on the host after the all-reduce.  `check_length=False` skips
@@ -87,9 +87,14 @@ class Job:
         (window design.ceiling_window(output_rate)) and the report act on the converted
         signal, so mm_job.ceiling_q28 and meter_on stay 0; None or `rate` itself plans
         exactly the job planned without it.  ValueError for a rate pair outside the
-        converter's limits."""
+        converter's limits.  `r128`: the EBU R 128 report of the delivered output (bit 1 of
+        meter_on, mm_last_r128; independent of `report`): kweight.sos is then filled whatever
+        else is planned; with `output_rate` the bit moves to the delivery, as `report` does;
+        not on a time-sharded range, whose rank does not hold the whole track."""
         if ceiling_dbtp is not None and seg_bounds is not None:
             raise ValueError("the true-peak ceiling needs the whole track: not available on a time-sharded range")
+        if r128 and seg_bounds is not None:
+            raise ValueError("the R 128 report needs the whole track: not available on a time-sharded range")
         if output_rate is not None and int(output_rate) == int(rate):
             output_rate = None
         if output_rate is not None and (seg_bounds is not None or single_chunk):
@@ -98,6 +103,7 @@ class Job:
         self.output_rate = None if output_rate is None else int(output_rate)
         self.resampler = Resampler(rate, output_rate) if output_rate is not None else None
         plan_report, report = report, bool(report) and output_rate is None  # (a delivery's report is planned below)
+        plan_r128, r128 = bool(r128), bool(r128) and output_rate is None
         if channels not in (1, 2):
             raise ValueError("only mono and stereo are supported (AME:119,137,152)")
         params = dict(params or {})
@@ -165,13 +171,16 @@ class Job:
         j.comp_warmup = COMP_WARMUP
         j.comp_max_iters = COMP_MAX_ITERS
         j.comp_super = comp_super_frames(self.rate, self.tile)
-        j.meter_on = int(bool(report))
+        j.meter_on = (native.REPORT_METER if report else 0) | (native.REPORT_R128 if r128 else 0)
         self.ceiling_dbtp = None if ceiling_dbtp is None else float(ceiling_dbtp)
         j.ceiling_q28 = 0 if ceiling_dbtp is None else design.ceiling_q28(ceiling_dbtp)
-        # --- loudness (with `report` alone: the geometry only, for the meter)
-        if lufs is not None or (report and self.frames_proc >= 0.4 * self.rate):
+        # --- loudness (with `report` alone: the geometry only, for the meter; with `r128`
+        # alone: the K-weighting sections only, for its own pass)
+        loud_geometry = lufs is not None or (report and self.frames_proc >= 0.4 * self.rate)
+        if loud_geometry or r128:
             self._fill_iir(j.kweight, design.kweight_sections(self.rate), [2],
                            self.tile // design.kweight_sub(self.tile), design.LB_THREADS)
+        if loud_geometry:
             if seg_bounds is None:
                 nb, lo, hi, segb, scale = design.loudness_blocks(self.frames_proc, self.rate)
             else:  # rank-local segments; blocks are gated over the whole track elsewhere
@@ -193,9 +202,11 @@ class Job:
             d.rs = ctypes.pointer(self.resampler.rs)
             d.ceiling_q28, j.ceiling_q28 = j.ceiling_q28, 0
             d.window = design.ceiling_window(self.output_rate)
-            d.meter_on = int(bool(plan_report))
-            if plan_report and self.frames_out >= 0.4 * self.output_rate:  # the output's loudness, as meter_pcm plans it
-                self._loud = Job(self.frames_out, self.output_rate, self.channels, {}, single_chunk=True, report=True)
+            d.meter_on = (native.REPORT_METER if plan_report else 0) | (native.REPORT_R128 if plan_r128 else 0)
+            # the output's loudness, as meter_pcm plans it, and the sections of the output's rate for the R 128 report
+            if (plan_report and self.frames_out >= 0.4 * self.output_rate) or plan_r128:
+                self._loud = Job(self.frames_out, self.output_rate, self.channels, {}, single_chunk=True,
+                                 report=bool(plan_report), r128=plan_r128)
                 d.loud = ctypes.pointer(self._loud.job)
             self.delivery = d
 
@@ -291,6 +302,48 @@ def meters(ctx: native.Context, cap: int = native.BATCH_STREAMS) -> list:
     return _last(ctx, "mm_last_meters", native.MMMeter, cap)
 
 
+def r128_dict(m: native.MMR128) -> dict:
+    """An mm_r128 as `info["r128"]`: the EBU R 128 figures of the delivered output (None
+    where the struct holds NaN: the signal is shorter than the 0.4 s or 3 s the figure
+    needs).  `integrated_lufs` is what an ITU-R BS.1770 meter reads (every channel
+    K-weighted, energies summed); report_dict's `output_loudness` is the reference's
+    channel-mean measure, up to 3.01 LU lower.  No reference counterpart."""
+    def val(x):
+        return None if math.isnan(x) else float(x)
+    return {"integrated_lufs": val(m.integrated), "momentary_max_lufs": val(m.momentary_max),
+            "short_term_max_lufs": val(m.short_term_max), "lra_lu": val(m.lra), "lra_low_lufs": val(m.lra_low),
+            "lra_high_lufs": val(m.lra_high), "relative_gate_lufs": val(m.relative_gate), "hops": int(m.hops),
+            "lra_blocks": int(m.lra_blocks)}
+
+
+def r128s(ctx: native.Context, cap: int = native.BATCH_STREAMS) -> list:
+    """The mm_r128 of every track of the context's last master call (mm_last_r128): one for
+    master_device, one per job for master_batch, in job order (frames 0 and NaN figures:
+    that job did not ask).  RuntimeError if no job of that call had `r128`."""
+    return _last(ctx, "mm_last_r128", native.MMR128, cap)
+
+
+def kweight_sos(rate: int):
+    """design.kweight_sections(rate) as the C-ABI's `const double sos[2][5]`."""
+    sos = ((ctypes.c_double * 5) * 2)()
+    for s, sec in enumerate(design.kweight_sections(rate)):
+        for k in range(5):
+            sos[s][k] = float(sec[k])
+    return sos
+
+
+def r128_pcm(pcm: np.ndarray, rate: int, device: int = 0) -> dict:
+    """The EBU R 128 report (r128_dict) of an int16 (or float32 = int16 / 32768) array [N]
+    or [N, ch] without mastering it (mm_r128_pcm)."""
+    ch = 1 if pcm.ndim == 1 else pcm.shape[1]
+    x, kind = _out_kind(pcm)
+    ctx = native.context(device)
+    m = native.MMR128()
+    ctx.check(ctx.lib.mm_r128_pcm(ctx.ptr, x.ctypes.data_as(ctypes.c_void_p), kind, x.shape[0], ch, int(rate),
+                                  kweight_sos(rate), ctypes.byref(m)), "mm_r128_pcm")
+    return r128_dict(m)
+
+
 def ceiling_dict(m: native.MMCeiling) -> dict:
     """An mm_ceiling as `info["ceiling"]`: the struct's integers, the ceiling and the linked
     true peak before and after in dBTP, the largest gain reduction in dB (limiter and
@@ -333,8 +386,10 @@ def _finish_info(info: dict, job: "Job", ctx: native.Context) -> dict:
         info["frames"], info["rate"], info["resample"] = job.frames_out, job.output_rate, resample_dict(m)
     if end.ceiling_q28:
         info["ceiling"] = ceiling_dict(ceilings(ctx, 1)[0])
-    if end.meter_on:
+    if end.meter_on & native.REPORT_METER:
         info["report"] = report_dict(meters(ctx, 1)[0], job.job.lufs_target if job.job.lufs_on else None)
+    if end.meter_on & native.REPORT_R128:
+        info["r128"] = r128_dict(r128s(ctx, 1)[0])
     return info
 
 
@@ -403,13 +458,16 @@ def master_pcm(pcm: np.ndarray, rate: int, params: dict, out_kind: int = native.
     that rate (mm_deliver): the chain's output is converted on the GPU, the ceiling and
     the report then act on the converted signal, out_pcm has info['frames'] frames at
     info['rate'] and info['resample'] (resample_dict) is added; absent or equal to `rate`,
-    the call is exactly the call without it."""
+    the call is exactly the call without it.  params['r128'] (truthy; independent of
+    'report') adds info['r128'] (r128_dict): the EBU R 128 figures of the delivered output."""
     ch = 1 if pcm.ndim == 1 else pcm.shape[1]
     params = dict(params or {})
     report = bool(params.pop("report", False))
     ceiling = params.pop("ceiling_dbtp", None)
     output_rate = params.pop("output_rate", None)
-    job = Job(pcm.shape[0], rate, ch, params, out_kind, report=report, ceiling_dbtp=ceiling, output_rate=output_rate)
+    r128 = bool(params.pop("r128", False))
+    job = Job(pcm.shape[0], rate, ch, params, out_kind, report=report, ceiling_dbtp=ceiling, output_rate=output_rate,
+              r128=r128)
     x, job.job.in_kind = _device_input(pcm, wide=True)
     shape = (job.frames_out,) if ch == 1 else (job.frames_out, ch)
     out = np.empty(shape, np.int16 if out_kind == native.MM_OUT_I16 else np.float32)
@@ -439,7 +497,7 @@ def master_device(ctx: native.Context, job: Job, d_in: int, d_out: int, res: nat
     with `report=True` is metered: `meters(ctx)[0]` (see report_dict); one planned with
     `ceiling_dbtp` is held under it first: `ceilings(ctx)[0]` (see ceiling_dict).  One planned
     with `output_rate` is delivered at that rate (mm_deliver_device): `d_out` then holds
-    `job.frames_out` frames."""
+    `job.frames_out` frames.  One planned with `r128=True`: `r128s(ctx)[0]` (see r128_dict)."""
     if job.delivery is not None:
         ctx.check(ctx.lib.mm_deliver_device(ctx.ptr, ctypes.byref(job.job), ctypes.byref(job.delivery),
                                             ctypes.c_void_p(d_in), ctypes.c_void_p(d_out),
@@ -458,7 +516,8 @@ def master_batch(ctx: native.Context, jobs, d_ins, d_outs, with_results: bool = 
     native.BATCH_STREAMS of them are in flight at once, each on its own stream.
     Returns one MMResult per job (or None).  Jobs planned with `report=True` are
     metered: `meters(ctx, len(jobs))` holds one mm_meter per job, in job order; jobs
-    planned with `ceiling_dbtp` are held under it: `ceilings(ctx, len(jobs))`."""
+    planned with `ceiling_dbtp` are held under it: `ceilings(ctx, len(jobs))`; jobs planned
+    with `r128=True` get their R 128 report: `r128s(ctx, len(jobs))`."""
     n = len(jobs)
     if any(j.delivery is not None for j in jobs):
         raise ValueError("delivery at another rate (output_rate) is not available for a batch")
@@ -482,6 +541,7 @@ def process(input_path: str, output_path: str, params: dict, device: int = 0, ve
     params['output_rate'] other than the file's rate delivers at that rate (mm_deliver_wav):
     the header carries it and info['frames'] / info['rate'] / info['resample'] describe the
     written file; the ceiling and the report act on the converted samples.
+    params['r128'] (truthy) adds info['r128'] (r128_dict), the EBU R 128 figures of the written samples.
     Raises ValueError for unreadable/unsupported input and RuntimeError for device
     failures, like the reference (AME:110-113)."""
     params = dict(params or {})
@@ -489,12 +549,13 @@ def process(input_path: str, output_path: str, params: dict, device: int = 0, ve
     report = bool(params.pop("report", False))
     ceiling = params.pop("ceiling_dbtp", None)
     output_rate = params.pop("output_rate", None)
+    r128 = bool(params.pop("r128", False))
     kind = native.MM_OUT_F32 if fmt == "f32" else native.MM_OUT_I16
     wi = wav_info(input_path, device)
     if verbose:
         print(f"Loaded {input_path}: {wi.frames} frames @ {wi.rate} Hz")
     job = Job(wi.frames, wi.rate, wi.channels, params, kind, report=report, ceiling_dbtp=ceiling,
-              output_rate=output_rate)
+              output_rate=output_rate, r128=r128)
     ctx = native.context(device)
     res = native.MMResult()
     if job.delivery is not None:

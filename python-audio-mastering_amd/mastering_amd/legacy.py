@@ -191,6 +191,8 @@ def soft_limiter(samples, threshold=0.98, device: int = 0):
 def master_pcm(pcm: np.ndarray, rate: int, settings: dict, device: int = 0) -> np.ndarray:
     """The legacy chain on int16 PCM [N] or [N, 2] -> int16 PCM (main.py:48-72)."""
     settings = dict(settings or {})
+    if settings.get("r128"):
+        raise ValueError("the R 128 report belongs to the mastering chain's delivery: not available in the legacy profile")
     n = pcm.shape[0]
     chunks = []
     bounds = design.chunk_bounds(n, rate)

@@ -77,6 +77,19 @@ class MMMeter(ctypes.Structure):
                 ("overs", ctypes.c_int64 * 2), ("loudness", ctypes.c_double)]
 
 
+class MMR128(ctypes.Structure):
+    _fields_ = [("frames", ctypes.c_int64), ("channels", ctypes.c_int32), ("rate", ctypes.c_int32),
+                ("hops", ctypes.c_int64), ("momentary_blocks", ctypes.c_int64),
+                ("short_term_blocks", ctypes.c_int64), ("lra_blocks", ctypes.c_int64),
+                ("integrated", ctypes.c_double), ("relative_gate", ctypes.c_double),
+                ("momentary_max", ctypes.c_double), ("short_term_max", ctypes.c_double),
+                ("lra", ctypes.c_double), ("lra_low", ctypes.c_double), ("lra_high", ctypes.c_double)]
+
+
+REPORT_METER, REPORT_R128 = 1, 2  # bits of mm_job.meter_on / mm_delivery.meter_on
+c_sos_p = ctypes.POINTER(ctypes.c_double * 5)  # const double sos[2][5]
+
+
 class MMCeiling(ctypes.Structure):
     _fields_ = [("frames", ctypes.c_int64), ("channels", ctypes.c_int32), ("window", ctypes.c_int32),
                 ("ceiling_q28", ctypes.c_int32), ("tp_in_q28", ctypes.c_int32), ("tp_limited_q28", ctypes.c_int32),
@@ -125,6 +138,8 @@ EXPORTS = ("mm_create", "mm_destroy", "mm_last_error", "mm_sync", "mm_version", 
            "mm_solve_geometry", "mm_np_sum_f32", "mm_check_compressor_math",
            "mm_meter_device", "mm_meter_pcm", "mm_last_meters", "mm_op_true_peak", "mm_true_peak_host",
            "mm_meter_span",
+           "mm_r128_from_hops", "mm_r128_host", "mm_r128_device", "mm_r128_pcm", "mm_op_r128_hops", "mm_r128_span",
+           "mm_last_r128",
            "mm_ceiling_device", "mm_ceiling_pcm", "mm_ceiling_host", "mm_last_ceilings", "mm_ceiling_span",
            "mm_ceiling_max_window",
            "mm_pcm_decode_device", "mm_op_pcm_decode", "mm_pcm_decode_host", "mm_pcm_decode_span",
@@ -215,6 +230,17 @@ def load():
             "mm_op_true_peak": ([vp, ctypes.c_int, vp, ctypes.c_int64, ctypes.c_int, c_double_p], ctypes.c_int),
             "mm_true_peak_host": ([P(ctypes.c_int16), ctypes.c_int64, ctypes.c_int, P(MMMeter)], ctypes.c_int),
             "mm_meter_span": ([], ctypes.c_int),
+            "mm_r128_from_hops": ([c_double_p, ctypes.c_int64, ctypes.c_int32, P(MMR128)], ctypes.c_int),
+            "mm_r128_host": ([P(ctypes.c_int16), ctypes.c_int64, ctypes.c_int, ctypes.c_int32, c_sos_p, c_double_p,
+                              ctypes.c_int64, P(MMR128)], ctypes.c_int),
+            "mm_r128_device": ([vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int32, c_sos_p,
+                                P(MMR128)], ctypes.c_int),
+            "mm_r128_pcm": ([vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int32, c_sos_p,
+                             P(MMR128)], ctypes.c_int),
+            "mm_op_r128_hops": ([vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int32, c_sos_p,
+                                 c_double_p, ctypes.c_int64], ctypes.c_int),
+            "mm_r128_span": ([], ctypes.c_int),
+            "mm_last_r128": ([vp, ctypes.c_int, P(MMR128)], ctypes.c_int),
             "mm_ceiling_device": ([vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int32, ctypes.c_int32,
                                    P(MMCeiling)], ctypes.c_int),
             "mm_ceiling_pcm": ([vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int32, ctypes.c_int32,
