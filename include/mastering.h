@@ -361,6 +361,16 @@ int mm_version(void);
    at rates up to 192 kHz does) or if comp_super is not 4 tiles (the rms kernel's
    workgroup shape). */
 int mm_solve_geometry(const mm_job *job, mm_solve_geom *out);
+/* Verification only (tests/test_gpu_record_base.py; an entry point added under ABI 5):
+   after a chain with the multiband compressor on this context, the release-jump
+   records of one band's active tiles, in compact order (chunk by chunk): tiles[i] =
+   the tile's index on the track, mmax[i] = its largest M, records[16 i .. 16 i + 15]
+   = its record (8 binades x 2 mantissa parities from the record's base; NaN where the
+   reference walk left its binade).  Fills at most `cap` tiles and returns the number
+   of active tiles in *count (a larger count than cap: nothing past cap was written).
+   Read-only; MM_ERR_STATE without such a chain. */
+int mm_solve_records(mm_ctx *ctx, int band, int64_t cap, int32_t *tiles, double *mmax, double *records,
+                     int64_t *count);
 /* sha256 prefix (16 hex digits) of the sources this library was built from
    (mastering_amd/srcsha.py: the csrc sources and this header) */
 const char *mm_source_sha(void);

@@ -118,6 +118,8 @@ struct CompArgs {
     int32_t *cnt[3];           // per tile: active frames
     double *mmax[3];           // per tile: largest M
     double *ced[3];            // per tile: (max,+) release summary {c, D} (double2; comp_rms_t)
+    int e0fix[3];              // the band's fixed record base: binade of the table's largest M, less JB - 1
+    double *desc_g[3];         // per tile with a nonzero M: release-jump record [2 JB] from e0fix (comp_rms_t)
     int32_t *total[3];         // per chunk: active frames (statistics)
     int32_t *cbtot[3];         // per column block: active tiles (comp_rms_t; zeroed per chain)
     int32_t *rank[3];          // per tile: active tiles before it in its chunk (comp_describe)

@@ -20,14 +20,18 @@
 //                (window sums in doubles, one-sided f32 estimate + one exact check),
 //                M = lut[r] gathered ONCE and stored as f64 into the super-tile-major
 //                M plane (column blocks of 64, so 64 walkers read 512 contiguous
-//                bytes per step), plus per tile its active count, largest M and
-//                (max,+) release summary `ce`, per column block its active-tile count.
+//                bytes per step), plus per tile its active count, largest M,
+//                (max,+) release summary `ce` and, while the tile's M values are in
+//                registers, its release-jump record: the exact effect of its T
+//                release steps on any state of the band's top EIGHT binades (JB = 8,
+//                both mantissa parities; the fixed base e0fix), per column block its
+//                active-tile count.
 //                Consumers gate every read of M on the tile's count: rows of tiles
 //                with no active frame are never stored (the quiet-tile skip).
 //  2. comp_describe per column block: ranks and lists the chunk's active tiles in
-//                compact order and records per active tile the exact effect of its T
-//                release steps on any state of the EIGHT binades above its largest M
-//                (release jumps, JB = 8, both mantissa parities).
+//                compact order with their records; only a tile whose largest M lies
+//                below the fixed base has its M rows read again here, for a record
+//                from the binade of that M (rec_base).
 //  3. comp_pass0 walker lanes (one per super-tile, a wave in lockstep) walk from a
 //                guess (the (max,+) release envelope folded over the preceding 32
 //                active tiles; exactly 0 at the chunk's first active tile), storing
@@ -62,8 +66,50 @@ __device__ __forceinline__ double div_cr(double m, double d, double rd) {
     return fma(rem, rd, q);
 }
 
+// IEEE binade of a positive normal double: x in [2^e, 2^(e+1))
+__device__ __forceinline__ int binade(double x) { return (int)((uint64_t)__double_as_longlong(x) >> 52) - 1023; }
+
+// ---- release-jump records: geometry ---------------------------------------------
+// An active tile's record holds, for JB consecutive binades from its BASE and both
+// mantissa parities, the exact effect of the tile's T release steps on a state of
+// that binade and parity (the exactness argument stands before release_jump below).
+// The base is the band's fixed one, e0fix = binade(the table's largest M) - (JB - 1),
+// whenever the tile's largest M reaches it: no state exceeds the table's largest M, so
+// e0fix .. e0fix + JB - 1 are ALL the binades a state at or above 2^e0fix can lie in,
+// and comp_rms_t can walk the references while it still holds the tile's M values (the
+// base does not wait for the tile's largest M).  A tile whose largest M lies below
+// 2^e0fix keeps binade(largest M) as its base (comp_describe walks it).  Every reader
+// takes the base from the tile's largest M through rec_base: nothing is stored for it.
+#ifndef MM_JB
+#define MM_JB 8
+#endif
+constexpr int JB = MM_JB;  // binades per record: base .. base + JB - 1
+constexpr int JF = JB < 4 ? JB : 4;  // binades of the records the pass-0 guess folds use (e_fold_tile)
+constexpr int DREC = 2 * JB;  // doubles per record: q[2 JB] (the tile's largest M: mmax)
+__device__ __forceinline__ int rec_base(double mx, int e0fix) {
+    const int e = binade(mx);
+    return e >= e0fix ? e0fix : e;
+}
+// the reference walk of binade e, mantissa parity p starts near the binade's top
+__device__ __forceinline__ double ref_start(int e, int p) {
+    constexpr uint64_t MANT = (1ull << 52) - 1;
+    return __longlong_as_double((long long)(((uint64_t)(e + 1023) << 52) | (MANT - 63 + (uint64_t)p)));
+}
+// its record entry after the tile's steps took it to r: the exact offset, or NaN if
+// it left its binade or ended on a zero mantissa (below 2^e + u)
+__device__ __forceinline__ double ref_entry(int e, int p, double r) {
+    constexpr uint64_t MANT = (1ull << 52) - 1;
+    const uint64_t rb = (uint64_t)__double_as_longlong(r);
+    const bool ok = (rb >> 52) == (uint64_t)(e + 1023) && (rb & MANT) != 0;
+    return ok ? ref_start(e, p) - r : __longlong_as_double(0x7ff8000000000000ll);
+}
+
+// Load blocks in flight of comp_rms_t.  The kernel has to stay within the 168 VGPRs
+// of three workgroups per CU (C2: 690 workgroups in 768 slots, one round) with phase
+// C's 2 JB reference walks (32 VGPRs) live: 135 VGPRs at 1, 22 more at 2, more than
+// 168 at 3 (DESIGN §8, §10a have the timings).
 #ifndef MM_RMS_NB
-#define MM_RMS_NB 3
+#define MM_RMS_NB 1
 #endif
 constexpr int RMS_B = 8;  // frames per load block of comp_rms_t
 constexpr int RMS_TPS = 4;  // tiles per super-tile comp_rms_t is written for (its four waves)
@@ -103,8 +149,9 @@ __device__ __forceinline__ double *chunk_plane(const CompArgs &a, int b, int64_t
 // stored one block later) and written to the super-tile-major plane that the
 // walkers and comp_apply read; rows past the end of a partial last tile get M = 0
 // (identity steps).  Also the tile's active count and largest M (the table is
-// nondecreasing in r), its (max,+) release summary for the pass-0 guesses, and the
-// per-chunk active count.
+// nondecreasing in r), its (max,+) release summary for the pass-0 guesses, its
+// release-jump record from the band's fixed base (desc_g; a tile with a nonzero M
+// only), and the per-chunk active count.
 #ifndef MM_RMS_MINB
 #define MM_RMS_MINB 1
 #endif
@@ -147,7 +194,7 @@ __device__ __forceinline__ double vmax(double x, double y) {
 //   C  lane = column, wave = tile position: M rows of 64 consecutive columns are
 //      stored as one 512-byte run (round 3 mapped lanes to consecutive tiles: 8 runs
 //      of 64 B per store), and the lane keeps its tile's (max,+) release
-//      summary (frames in order).
+//      summary and walks its 2 JB release-jump references (frames in order).
 // Gathers of block q are in flight while block q+1's rms runs; one workgroup
 // barrier per block (double-buffered R and M stages).
 constexpr int RT_SLOTS = 4 * 68;                      // M stage slots: position-major, 68 per position
@@ -248,7 +295,14 @@ __global__ void __launch_bounds__(256, MM_RMS_MINB) comp_rms_t_kernel(CompArgs a
     double *Mo = chunk_plane(a, b, cc);
     uint32_t eC = col_elem(a, cc * a.SPC + jtC / 4) + (uint32_t)(w * a.TP) * 64u;  // row w*TP of its column
     double ce = 0.0, De = 0.0;
+    bool anyM = false;                                // some M of the tile's own rows is nonzero
     const int slotC = w * 68 + lane;                  // == rt_slot(tlC)
+    // the tile's release-jump record from the band's fixed base: the 2 JB reference
+    // walks take the same d the (max,+) summary takes (rows past the tile: d = 0)
+    const int e0f = a.e0fix[b];
+    double ref[2 * JB];
+#pragma unroll
+    for (int k = 0; k < 2 * JB; ++k) ref[k] = ref_start(e0f + k / 2, k % 2);
 
     constexpr int B = RMS_B, NB = MM_RMS_NB;
     const int NBK = (T + B - 1) / B;
@@ -298,6 +352,9 @@ __global__ void __launch_bounds__(256, MM_RMS_MINB) comp_rms_t_kernel(CompArgs a
             const double d = div_cr(mj, Rf, rR);
             ce = vmax(mj, ce - d);
             De += d;
+            anyM = anyM || mj != 0.0;
+#pragma unroll
+            for (int k = 0; k < 2 * JB; ++k) ref[k] = ref[k] - d;
         }
     };
     auto run = [&](auto st, auto &&load) __attribute__((always_inline)) {
@@ -343,6 +400,14 @@ __global__ void __launch_bounds__(256, MM_RMS_MINB) comp_rms_t_kernel(CompArgs a
     if (vC)
         for (int i = T; i < a.TP; ++i, eC += 64u) Mo[eC] = 0.0;
     if (vC) reinterpret_cast<double2 *>(a.ced[b])[gC] = make_double2(ce, De);
+    // (anyM <=> cnt != 0, the tiles comp_describe copies a record of: M != 0 exactly
+    // from row r0 of the table on, which stage_compress checks on the host)
+    if (vC && anyM) {
+        double2 *rec = reinterpret_cast<double2 *>(a.desc_g[b] + gC * DREC);
+#pragma unroll
+        for (int k = 0; k < JB; ++k)
+            rec[k] = make_double2(ref_entry(e0f + k, 0, ref[2 * k]), ref_entry(e0f + k, 1, ref[2 * k + 1]));
+    }
     if (vA) {
         a.cnt[b][gA] = active;
         a.mmax[b][gA] = lut[rmx];
@@ -399,9 +464,6 @@ __device__ __forceinline__ BandStep band_step(const CompArgs &a, int b) {
     s.rR = a.rcp_release[b];
     return s;
 }
-
-// IEEE binade of a positive normal double: x in [2^e, 2^(e+1))
-__device__ __forceinline__ int binade(double x) { return (int)((uint64_t)__double_as_longlong(x) >> 52) - 1023; }
 
 // One envelope step, exactly pydub's
 //   if rms > thr and att <= M: att = min(att + M/A, M)
@@ -599,26 +661,23 @@ struct Walker {
 // result.  rho therefore depends only on d, e and the parity of A.  A reference
 // walk r that starts in binade e with the same parity and stays in it rounds
 // every step exactly like a, so after the tile's T release steps a ends at
-// a - (r0 - rT).  The describer walks 2 * JB such references per active tile
-// (binades e0 .. e0+JB-1 from their tops, both parities; e0 = binade of the
-// tile's largest M, below which no releasing state lies) and stores q = r0 - rT
-// (exact; NaN if the reference left its binade) and the largest M.  A fix-up
+// a - (r0 - rT).  Each active tile has 2 * JB such references walked (binades
+// e0 .. e0+JB-1 from their tops, both parities; e0 = rec_base(the tile's largest
+// M): comp_rms_t walks them from the band's fixed base, comp_describe the tiles
+// below it) and q = r0 - rT stored (exact; NaN if the reference left its binade),
+// beside the largest M.  The argument never uses the value of e0, only that a
+// reference exists for the state's (binade, parity); a state below the binade of
+// the largest M never jumps (x > max M fails).  A fix-up
 // walker in state a (binade e, parity p) may jump iff x = a - q[e - e0][p] has
 //   x > max M  (every entry state of the tile, all >= x, is > its M: release)
 //   x >= 2^e + u (every exact difference a_k - d_k >= a_{k+1} - u/2 > 2^e: grid u)
 // and then lands EXACTLY on the state the step-by-step walk reaches.  Inactive
 // frames (M = 0) are d = 0 steps for both.
-#ifndef MM_JB
-#define MM_JB 8
-#endif
-constexpr int JB = MM_JB;  // binades per descriptor: e0 .. e0 + JB - 1
-constexpr int JF = JB < 4 ? JB : 4;  // binades of the records the pass-0 guess folds use (e_fold_tile)
 struct SegDesc {
     double mx;
-    int e0;
+    int e0;  // rec_base(mx)
     double q[2 * JB];
 };
-constexpr int DREC = 2 * JB;  // doubles per descriptor record: q[2 JB] (max M: mmax, e0 = its binade)
 
 __device__ __forceinline__ bool release_jump(const SegDesc &d, double att, double *out) {
     constexpr uint64_t MANT = (1ull << 52) - 1;
@@ -636,21 +695,19 @@ __device__ __forceinline__ bool release_jump(const SegDesc &d, double att, doubl
     return true;
 }
 
-// The describer of one active tile as a stream consumer: the 2 * JB reference
-// walks over its T rows, each off every dependency chain but its own.
+// The describer of one active tile below the band's fixed base as a stream
+// consumer: the 2 * JB reference walks over its T rows from e0 = binade(its largest
+// M), each off every dependency chain but its own (comp_rms_t's phase C runs the
+// same walks from the fixed base for every other tile).
 struct Describer {
-    static constexpr uint64_t MANT = (1ull << 52) - 1;
-    double r0[2 * JB], r[2 * JB];
+    double r[2 * JB];
     int e0;
     BandStep bs;
     __device__ __forceinline__ void init(const double (&)[WB]) {}
     __device__ __forceinline__ void tile(int i) {
         if (i != 0) return;
 #pragma unroll
-        for (int k = 0; k < 2 * JB; ++k) {  // top of binade e0 + k/2, parity k % 2
-            const uint64_t bits = ((uint64_t)(e0 + k / 2 + 1023) << 52) | (MANT - 63 + (uint64_t)(k % 2));
-            r0[k] = r[k] = __longlong_as_double((long long)bits);
-        }
+        for (int k = 0; k < 2 * JB; ++k) r[k] = ref_start(e0 + k / 2, k % 2);
     }
     __device__ __forceinline__ void frame(int, double m, double) {
         const double dec = div_cr(m, bs.R, bs.rR);
@@ -659,30 +716,26 @@ struct Describer {
     }
     __device__ __forceinline__ void store(double *rec_) const {
         double2 *rec = reinterpret_cast<double2 *>(rec_);
-        double q[2 * JB];
 #pragma unroll
-        for (int k = 0; k < 2 * JB; ++k) {
-            // the reference stayed in its binade with a nonzero mantissa (>= 2^e + u) at the end
-            const uint64_t rb = (uint64_t)__double_as_longlong(r[k]);
-            const bool ok = (rb >> 52) == (uint64_t)(e0 + k / 2 + 1023) && (rb & MANT) != 0;
-            q[k] = ok ? r0[k] - r[k] : __longlong_as_double(0x7ff8000000000000ll);
-        }
-#pragma unroll
-        for (int k = 0; k < JB; ++k) rec[k] = make_double2(q[2 * k], q[2 * k + 1]);
+        for (int k = 0; k < JB; ++k)
+            rec[k] = make_double2(ref_entry(e0 + k, 0, r[2 * k]), ref_entry(e0 + k, 1, r[2 * k + 1]));
     }
 };
 
 // 2. links + describers, ONE launch.  grid: (column blocks, 3), a block of
 // 64 * TPS threads = one column block (64 super-tiles x TPS tiles = 64 TPS
 // consecutive tiles of one chunk), lanes mapped to tiles as in comp_rms_t's phase
-// C (wave k: tile position k of the 64 columns), so the describers' M loads are
+// C (wave k: tile position k of the 64 columns), so a describer's M loads are
 // 512-byte runs.
 //  * links: ranks the chunk's active tiles (rank[g] = active tiles before g in its
 //    chunk: the counts comp_rms_t left per column block for the blocks before this
 //    one, plus a scan over the block's tiles in tile order), lists them at compact
 //    index ci = chunk * K + rank (tl = the tile, mmaxc = its largest M, cedc = its
 //    (max,+) summary) and counts them (nact[c], by the chunk's last block);
-//  * describers: an active tile's release-jump record (Describer).
+//  * records: an active tile's release-jump record at its compact index: the copy
+//    of comp_rms_t's record (128 bytes) when the tile's largest M reaches the band's
+//    fixed base, else a Describer walk over the tile's M rows from the binade of its
+//    largest M (sparse, barely-over-threshold tiles; a wave without one exits).
 // (Round 3 ran the links as one 1024-thread block per chunk and band: 30 blocks
 // for a 5-min track, 26 us of latency before the describers' own launch.)
 #ifndef MM_DESC_NB
@@ -705,8 +758,11 @@ __global__ void __launch_bounds__(64 * DESC_MAX_TPS) comp_describe_kernel(CompAr
     const int64_t g = cc * a.K + jt;
     const bool valid = jt < a.K && g < a.G;
     const bool live = valid && a.cnt[b][g] != 0;
+    // the record: comp_rms_t's (from the fixed base) unless the tile's largest M lies below it
+    const double mx = live ? a.mmax[b][g] : 0.0;
+    const bool own = live && binade(mx) < a.e0fix[b];
     // tile order within the block: tile jt = (column block base) + l * TPS + kc
-    flag[l * TPS + kc] = live ? 1 : 0;
+    flag[l * TPS + kc] = live ? (own ? 1 : 3) : 0;  // (3: live with comp_rms_t's record)
     if (threadIdx.x < 64) {  // active tiles of the chunk's earlier column blocks (comp_rms_t counts), wave 0
         int32_t acc = 0;
         const int32_t *ct = a.cbtot[b] + cc * (a.SPC >> 6);
@@ -735,15 +791,29 @@ __global__ void __launch_bounds__(64 * DESC_MAX_TPS) comp_describe_kernel(CompAr
         a.mmaxc[b][ci] = a.mmax[b][g];
         reinterpret_cast<double2 *>(a.cedc[b])[ci] = reinterpret_cast<const double2 *>(a.ced[b])[g];
     }
-    if (!a.jumps || __all(!live)) return;
-    const int64_t gc = live ? g : cc * a.K;  // (dead lanes: the chunk's first tile)
+    if (!a.jumps) return;
+    // comp_rms_t's records, tile-indexed, to the tiles' compact indices: the block's
+    // tiles are consecutive and so are their records (and the live ones' compact
+    // indices), so JB consecutive threads copy one record (16 bytes each): whole
+    // 128-byte lines both ways (a lane copying its own tile's record would touch 64
+    // lines per instruction)
+    {
+        const double2 *__restrict__ src = reinterpret_cast<const double2 *>(a.desc_g[b]) + (g - (l * TPS + kc)) * JB;
+        double2 *__restrict__ dst = reinterpret_cast<double2 *>(a.descc[b]) + cc * a.K * JB;
+#pragma unroll
+        for (int it = 0; it < JB; ++it) {
+            const int e = it * NT + t, i = e / JB;  // tile i of the block, entry e % JB of its record
+            if (flag[i] == 3) dst[(int64_t)pre[i] * JB + (e - i * JB)] = src[e];
+        }
+    }
+    if (__all(!own)) return;
+    const int64_t gc = own ? g : cc * a.K;  // (other lanes: the chunk's first tile)
     Describer d;
     d.bs = band_step(a, b);
-    const double mx = a.mmax[b][gc];
-    d.e0 = mx > 0.0 ? binade(mx) : 0;
+    d.e0 = own ? binade(mx) : 0;
     const uint32_t off = tile_off(a, gc);
     stream_col<true, MM_DESC_NB>(plane(a, b, cc), [&](int) { return off; }, 1, a.TP, d);
-    if (live) d.store(a.descc[b] + ci * DREC);
+    if (own) d.store(a.descc[b] + ci * DREC);
 }
 
 // ---- super-tile release jumps --------------------------------------------------
@@ -802,7 +872,7 @@ __device__ void compose_super(const CompArgs &a, int b, int64_t s, int64_t ci0) 
         const int e = e0s + k / 2;
 #pragma unroll
         for (int t = 0; t < SJ_TPS; ++t) {
-            const int kt = e - binade(mxt[t]);
+            const int kt = e - rec_base(mxt[t], a.e0fix[b]);
             const int idx = 2 * min(max(kt, 0), JB - 1) + par;
             double qv = q[t][0];
 #pragma unroll
@@ -827,7 +897,10 @@ __device__ void compose_super(const CompArgs &a, int b, int64_t s, int64_t ci0) 
 // in the tile and ends on ct (the walk from 0, comp_rms_t); above it the pure release
 // E - q (exact while it stays in E's binade: the offsets do not depend on M), max'ed
 // with ct (a walk that clamps ends on ct's values: the steps are monotone).  An
-// uncovered E takes E - Dt (a guess; exactness never depends on it).
+// uncovered E takes E - Dt (a guess; exactness never depends on it).  qat(i) is the
+// record entry of binade binade(mx) + i / 2, parity i % 2: the JF binades from the
+// tile's largest M upwards, wherever the record's base lies (pass 0 stages exactly
+// those; NaN past the record's last binade, which no state reaches).
 template <typename QF>
 __device__ __forceinline__ double e_fold_tile(double E, double ct, double Dt, double mx, QF &&qat) {
     constexpr uint64_t MANT = (1ull << 52) - 1;
@@ -897,10 +970,14 @@ __global__ void __launch_bounds__(PASS0_BLOCK) comp_pass0_kernel(CompArgs a) {
                 const double2 v = cd[lo + i];
                 sc_c[i] = v.x;
                 sc_d[i] = v.y;
-                sc_m[i] = a.mmaxc[b][lo + i];
+                const double mxi = a.mmaxc[b][lo + i];
+                sc_m[i] = mxi;
+                // the JF binades from the tile's largest M upwards (the record may start below)
+                const int sh = binade(mxi) - rec_base(mxi, a.e0fix[b]);
 #pragma unroll
                 for (int k = 0; k < JF; ++k) {
-                    const double2 q = qd[(lo + i) * (DREC / 2) + k];
+                    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+                    const double2 q = sh + k < JB ? qd[(lo + i) * (DREC / 2) + sh + k] : make_double2(nan, nan);
                     sc_q[(2 * k) * EW_MAX + i] = q.x;
                     sc_q[(2 * k + 1) * EW_MAX + i] = q.y;
                 }
@@ -1162,7 +1239,7 @@ __global__ void __launch_bounds__(64) comp_fix_kernel(CompArgs a, const unsigned
             double x;
             SegDesc d;
             d.mx = m.mx;
-            d.e0 = binade(m.mx);
+            d.e0 = rec_base(m.mx, a.e0fix[b]);
 #pragma unroll
             for (int k = 0; k < 2 * JB; ++k) d.q[k] = m.q[k];
             if (a.jumps && release_jump(d, att, &x)) {

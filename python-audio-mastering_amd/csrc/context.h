@@ -60,6 +60,8 @@ struct mm_ctx {
     std::vector<std::string> stat_order;
     // host tables already resident on the device
     uint64_t lut_key[3] = {0, 0, 0};  // content keys of the band tables on the device (0: none)
+    uint64_t lut_ok_key[3] = {0, 0, 0};  // keys of the band tables last checked against their r0 (validate; 0: none)
+    int64_t lut_ok_r0[3] = {0, 0, 0};
     uint64_t sat_key = 0;             // content key of the exciter table on the device (0: none)
     bool sat_codes = false;           // its correction codes are complete (no entry needs the table)
     std::map<std::string, std::vector<double>> mats_cache;

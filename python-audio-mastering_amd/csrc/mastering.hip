@@ -160,6 +160,22 @@ static int validate(mm_ctx *c, const mm_job *j) {
             if (j->band[b].look < 0) return set_err(c, MM_ERR_ARG, "band %d: look < 0", b);
             if (!(j->band[b].release_frames >= 1.0) || !(j->band[b].attack_frames > 0.0))
                 return set_err(c, MM_ERR_ARG, "band %d: release must span >= 1 frame", b);
+            // r0 must be the table's first nonzero row and every row from it on nonzero: the
+            // tiles with an active frame (rms >= r0: cnt, comp_describe's live tiles) are then
+            // exactly the tiles with a nonzero M (the ones comp_rms_t writes a record for).
+            // The two rows at r0 are checked for every job, the whole column unless this
+            // context checked a table of the same content key against the same r0 last.
+            const double *lt = j->band[b].lut;
+            const int64_t r0 = j->band[b].r0;
+            const uint64_t key = j->band[b].lut_key;
+            bool ok = r0 >= 0 && r0 <= 32769 && (r0 == 0 || lt[4 * (r0 - 1)] == 0.0) &&
+                      (r0 > 32768 || lt[4 * r0] != 0.0);
+            if (ok && (key == 0 || c->lut_ok_key[b] != key || c->lut_ok_r0[b] != r0)) {
+                for (int64_t r = 0; r <= 32768 && ok; ++r) ok = (lt[4 * r] != 0.0) == (r >= r0);
+                c->lut_ok_key[b] = ok ? key : 0;
+                c->lut_ok_r0[b] = r0;
+            }
+            if (!ok) return set_err(c, MM_ERR_ARG, "band %d: r0 %lld is not the table's first nonzero row", b, (long long)r0);
         }
     }
     if (j->lufs_on) {
@@ -418,6 +434,8 @@ static int stage_compress(mm_ctx *c, const mm_job *j, short2 *const bands[3], co
     RET(get_buf(c, "comp_ced", (size_t)6 * G, &ced));
     RET(get_buf(c, "comp_cedc", (size_t)6 * NC, &cedc));
     RET(get_buf(c, "comp_descc", (size_t)3 * DREC * NC, &descc));
+    double *desc_g;
+    RET(get_buf(c, "comp_desc_g", (size_t)3 * DREC * std::max<int64_t>(G, 1), &desc_g));
     int32_t *ranks, *tls, *nacts;
     RET(get_buf(c, "comp_rank", (size_t)3 * G, &ranks));
     RET(get_buf(c, "comp_tl", (size_t)3 * NC, &tls));
@@ -477,6 +495,12 @@ static int stage_compress(mm_ctx *c, const mm_job *j, short2 *const bands[3], co
         ca.cedc[b] = cedc + (size_t)2 * b * NC;
         ca.tstc[b] = tstc + (size_t)b * NC;
         ca.descc[b] = descc + (size_t)b * DREC * NC;
+        ca.desc_g[b] = desc_g + (size_t)b * DREC * G;
+        // the fixed record base: no state exceeds the table's largest M (its last row: the
+        // table is nondecreasing), so JB binades down from that M's hold every state at or
+        // above 2^e0fix (a table without a positive M has no active tile: any base does)
+        const double mtop = j->band[b].lut[(size_t)4 * 32768];
+        ca.e0fix[b] = (mtop > 0.0 ? std::max(ilogb(mtop), -900) : 0) - (JB - 1);
         ca.start[b] = st + (size_t)b * NS;
         ca.end[b] = ends + (size_t)b * NS;
         ca.claim[b] = c->ctl.claims(b);
@@ -1023,6 +1047,36 @@ int mm_version(void) { return MM_ABI_VERSION; }
 int mm_solve_geometry(const mm_job *j, mm_solve_geom *out) {
     if (!j || !out) return MM_ERR_ARG;
     return solve_geometry(j, out);
+}
+
+// Verification only: the last chain's release-jump records of one band, active tile
+// by active tile in compact order (the solve's buffers stay on the context)
+int mm_solve_records(mm_ctx *c, int band, int64_t cap, int32_t *tiles, double *mmax, double *records,
+                     int64_t *count) {
+    if (!c || !count || band < 0 || band > 2 || cap < 0 || (cap > 0 && (!tiles || !mmax || !records)))
+        return set_err(c, MM_ERR_ARG, "bad arguments");
+    const Solve &sv = c->comp;
+    if (!sv.on) return set_err(c, MM_ERR_STATE, "no envelope solve on this context");
+    const CompArgs &ca = sv.ca;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int64_t nchunks = ca.GS / ca.SPC;
+    std::vector<int32_t> nact((size_t)nchunks);
+    HIPCHK(c, hipMemcpy(nact.data(), ca.nact[band], (size_t)nchunks * sizeof(int32_t), hipMemcpyDeviceToHost));
+    int64_t n = 0;
+    for (int64_t ch = 0; ch < nchunks; ++ch) {
+        const int64_t na = nact[(size_t)ch], take = std::max<int64_t>(0, std::min(na, cap - n));
+        const int64_t ci = ch * ca.K;
+        if (take > 0) {
+            HIPCHK(c, hipMemcpy(tiles + n, ca.tl[band] + ci, (size_t)take * sizeof(int32_t), hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(mmax + n, ca.mmaxc[band] + ci, (size_t)take * sizeof(double), hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(records + n * DREC, ca.descc[band] + ci * DREC, (size_t)take * DREC * sizeof(double),
+                                hipMemcpyDeviceToHost));
+        }
+        n += na;
+    }
+    *count = n;
+    return MM_OK;
 }
 
 #ifndef MM_SOURCE_SHA

@@ -135,7 +135,7 @@ EXPORTS = ("mm_create", "mm_destroy", "mm_last_error", "mm_sync", "mm_version", 
            "mm_op_pcm_to_float", "mm_op_saturation", "mm_op_saturation_table", "mm_op_stereo_width", "mm_op_quantize", "mm_op_soft_limiter",
            "mm_op_gain", "mm_op_sosfilt", "mm_op_loudness", "mm_op_multiband", "mm_master_batch",
            "mm_op_saturation_legacy", "mm_op_soft_limiter_legacy", "mm_op_sosfilt_mix", "mm_op_compress_bands",
-           "mm_solve_geometry", "mm_np_sum_f32", "mm_check_compressor_math",
+           "mm_solve_geometry", "mm_solve_records", "mm_np_sum_f32", "mm_check_compressor_math",
            "mm_meter_device", "mm_meter_pcm", "mm_last_meters", "mm_op_true_peak", "mm_true_peak_host",
            "mm_meter_span",
            "mm_r128_from_hops", "mm_r128_host", "mm_r128_device", "mm_r128_pcm", "mm_op_r128_hops", "mm_r128_span",
@@ -219,6 +219,8 @@ def load():
                                    ctypes.c_double, vp], ctypes.c_int),
             "mm_op_compress_bands": ([vp, P(MMJob), vp, vp, vp, vp], ctypes.c_int),
             "mm_solve_geometry": ([P(MMJob), P(MMSolveGeom)], ctypes.c_int),
+            "mm_solve_records": ([vp, ctypes.c_int, ctypes.c_int64, P(ctypes.c_int32), c_double_p, c_double_p,
+                                  c_int64_p], ctypes.c_int),
             "mm_np_sum_f32": ([P(ctypes.c_float), ctypes.c_int64, P(ctypes.c_float)], ctypes.c_int),
             "mm_check_compressor_math": ([vp, ctypes.c_int, c_double_p, c_double_p, ctypes.c_int64, c_double_p],
                                          ctypes.c_int),

@@ -21,12 +21,13 @@ MIN_F64 = {
     "eq": "112 (cascade: 4 x 5 fused pass 1 + 4 x 9 scipy-order pass 2, x2 ch) + width 8",
     "xover": "112 (same for LP2+HP2) + mid 4 + 3 quantise muls x2",
     "kweight": "~22 (mono: 2 x 5 fused + 2 x 9 scipy + energy)",
-    "comp_rms": "~39 (3 bands x: rms check 3, window sum 4, release summary 6)",
-    "comp_describe": "2 JB = 16 reference walks per active tile frame (active tiles only)",
+    "comp_rms": "~87 (3 bands x: rms check 3, window sum 4, release summary 6, 2 JB = 16 reference walks)",
+    "comp_describe": "— (links; a 128-byte record copied per active tile; 16 reference walks only for tiles below the fixed base)",
     "comp_pass0": "~8 per band-frame walked (2 Markstein divisions + step)",
     "comp_fix": "~8 per re-walked band-frame (serial chains)",
     "comp_apply": "~45 (3 bands x: divisions 6, step 3, gain 10^(-att/20) when it moves, 2 x audioop.mul)",
     "finalize": "~10 (gain, soft limiter, quantise x2)",
+    "kw_blocks": "4 (each mono frame's f32 square added into the 4 overlapping 0.4 s blocks)",
 }
 
 
