@@ -627,7 +627,10 @@ int mm_op_gain(mm_ctx *ctx, int dtype, const void *in, int64_t n, double gain, d
 /* scipy.signal.sosfilt of ONE cascade (f->nsec 1..4 sections, all in branch 0,
  * tables for LB tiles/block = 256/channels) over each channel column of
  * [frames][channels], zero initial state; f64 out.  round_f32: every section's
- * output is rounded to f32 (pyloudnorm's lfilter write-backs).  Replaces
+ * output is rounded to f32 (pyloudnorm's lfilter write-backs; such a cascade runs
+ * one launch per section, because the tile carry cannot hold a rounded hand-over).
+ * f->tile in [1, 512] with 16 * (tile * channels + 1) * 8 <= 65536 bytes (the layout
+ * transposes' LDS: tile <= 255 stereo, 511 mono), else MM_ERR_ARG.  Replaces
  * apply_eq_to_samples / apply_shelf_filter / apply_peak_filter (AME:146-194). */
 int mm_op_sosfilt(mm_ctx *ctx, int dtype, const void *in, int64_t frames, int channels, const mm_iir *f,
                   int round_f32, double *out);

@@ -243,6 +243,8 @@ static int loudness_check(mm_ctx *c, const mm_job *j, int dtype) {
         return set_err(c, MM_ERR_ARG, "missing loudness geometry");
     const int T = j->kweight.tile;  // the K-weighting tables' (sub-)tile
     if (T < 1 || T > 512) return set_err(c, MM_ERR_ARG, "K-weighting tables built for %d-frame tiles", T);
+    size_t lds;
+    RET(transpose_lds(c, T, 1, &lds));  // the mono line's transpose
     for (int64_t s = 0; s + 1 < j->n_segs; ++s)
         if (std::min<int64_t>(j->seg_bounds[s + 1], N) - j->seg_bounds[s] < T)
             return set_err(c, MM_ERR_ARG, "loudness segment shorter than a tile");
@@ -272,7 +274,8 @@ static int loudness_device(mm_ctx *c, const mm_job *j, int dtype, const void *di
     double *tm;
     RET(get_buf(c, "op_tm", (size_t)G * T, &tm));
     const unsigned nb = blocks_for(G, OPS_TILES);
-    const size_t lds = ((size_t)OPS_TILES * (T + 1)) * sizeof(double);
+    size_t lds;
+    RET(transpose_lds(c, T, 1, &lds));
     if (dtype == MM_F32)
         RET(launch(c, "to_tile_major", to_tile_major_kernel<float, 1>, dim3(nb), dim3(256), lds, (const float *)mono, tm,
                    N, G, T));

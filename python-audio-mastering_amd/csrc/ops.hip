@@ -169,9 +169,9 @@ __global__ void __launch_bounds__(256) from_tile_major_kernel(const double *tm, 
 
 // ------------------------------------------------------- generic DF2T cascade
 // scipy.signal.sosfilt / lfilter (f64) over each channel line of a tile-major
-// array, zero initial state, one launch (lookback.h carry).  R32: the output of
-// every section is rounded to f32 before the next one (pyloudnorm writes each
-// lfilter pass back into its float32 array, AME:218).
+// array, zero initial state, one launch (lookback.h carry).  R32: the section's
+// output is rounded to f32 (pyloudnorm writes each lfilter pass back into its
+// float32 array, AME:218); only single sections are launched so (iir_in_place).
 struct IirOpArgs {
     int64_t N, G;
     int T;
@@ -328,14 +328,26 @@ int check_dtype(mm_ctx *c, int dtype) {
 // the filter tables' tile, OPS_TILE or the K-weighting sub-tile)
 constexpr int OPS_TILE = 125;
 
+// Dynamic LDS of the two transposes for T-frame tiles of ch channels.  Nothing raises
+// a kernel's default limit of 64 KiB, so a tile that needs more is refused here,
+// before anything is uploaded or launched.
+int transpose_lds(mm_ctx *c, int T, int ch, size_t *lds) {
+    *lds = ((size_t)OPS_TILES * ((size_t)T * ch + 1)) * sizeof(double);
+    if (*lds > 64 * 1024)
+        return set_err(c, MM_ERR_ARG, "tile %d: the layout transposes need %zu bytes of LDS for %d channel(s), limit 65536",
+                       T, *lds, ch);
+    return MM_OK;
+}
+
 int upload_tile_major(mm_ctx *c, int dtype, const void *in, int64_t N, int ch, int64_t G, double **tm, int T) {
+    size_t lds;
+    RET(transpose_lds(c, T, ch, &lds));
     const size_t in_bytes = (size_t)N * ch * dtype_size(dtype);
     char *din;
     RET(get_buf(c, "op_in", std::max<size_t>(in_bytes, 1), &din));
     RET(get_buf(c, "op_tm", (size_t)std::max<int64_t>(G, 1) * T * ch, tm));
     if (in_bytes) HIPCHK(c, hipMemcpyAsync(din, in, in_bytes, hipMemcpyHostToDevice, c->stream));
     const unsigned nb = blocks_for(G, OPS_TILES);
-    const size_t lds = ((size_t)OPS_TILES * (T * ch + 1)) * sizeof(double);
     if (dtype == MM_F32) {
         if (ch == 2) return launch(c, "to_tile_major", to_tile_major_kernel<float, 2>, dim3(nb), dim3(256), lds,
                                    (const float *)din, *tm, N, G, T);
@@ -351,7 +363,9 @@ int upload_tile_major(mm_ctx *c, int dtype, const void *in, int64_t N, int ch, i
 template <int NS, int CH>
 int launch_iir_op_ns(mm_ctx *c, bool r32, unsigned nblk, const IirOpArgs &ia, const LbArgs &lb) {
     const size_t lds = lb_lds_bytes<2 * NS, CH>();
-    if (r32) return launch(c, "iir_op", iir_op_kernel<NS, CH, true>, dim3(nblk), dim3(LB_THREADS), lds, ia, lb);
+    if constexpr (NS == 1) {  // (iir_in_place runs a rounded cascade one section per launch)
+        if (r32) return launch(c, "iir_op", iir_op_kernel<1, CH, true>, dim3(nblk), dim3(LB_THREADS), lds, ia, lb);
+    }
     return launch(c, "iir_op", iir_op_kernel<NS, CH, false>, dim3(nblk), dim3(LB_THREADS), lds, ia, lb);
 }
 
@@ -365,13 +379,45 @@ int launch_iir_op(mm_ctx *c, int nsec, bool r32, unsigned nblk, const IirOpArgs 
     }
 }
 
+// Section s of the cascade f as a filter of its own.  The one-frame matrix is block
+// lower-triangular with one 2 x 2 diagonal block per section, so the diagonal blocks
+// of its powers are the powers of that block, computed by the same products: the
+// section's tables are cut out of the cascade's.
+void iir_section(const mm_iir *f, int s, mm_iir *o) {
+    memset(o, 0, sizeof *o);
+    o->nsec = o->nsec_branch0 = 1;
+    o->dim = 2;
+    o->tpb = f->tpb;
+    o->tile = f->tile;
+    memcpy(o->sos[0], f->sos[s], sizeof o->sos[0]);
+    for (int r = 0; r < 2; ++r)
+        for (int k = 0; k < 2; ++k) {
+            const int src = (2 * s + r) * MM_MAX_DIM + 2 * s + k, dst = r * MM_MAX_DIM + k;
+            for (int e = 0; e < MM_TILE_POW; ++e) o->phi_tile_pow[e][dst] = f->phi_tile_pow[e][src];
+            for (int e = 0; e < MM_BLK_POW; ++e) o->phi_blk_pow[e][dst] = f->phi_blk_pow[e][src];
+        }
+}
+
 // cascade f over a tile-major array in place (zero initial state, one line per channel)
 int iir_in_place(mm_ctx *c, const mm_iir *f, int64_t N, int ch, int64_t G, double *tm, int round_f32,
-                 const double *mix = nullptr, int mix_a_f32 = 0) {
+                 const double *mix = nullptr, int mix_a_f32 = 0, int section = 0) {
     if (f->nsec < 1 || f->nsec > 4) return set_err(c, MM_ERR_ARG, "nsec %d out of [1, 4]", f->nsec);
     if (f->nsec_branch0 != f->nsec) return set_err(c, MM_ERR_ARG, "the operator filters ONE cascade");
     if (f->tpb != LB_THREADS / ch)
         return set_err(c, MM_ERR_ARG, "tables built for %d tiles/block, need %d", f->tpb, LB_THREADS / ch);
+    if (round_f32 && f->nsec > 1) {
+        // The f32 write-back makes a later section's input a non-linear function of the
+        // earlier sections' states, which the tile maps (zero-state response + Phi s)
+        // cannot carry: in one launch some 5 % of the samples came out one f32 step from
+        // the sequential filter's.  A single section's state never sees its own rounded
+        // output, so one launch per section is the sequential result up to the f64 carry.
+        std::vector<mm_iir> one(1);
+        for (int s = 0; s < f->nsec; ++s) {
+            iir_section(f, s, one.data());
+            RET(iir_in_place(c, one.data(), N, ch, G, tm, 1, nullptr, 0, s));
+        }
+        return MM_OK;
+    }
     IirOpArgs ia{};
     ia.N = N;
     ia.G = G;
@@ -387,7 +433,8 @@ int iir_in_place(mm_ctx *c, const mm_iir *f, int64_t N, int ch, int64_t G, doubl
         ia.mix_a_f32 = mix_a_f32;
     }
     LbArgs lb{};
-    RET(upload_tables(c, "op_iir", *f, lb));
+    const char *tab_name[4] = {"op_iir", "op_iir_s1", "op_iir_s2", "op_iir_s3"};  // each caches its last upload
+    RET(upload_tables(c, tab_name[section], *f, lb));
     const unsigned nblk = blocks_for(G, LB_THREADS / ch);
     RET(lb_prepare(c, nblk, ch, lb));
     RET(get_buf(c, "op_lb_error", 4, &lb.error));
@@ -530,6 +577,8 @@ static int sosfilt_common(mm_ctx *c, int dtype, const void *in, int64_t frames, 
     if (frames == 0) return MM_OK;
     const int T = f->tile;
     if (T < 1 || T > 512) return set_err(c, MM_ERR_ARG, "filter tables built for %d-frame tiles", T);
+    size_t lds;
+    RET(transpose_lds(c, T, channels, &lds));
     const int64_t G = (frames + T - 1) / T;
     double *tm;
     RET(upload_tile_major(c, dtype, in, frames, channels, G, &tm, T));
@@ -537,7 +586,6 @@ static int sosfilt_common(mm_ctx *c, int dtype, const void *in, int64_t frames, 
     double *dout;
     RET(get_buf(c, "op_out", (size_t)frames * channels, &dout));
     const unsigned nb = blocks_for(G, OPS_TILES);
-    const size_t lds = ((size_t)OPS_TILES * (T * channels + 1)) * sizeof(double);
     if (channels == 2)
         RET(launch(c, "from_tile_major", from_tile_major_kernel<2>, dim3(nb), dim3(256), lds, (const double *)tm, dout,
                    frames, G, T));

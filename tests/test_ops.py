@@ -8,7 +8,10 @@ each check.
 Tolerances: integer outputs (quantise, multiband int16) bit-exact except where a
 floating-point stage before a truncation can land on the other side of an
 integer (stated per test); f64 IIR outputs 1e-12 absolute (the look-back composes
-tile carries in a different order than scipy's sequential loop); f32 tanh 2 ulp
+tile carries in a different order than scipy's sequential loop; that figure holds
+for this 8192-frame fixture in one workgroup: longer signals, other tiles and the
+workgroup seams are in tests/test_gpu_iir_seams.py, with a tolerance derived per
+case); f32 tanh 2 ulp
 (numpy's f32 tanh is not correctly rounded); everything else bit-exact."""
 import os
 
