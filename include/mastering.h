@@ -212,6 +212,64 @@ typedef struct mm_ceiling {
     int64_t limited_frames;  /* frames with g < ONE                                 */
 } mm_ceiling;
 
+/* Delivery to an R 128 loudness target under the true-peak ceiling (no reference counterpart):
+ * the static gain that makes the DELIVERED signal read the target on a BS.1770-4 meter with
+ * the ceiling held, found by re-measuring after every limiter pass.
+ * Notation: s[c][n] the source on the int16 grid (1 or 2 channels, N frames, rate R); T the
+ * target in LUFS, carried as centi-LU level_clu = round(100 T) (0: off); C, W the ceiling and
+ * window of mm_ceiling (C = 0: no ceiling); ONE = 2^16; I(x) = mm_r128.integrated of x with
+ * the caller's K-weighting sections; gain(x, g)[n] = clip(((int64)x[n] * g + 2^15) >> 16,
+ * -32768, 32767) (arithmetic shift; `clipped` counts the samples the clip moved);
+ * ceil(x, C, W) = mm_ceiling as it stands; q(G) = clamp(floor(G * 2^16 + 0.5), 2^8, 2^21).
+ * Constants: MM_LEVEL_PASSES = 5, TOL = 0.05 LU, SMIN = 0.25.
+ *   1. I_src = I(s).  Not finite (fewer than 4 hops, or silence): the result is ceil(s, C, W),
+ *      or s itself when C = 0; status UNMEASURABLE, passes = 0.
+ *   2. g_0 = q(10^((T - I_src) / 20)).
+ *   3. Pass k forms y_k from the SOURCE, never from y_(k-1): rounding does not accumulate.
+ *      C = 0:  g_peak = min(floor(32767 * 2^16 / max|s|), 2^21); g_k > g_peak: g_k = g_peak and
+ *              the pass is capped.  y_k = gain(s, g_k): nothing can clip.
+ *      C != 0, g_k <= ONE:  y_k = ceil(gain(s, g_k), C, W).
+ *      C != 0, g_k > ONE (the limiter runs BEFORE the boost, so that the boost cannot clip
+ *              first):  g_cap = ((C - 8286) * 2^16) >> 24; g_k > g_cap: g_k = g_cap and the pass
+ *              is capped.  C' = floor((C - 8286) * 2^16 / g_k) (>= 2^24: a legal ceiling).
+ *              y_k = ceil(gain(ceil(s, C', W), g_k), C, W).  Since |Y(gain(u, g))| <= g |Y(u)| /
+ *              2^16 + 8285.5 < C, the last ceil is normally a meter pass that writes nothing:
+ *              it is there so that the guarantee is mm_ceiling's own even if a sample clipped.
+ *   4. I_k = I(y_k), d_k = 20 log10(g_k / 2^16).  y_k is delivered at the first of these that
+ *      holds, in this order: |T - I_k| <= TOL: REACHED; the pass was capped: CAPPED; k >= 1,
+ *      d_k != d_(k-1) and the measured slope m = (I_k - I_(k-1)) / (d_k - d_(k-1)) < SMIN:
+ *      SATURATED (the limiter eats the gain: pushing on only squashes the signal);
+ *      k = MM_LEVEL_PASSES - 1: PASSES_SPENT.
+ *   5. Otherwise g_(k+1) = q((g_k / 2^16) * 10^((T - I_k) / (20 slope))), slope = min(m, 1)
+ *      when m is defined (a secant step), 1 on pass 0.
+ * Channels are linked: one gain for all of them. */
+#define MM_LEVEL_PASSES 5
+#define MM_LEVEL_OFF 0
+#define MM_LEVEL_REACHED 1
+#define MM_LEVEL_CAPPED 2
+#define MM_LEVEL_SATURATED 3
+#define MM_LEVEL_PASSES_SPENT 4
+#define MM_LEVEL_UNMEASURABLE 5
+typedef struct mm_level {
+    int64_t frames;          /* 0: this track had no loudness target (mm_last_levels) */
+    int32_t channels;
+    int32_t rate;
+    int32_t target_clu;      /* level_clu                                            */
+    int32_t ceiling_q28;     /* C (0: none)                                          */
+    int32_t window;          /* W                                                    */
+    int32_t status;          /* MM_LEVEL_*                                           */
+    int32_t passes;          /* passes run; the last one is delivered                */
+    int32_t gain_q16;        /* g of the delivered pass (ONE if none)                */
+    int32_t pass_gain_q16[MM_LEVEL_PASSES]; /* g_k, after any cap                    */
+    int32_t min_gain_q16;    /* of the delivered pass's limiting ceil call: the one at C',
+                                else the one at C (ONE: none, or nothing limited)     */
+    double source_lufs;      /* I_src                                                */
+    double pass_lufs[MM_LEVEL_PASSES]; /* I_k (NaN: pass not run)                    */
+    double loudness;         /* I of the delivered signal; NaN if unmeasurable       */
+    int64_t clipped;         /* samples the delivered pass's gain clipped            */
+    int64_t limited_frames;  /* of the same ceil call as min_gain_q16                */
+} mm_level;
+
 /* The sample-rate converter (no reference counterpart), all integers.  With g =
  * gcd(rate_in, rate_out): L = rate_out / g, M = rate_in / g.  taps is the caller's table
  * c[L][K] (design.resample_taps: a Kaiser-windowed sinc of 64 zero crossings a side, every
@@ -294,15 +352,21 @@ typedef struct mm_r128 {
 #define MM_REPORT_R128 2  /* mm_r128 (mm_last_r128), from the kweight.sos and the rate of
                              the job (a delivery: of its `loud` job, which must be set)  */
 
-/* What mm_job cannot carry for a delivery at another rate (mm_deliver*): the converter
- * and, acting on the converted signal, the ceiling and the report. */
+/* What mm_job cannot carry for a delivery (mm_deliver*): the converter to another rate and,
+ * acting on the delivered signal, the loudness target, the ceiling and the report. */
 typedef struct mm_delivery {
-    const mm_resampler *rs;
+    const mm_resampler *rs;  /* NULL: deliver at the job's own rate (the chain writes the
+                                caller's output itself; mm_last_resample: MM_ERR_STATE)  */
     int32_t ceiling_q28;     /* 0 = off; else as mm_job.ceiling_q28                  */
     int32_t window;          /* the ceiling's look-ahead at rate_out (frames)        */
     int32_t meter_on;        /* MM_REPORT_METER: meter the delivered output (mm_last_meters);
                                 MM_REPORT_R128: its R 128 report (mm_last_r128)       */
-    int32_t _pad;
+    int32_t level_clu;       /* the former pad: 0 = off (nothing new is queued); else the
+                                loudness target in centi-LU, -4000 .. -500 (design.level_clu):
+                                the delivered signal is levelled to it under the ceiling
+                                (mm_level, mm_last_levels), which replaces the plain ceiling
+                                call; needs `loud` for its kweight.sos and rate, as
+                                MM_REPORT_R128 does                                      */
     const struct mm_job *loud; /* a job carrying the loudness geometry of the OUTPUT
                                 (frames_proc = frames_out, channels, rate = rate_out,
                                 kweight with tpb 256, blocks, segments), as for
@@ -352,7 +416,11 @@ int mm_sync(mm_ctx *ctx);
    mm_deliver_wav); and, again as new structs and entry points only and a new value of an
    existing field (bit 1 of mm_job.meter_on and mm_delivery.meter_on): mm_r128 and the R 128
    report (mm_r128_from_hops, mm_r128_host, mm_r128_device, mm_r128_pcm, mm_op_r128_hops,
-   mm_r128_span, mm_last_r128).  A caller built against an older header must
+   mm_r128_span, mm_last_r128); and, as a new struct and entry points and in the place of
+   mm_delivery's pad (a caller that zeroed it gets what it got): mm_delivery.level_clu, a
+   delivery without a converter (rs == NULL), mm_level and the level entry points
+   (mm_level_device, mm_level_pcm, mm_level_host, mm_op_level_gain, mm_last_levels,
+   mm_level_span).  A caller built against an older header must
    refuse a library whose version differs from its own MM_ABI_VERSION. */
 #define MM_ABI_VERSION 5
 int mm_version(void);
@@ -472,6 +540,38 @@ int mm_ceiling_span(void);
 /* The largest look-ahead window, in frames (1024). */
 int mm_ceiling_max_window(void);
 
+/* ---- delivery to a loudness target -------------------------------------------- */
+/* Level a device-resident signal, interleaved [frames][channels] of `kind` (MM_OUT_I16, or
+ * MM_OUT_F32 = the same PCM / 32768), in place to level_clu under the ceiling ceiling_q28
+ * (0: none; window as mm_ceiling_device), as mm_level defines, with the K-weighting
+ * sections sos of its rate.  ceil_out (may be NULL) receives, when ceiling_q28 != 0, the
+ * final mm_ceiling call at C on the delivered pass.  MM_ERR_ARG, with words in
+ * mm_last_error and the context still usable, for level_clu outside [-4000, -500], a bad
+ * kind, channels, ceiling or window, rate < 2000 or null sections.  Synchronous on return. */
+int mm_level_device(mm_ctx *ctx, void *d_pcm, int kind, int64_t frames, int channels, int32_t rate,
+                    const double sos[2][5], int32_t level_clu, int32_t ceiling_q28, int32_t window, mm_level *out,
+                    mm_ceiling *ceil_out);
+/* The same on a host buffer, in place. */
+int mm_level_pcm(mm_ctx *ctx, void *pcm, int kind, int64_t frames, int channels, int32_t rate, const double sos[2][5],
+                 int32_t level_clu, int32_t ceiling_q28, int32_t window, mm_level *out, mm_ceiling *ceil_out);
+/* The definition restated in plain C++ on the host (no context, no GPU), in place on
+ * interleaved int16: mm_ceiling_host, mm_r128_host and the gain under the same rule. */
+int mm_level_host(int16_t *pcm, int64_t frames, int channels, int32_t rate, const double sos[2][5], int32_t level_clu,
+                  int32_t ceiling_q28, int32_t window, mm_level *out, mm_ceiling *ceil_out);
+/* The gain kernel alone on host buffers (a per-stage operator, for parity checks): n samples
+ * of `kind` by gain_q16 in [2^8, 2^21], through device views that start src_off and dst_off
+ * samples (0 .. 7) past a 16-byte boundary; dst_off < 0: in place.  *clipped and *peak are
+ * the kernel's statistics (samples the clip moved; max |delivered sample|). */
+int mm_op_level_gain(mm_ctx *ctx, const void *in, int kind, int64_t n, int src_off, int dst_off, int32_t gain_q16,
+                     void *out_pcm, int64_t *clipped, int32_t *peak);
+/* The levels of the last master call on this context, as mm_last_meters (a call without a
+ * delivery, or a batch, sets none): copies min(cap, n) and returns n.  MM_ERR_STATE if that
+ * call set no loudness target. */
+int mm_last_levels(mm_ctx *ctx, int cap, mm_level *out);
+/* Samples one workgroup of the gain kernel covers in whole 16-byte vectors (its seams lie
+ * at multiples of this past the first 16-byte boundary of the destination). */
+int mm_level_span(void);
+
 /* ---- delivery at another sample rate ----------------------------------------- */
 /* Convert a device-resident signal, interleaved [frames][channels] of `kind` (MM_OUT_I16,
  * or MM_OUT_F32 = the same PCM / 32768: both give the same integers), into d_out
@@ -493,7 +593,10 @@ int mm_resample_span(void);
 /* mm_master_device / mm_master / mm_master_wav with a delivery: the chain runs into a
  * context buffer, the converter writes the caller's output ([frames_out][channels] of
  * job->out_kind; the WAV header carries rate_out and frames_out), then the delivery's
- * ceiling and report act on it, so both hold for what is delivered.  The job must have
+ * level, ceiling and report act on it, so all hold for what is delivered.  Without a
+ * converter (rs == NULL) the chain writes the caller's output ([frames_proc][channels]) and
+ * window is the ceiling's look-ahead at the job's rate.  level_clu != 0 needs `loud`
+ * (MM_ERR_ARG otherwise).  The job must have
  * ceiling_q28 == 0 and meter_on == 0 (MM_ERR_ARG: they would act at the source rate) and
  * rs->rate_in == job->rate.  mm_result is the chain's (frames_out = frames_proc);
  * mm_last_meters and mm_last_ceilings report slot 0 as after mm_master. */

@@ -329,14 +329,25 @@ static int ceiling_device(mm_ctx *c, void *d_pcm, int kind, int64_t frames, int 
     return MM_OK;
 }
 
+// level.hip: the level of a delivered signal, which contains its ceiling
+static int level_device(mm_ctx *c, void *d_pcm, int kind, int64_t frames, int channels, int32_t rate,
+                        const double sos[2][5], int32_t level_clu, int32_t C, int32_t W, mm_level *out,
+                        mm_ceiling *ceil_out);
+
 // The end of a master call for delivered buffer i (results_reset sized the call's results):
-// the ceiling, then the reports, which so measure what is delivered: bit 0 of meter_on the
+// the ceiling, or with a loudness target (level_clu, a delivery's) the level that contains
+// it, then the reports, which so measure what is delivered: bit 0 of meter_on the
 // meter, bit 1 the R 128 report (r128.hip) with the K-weighting sections and the rate of
-// `loud`.  A track that did not ask for what another track of the call asked for leaves a
-// cleared entry.
+// `loud`, which the level takes too.  A track that did not ask for what another track of the
+// call asked for leaves a cleared entry.
 static int finish_delivered(mm_ctx *c, void *d_out, int kind, int64_t frames, int channels, int i, int32_t ceiling_q28,
-                            int32_t window, int meter_on, const mm_job *loud) {
-    if (ceiling_q28) RET(ceiling_device(c, d_out, kind, frames, channels, ceiling_q28, window, &c->ceilings[(size_t)i]));
+                            int32_t window, int meter_on, const mm_job *loud, int32_t level_clu) {
+    if (level_clu) {
+        if (!loud || loud->kweight.nsec != 2)
+            return set_err(c, MM_ERR_ARG, "a loudness target needs a job with the K-weighting sections (kweight.sos)");
+        RET(level_device(c, d_out, kind, frames, channels, loud->rate, loud->kweight.sos, level_clu, ceiling_q28, window,
+                         &c->levels[(size_t)i], ceiling_q28 ? &c->ceilings[(size_t)i] : nullptr));
+    } else if (ceiling_q28) RET(ceiling_device(c, d_out, kind, frames, channels, ceiling_q28, window, &c->ceilings[(size_t)i]));
     else if (!c->ceilings.empty()) c->ceilings[(size_t)i].channels = channels;
     if (meter_on & MM_REPORT_METER) RET(meter_device(c, d_out, kind, frames, channels, loud, &c->meters[(size_t)i]));
     else if (!c->meters.empty()) meter_clear(&c->meters[(size_t)i], 0, channels);

@@ -73,6 +73,8 @@ struct mm_ctx {
     std::vector<mm_r128> r128s;
     // ceilings of the last master call (mm_last_ceilings; empty: no job set one)
     std::vector<mm_ceiling> ceilings;
+    // levels of the last master call (mm_last_levels; empty: its delivery set no loudness target)
+    std::vector<mm_level> levels;
     // the converter's taps on the device ("rs_taps": content key and geometry; key 0: none)
     // and the statistics of the last delivery (mm_last_resample)
     uint64_t rs_key = 0;

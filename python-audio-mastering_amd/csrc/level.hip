@@ -1,0 +1,432 @@
+// level.hip — delivery to an R 128 loudness target under the true-peak ceiling: the static
+// gain that makes the DELIVERED signal read the target on a BS.1770-4 meter with the
+// ceiling held (mm_level in include/mastering.h).  No reference counterpart.  The stage is a
+// short secant search on the one number a delivery spec names: every pass forms its
+// candidate from the kept source (so rounding never accumulates), limits it with
+// ceiling.hip's ceiling_device and measures it with r128.hip's r128_device, both unchanged;
+// the decisions (level_first / level_next) are plain C++ shared with the host restatement
+// mm_level_host, which composes mm_ceiling_host and mm_r128_host the same way.
+//
+// One new kernel, level_gain: s' = clip((s * g + 2^15) >> 16) on the samples as one mono
+// line, src -> dst (src == dst allowed).  It is a streaming kernel (2 or 4 bytes in, as
+// many out, a handful of integer operations a sample), so all that matters is the width of
+// its memory instructions: a lane moves 16 bytes a load and a store (8 int16 or 4 f32), a
+// wave one contiguous 1 KiB run, and a workgroup LEVEL_SPAN samples in LEVEL_SPAN / (256
+// lanes * samples per vector) independent vectors a lane, which are all loaded before the
+// first is stored, non-temporally both ways (every byte is touched once a launch).  One
+// workgroup a span: spans of 16384 samples ran 30 us on the 5-minute track where 8192 ran 35
+// and 4096 more, and a persistent grid-stride form no faster.  The vectors are aligned to the DESTINATION: the up to 15 bytes before
+// the first 16-byte boundary of dst and what is left after the last whole vector are
+// single samples (lanes of workgroup 0), so any sample count and any sample-aligned view
+// is right; when src does not share dst's offset within 16 bytes, the loads alone fall back
+// to single samples (level_device keeps its source copy at the delivered buffer's offset,
+// so the chain never takes that path).  `clipped` is summed and the peak maximised over a
+// wave by shuffles and folded with at most one integer atomic a wave: no result depends on
+// the launch geometry.
+//
+// Included at the end of mastering.hip after r128.hip and ceiling.hip, whose
+// finish_delivered runs a level in the place of the plain ceiling call (it contains it).
+
+namespace mm {
+
+constexpr int LEVEL_ONE = 1 << 16;
+constexpr int LEVEL_GMIN = 1 << 8, LEVEL_GMAX = 1 << 21;  // q()'s clamp: -48.2 .. +30.1 dB
+constexpr int LEVEL_THREADS = 256;
+constexpr int LEVEL_SPAN = 16384;  // samples of whole vectors per workgroup (mm_level_span)
+
+// device result block of one gain launch (zeroed on the stream before it)
+struct LevelDev {
+    unsigned long long clipped;  // products outside the int16 range
+    unsigned peak;               // max |delivered sample|, 0..32768
+    unsigned _pad;
+};
+
+// One sample by g, the definition's clip(((int64)s * g + 2^15) >> 16) in 32-bit pieces: with
+// g = gh * 2^16 + gl (gh <= 32, gl < 2^16), s * g + 2^15 = (s * gh) * 2^16 + (s * gl + 2^15)
+// and the first term is a multiple of 2^16, so the floor is s * gh + ((s * gl + 2^15) >> 16):
+// |s * gl + 2^15| < 2^31 and |s * gh| <= 2^20, both exact in int32, the shift arithmetic.
+// (mm_level_host multiplies in int64 as the definition is written.)
+__device__ __forceinline__ int level_scale(int s, int gh, int gl, unsigned &clipped, int &peak) {
+    const int y = s * gh + ((s * gl + (1 << 15)) >> 16);
+    const int d = min(32767, max(-32768, y));
+    clipped += d != y;
+    peak = max(peak, abs(d));
+    return d;
+}
+
+template <typename T>
+struct LevelVec;
+template <>
+struct LevelVec<int16_t> {
+    typedef short type __attribute__((ext_vector_type(8)));
+};
+template <>
+struct LevelVec<float> {
+    typedef float type __attribute__((ext_vector_type(4)));
+};
+
+// Workgroup b takes the whole vectors [b * VPB, (b + 1) * VPB) of dst + head; workgroup 0
+// also the `head` samples before them (lanes 0 ..) and the tail after the last (lanes 64 ..).
+template <typename T>
+__global__ void __launch_bounds__(LEVEL_THREADS) level_gain_kernel(const T *__restrict__ src, T *__restrict__ dst,
+                                                                    int64_t n, int head, int src_vec, int g,
+                                                                    LevelDev *st) {
+    constexpr int VEC = 16 / (int)sizeof(T);                   // samples per 16-byte vector
+    constexpr int VPL = LEVEL_SPAN / (LEVEL_THREADS * VEC);    // vectors per lane
+    typedef typename LevelVec<T>::type V;
+    static_assert(sizeof(V) == 16 && VPL * LEVEL_THREADS * VEC == LEVEL_SPAN, "a workgroup covers LEVEL_SPAN samples");
+    const int tid = threadIdx.x, gh = g >> 16, gl = g & 0xFFFF;
+    const int64_t nvec = (n - head) / VEC;
+    const int64_t v0 = (int64_t)blockIdx.x * (LEVEL_THREADS * VPL) + tid;
+    unsigned clipped = 0;
+    int peak = 0;
+    V v[VPL];
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) {
+        const int64_t vi = v0 + (int64_t)j * LEVEL_THREADS;
+        if (vi < nvec) {
+            const T *p = src + head + vi * VEC;
+            if (src_vec) {
+                v[j] = __builtin_nontemporal_load(reinterpret_cast<const V *>(p));
+            } else {
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) v[j][k] = p[k];
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) {
+        const int64_t vi = v0 + (int64_t)j * LEVEL_THREADS;
+        if (vi < nvec) {
+            V o;
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) o[k] = pcm_encode<T>(level_scale(pcm_decode<T>((T)v[j][k]), gh, gl, clipped, peak));
+            __builtin_nontemporal_store(o, reinterpret_cast<V *>(dst + head + vi * VEC));
+        }
+    }
+    if (blockIdx.x == 0) {  // the single samples: fewer than VEC at either end
+        const int64_t tail0 = head + nvec * VEC;
+        int64_t i = -1;
+        if (tid < head) i = tid;
+        else if (tid >= 64 && tail0 + (tid - 64) < n) i = tail0 + (tid - 64);
+        if (i >= 0) dst[i] = pcm_encode<T>(level_scale(pcm_decode<T>(src[i]), gh, gl, clipped, peak));
+    }
+    clipped = wave_sum_u32(clipped);
+    peak = wave_max_i32(peak);
+    // at most one atomic of either kind a wave, and none for a peak the block already holds:
+    // thousands of waves on one address serialise (the maximum only grows, so a stale read
+    // costs an atomic, never a result)
+    if ((tid & 63) == 0) {
+        if (clipped) atomicAdd(&st->clipped, (unsigned long long)clipped);
+        if ((unsigned)peak > __atomic_load_n(&st->peak, __ATOMIC_RELAXED)) atomicMax(&st->peak, (unsigned)peak);
+    }
+}
+
+}  // namespace mm
+
+// ======================================================= the rule, host and device alike
+namespace {
+
+constexpr int LEVEL_PASSES = MM_LEVEL_PASSES;
+constexpr double LEVEL_TOL = 0.05, LEVEL_SMIN = 0.25;
+
+// q(G) = clamp(floor(G * 2^16 + 0.5), 2^8, 2^21) (not-a-number and anything below: 2^8)
+int32_t level_q(double G) {
+    const double v = std::floor(G * 65536.0 + 0.5);
+    if (!(v >= (double)LEVEL_GMIN)) return LEVEL_GMIN;
+    return v > (double)LEVEL_GMAX ? LEVEL_GMAX : (int32_t)v;
+}
+
+double level_db(int32_t g) { return 20.0 * std::log10((double)g / 65536.0); }
+
+void level_clear(mm_level *o, int64_t frames, int channels, int rate, int32_t clu, int32_t C, int32_t W) {
+    memset(o, 0, sizeof *o);
+    o->frames = frames;
+    o->channels = channels;
+    o->rate = rate;
+    o->target_clu = clu;
+    o->ceiling_q28 = C;
+    o->window = W;
+    o->status = MM_LEVEL_OFF;
+    o->gain_q16 = LEVEL_ONE;
+    o->min_gain_q16 = LEVEL_ONE;
+    o->source_lufs = o->loudness = NAN;
+    for (double &v : o->pass_lufs) v = NAN;
+}
+
+// g_0 of step 2
+int32_t level_first(const mm_level *o) {
+    return level_q(std::pow(10.0, ((double)o->target_clu / 100.0 - o->source_lufs) / 20.0));
+}
+
+// Steps 4 and 5 after pass k = o->passes - 1 was measured (pass_gain_q16[k] the gain it ran
+// with, pass_lufs[k] its loudness): sets the status and returns 0 when the pass is
+// delivered, else returns the next gain.
+int32_t level_next(mm_level *o, bool capped) {
+    const int k = o->passes - 1;
+    const double T = (double)o->target_clu / 100.0, Ik = o->pass_lufs[k], dk = level_db(o->pass_gain_q16[k]);
+    bool have_m = false;
+    double m = 1.0;
+    if (k >= 1) {
+        const double dp = level_db(o->pass_gain_q16[k - 1]);
+        if (dk != dp) {
+            have_m = true;
+            m = (Ik - o->pass_lufs[k - 1]) / (dk - dp);
+        }
+    }
+    if (std::fabs(T - Ik) <= LEVEL_TOL) o->status = MM_LEVEL_REACHED;
+    else if (capped) o->status = MM_LEVEL_CAPPED;
+    else if (have_m && m < LEVEL_SMIN) o->status = MM_LEVEL_SATURATED;
+    else if (k == LEVEL_PASSES - 1) o->status = MM_LEVEL_PASSES_SPENT;
+    if (o->status != MM_LEVEL_OFF) {
+        o->gain_q16 = o->pass_gain_q16[k];
+        o->loudness = Ik;
+        return 0;
+    }
+    const double slope = have_m ? std::min(m, 1.0) : 1.0;
+    return level_q(((double)o->pass_gain_q16[k] / 65536.0) * std::pow(10.0, (T - Ik) / (20.0 * slope)));
+}
+
+// the boost branch's cap and inner ceiling (step 3, C != 0 and g > ONE)
+int32_t level_boost_cap(int32_t C) { return (int32_t)((((int64_t)C - CEIL_GUARD) << 16) >> 24); }
+int32_t level_inner_ceiling(int32_t C, int32_t g) { return (int32_t)((((int64_t)C - CEIL_GUARD) << 16) / g); }
+
+// the clip-free gain of a signal of sample peak `peak` (step 3, C == 0)
+int32_t level_peak_cap(int32_t peak) {
+    return peak > 0 ? (int32_t)std::min<int64_t>(((int64_t)32767 << 16) / peak, LEVEL_GMAX) : LEVEL_GMAX;
+}
+
+// why the arguments are not a levelling job, or null (C == 0: no ceiling, W is then ignored)
+const char *level_bad_args(int64_t frames, int channels, int rate, int32_t clu, int32_t C, int32_t W) {
+    if (clu < -4000 || clu > -500) return "level_clu out of range [-4000, -500] (-40 .. -5 LUFS)";
+    if (const char *why = r128_refusal(channels, frames, rate)) return why;
+    return C ? ceiling_bad_args(frames, channels, C, W) : nullptr;
+}
+
+// src -> dst by g, queued; the statistics land in *st (zeroed here)
+int level_gain_launch(mm_ctx *c, const void *src, void *dst, int kind, int64_t n, int32_t g, LevelDev *st) {
+    HIPCHK(c, hipMemsetAsync(st, 0, sizeof(LevelDev), c->stream));
+    if (n == 0) return MM_OK;
+    const size_t sb = pcm_sample_bytes(kind);
+    const int head = (int)std::min<int64_t>(n, (int64_t)(((16 - ((uintptr_t)dst & 15)) & 15) / sb));
+    const int src_vec = ((((uintptr_t)src) ^ ((uintptr_t)dst)) & 15) == 0;
+    const int64_t nvec = (n - head) / (int64_t)(16 / sb), vpb = LEVEL_SPAN / (int64_t)(16 / sb);
+    const dim3 grid((unsigned)std::max<int64_t>(1, (nvec + vpb - 1) / vpb)), block(LEVEL_THREADS);
+    return dispatch_pcm(kind, 1, [&](auto, auto t) {  // (pointwise: the samples as one mono line)
+        using T = decltype(t);
+        return launch(c, "level_gain", level_gain_kernel<T>, grid, block, 0, static_cast<const T *>(src), static_cast<T *>(dst), n,
+                      head, src_vec, (int)g, st);
+    });
+}
+
+}  // namespace
+
+// The level on a device-resident signal, in place (synchronous on return).  ceil_out (may be
+// null) receives the final mm_ceiling call at C on the delivered pass when C != 0.
+static int level_device(mm_ctx *c, void *d_pcm, int kind, int64_t frames, int channels, int32_t rate,
+                        const double sos[2][5], int32_t level_clu, int32_t C, int32_t W, mm_level *out,
+                        mm_ceiling *ceil_out) {
+    if (!c || !out || !sos || (frames > 0 && !d_pcm)) return set_err(c, MM_ERR_ARG, "bad arguments");
+    if (!pcm_kind_ok(kind)) return set_err(c, MM_ERR_ARG, PCM_BAD_KIND, kind);
+    if (const char *why = level_bad_args(frames, channels, rate, level_clu, C, W)) return set_err(c, MM_ERR_ARG, "level: %s", why);
+    level_clear(out, frames, channels, rate, level_clu, C, W);
+    mm_ceiling ce_own, ce_in;
+    mm_ceiling *ce = ceil_out ? ceil_out : &ce_own;
+    mm_r128 r;
+    RET(r128_device(c, d_pcm, kind, frames, channels, rate, sos, &r));
+    out->source_lufs = r.integrated;
+    if (!std::isfinite(r.integrated)) {  // fewer than 4 hops, or silence: no gain to find
+        out->status = MM_LEVEL_UNMEASURABLE;
+        if (C) {
+            RET(ceiling_device(c, d_pcm, kind, frames, channels, C, W, ce));
+            out->limited_frames = ce->limited_frames;
+            out->min_gain_q16 = ce->min_gain_q16;
+        }
+        return MM_OK;
+    }
+    // the source, kept at the delivered buffer's offset within 16 bytes (whole-vector loads)
+    const int64_t n = frames * channels;
+    const size_t bytes = pcm_bytes(kind, frames, channels);
+    char *keep;
+    LevelDev *st, hs{};
+    RET(get_buf(c, "level_src", bytes + 16, &keep));
+    RET(get_buf(c, "level_res", 1, &st));
+    char *src = keep + ((uintptr_t)d_pcm & 15);
+    int32_t g_peak = LEVEL_GMAX;
+    if (C) {
+        HIPCHK(c, hipMemcpyAsync(src, d_pcm, bytes, hipMemcpyDeviceToDevice, c->stream));
+    } else {  // the copy through the kernel at ONE (the identity): it brings max |s|
+        RET(level_gain_launch(c, d_pcm, src, kind, n, LEVEL_ONE, st));
+        HIPCHK(c, hipMemcpyAsync(&hs, st, sizeof hs, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        g_peak = level_peak_cap((int32_t)hs.peak);
+    }
+    int32_t g = level_first(out);
+    while (g) {
+        bool capped = false, boost = false;
+        if (!C) {
+            if (g > g_peak) g = g_peak, capped = true;
+            RET(level_gain_launch(c, src, d_pcm, kind, n, g, st));
+        } else if (g <= LEVEL_ONE) {
+            RET(level_gain_launch(c, src, d_pcm, kind, n, g, st));
+        } else {  // the limiter before the boost, so that the boost cannot clip first
+            const int32_t g_cap = level_boost_cap(C);
+            if (g > g_cap) g = g_cap, capped = true;
+            boost = true;
+            HIPCHK(c, hipMemcpyAsync(d_pcm, src, bytes, hipMemcpyDeviceToDevice, c->stream));
+            RET(ceiling_device(c, d_pcm, kind, frames, channels, level_inner_ceiling(C, g), W, &ce_in));
+            RET(level_gain_launch(c, d_pcm, d_pcm, kind, n, g, st));
+        }
+        HIPCHK(c, hipMemcpyAsync(&hs, st, sizeof hs, hipMemcpyDeviceToHost, c->stream));  // (behind the next sync)
+        if (C) {
+            RET(ceiling_device(c, d_pcm, kind, frames, channels, C, W, ce));
+            if (!boost) ce_in = *ce;
+        }
+        RET(r128_device(c, d_pcm, kind, frames, channels, rate, sos, &r));
+        const int k = out->passes++;
+        out->pass_gain_q16[k] = g;
+        out->pass_lufs[k] = r.integrated;
+        out->clipped = (int64_t)hs.clipped;
+        if (C) {
+            out->limited_frames = ce_in.limited_frames;
+            out->min_gain_q16 = ce_in.min_gain_q16;
+        }
+        g = level_next(out, capped);
+    }
+    return MM_OK;
+}
+
+extern "C" {
+
+int mm_level_span(void) { return LEVEL_SPAN; }
+
+int mm_level_device(mm_ctx *c, void *d_pcm, int kind, int64_t frames, int channels, int32_t rate, const double sos[2][5],
+                    int32_t level_clu, int32_t ceiling_q28, int32_t window, mm_level *out, mm_ceiling *ceil_out) {
+    if (!c) return MM_ERR_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    return level_device(c, d_pcm, kind, frames, channels, rate, sos, level_clu, ceiling_q28, window, out, ceil_out);
+}
+
+int mm_level_pcm(mm_ctx *c, void *pcm, int kind, int64_t frames, int channels, int32_t rate, const double sos[2][5],
+                 int32_t level_clu, int32_t ceiling_q28, int32_t window, mm_level *out, mm_ceiling *ceil_out) {
+    if (!c) return MM_ERR_ARG;
+    if (!out || !sos || (frames > 0 && !pcm)) return set_err(c, MM_ERR_ARG, "bad arguments");
+    if (!pcm_kind_ok(kind)) return set_err(c, MM_ERR_ARG, PCM_BAD_KIND, kind);
+    if (const char *why = level_bad_args(frames, channels, rate, level_clu, ceiling_q28, window))
+        return set_err(c, MM_ERR_ARG, "level: %s", why);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t bytes = pcm_bytes(kind, frames, channels);
+    char *dio;
+    RET(pcm_upload(c, "level_io", pcm, bytes, &dio));
+    RET(level_device(c, dio, kind, frames, channels, rate, sos, level_clu, ceiling_q28, window, out, ceil_out));
+    return pcm_download(c, pcm, dio, bytes);
+}
+
+int mm_last_levels(mm_ctx *c, int cap, mm_level *out) {
+    if (!c || cap < 0 || (cap > 0 && !out)) return set_err(c, MM_ERR_ARG, "bad arguments");
+    if (c->levels.empty()) return set_err(c, MM_ERR_STATE, "the last master call set no loudness target");
+    const int n = (int)c->levels.size();
+    for (int i = 0; i < std::min(n, cap); ++i) out[i] = c->levels[(size_t)i];
+    return n;
+}
+
+// The gain kernel alone on host buffers (a per-stage operator, for parity checks): n samples
+// of `kind` by g, through device views that start src_off and dst_off samples (0 .. 7) past
+// a 16-byte boundary; dst_off < 0: in place (src == dst).
+int mm_op_level_gain(mm_ctx *c, const void *in, int kind, int64_t n, int src_off, int dst_off, int32_t g, void *out_pcm,
+                     int64_t *clipped, int32_t *peak) {
+    if (!c) return MM_ERR_ARG;
+    if (!clipped || !peak || (n > 0 && (!in || !out_pcm)) || n < 0 || n >= (int64_t)1 << 32 || src_off < 0 || src_off > 7 ||
+        dst_off > 7)
+        return set_err(c, MM_ERR_ARG, "bad arguments");
+    if (!pcm_kind_ok(kind)) return set_err(c, MM_ERR_ARG, PCM_BAD_KIND, kind);
+    if (g < LEVEL_GMIN || g > LEVEL_GMAX) return set_err(c, MM_ERR_ARG, "level: gain_q16 out of range [2^8, 2^21]");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t sb = pcm_sample_bytes(kind), bytes = (size_t)n * sb;
+    char *a, *b;
+    LevelDev *st, hs{};
+    RET(get_buf(c, "level_op_a", bytes + 64, &a));
+    RET(get_buf(c, "level_op_b", bytes + 64, &b));
+    RET(get_buf(c, "level_res", 1, &st));
+    char *src = a + (size_t)src_off * sb, *dst = dst_off < 0 ? src : b + (size_t)dst_off * sb;
+    if (bytes) HIPCHK(c, hipMemcpyAsync(src, in, bytes, hipMemcpyHostToDevice, c->stream));
+    RET(level_gain_launch(c, src, dst, kind, n, g, st));
+    HIPCHK(c, hipMemcpyAsync(&hs, st, sizeof hs, hipMemcpyDeviceToHost, c->stream));
+    RET(pcm_download(c, out_pcm, dst, bytes));
+    resolve_events(c);
+    *clipped = (int64_t)hs.clipped;
+    *peak = (int32_t)hs.peak;
+    return MM_OK;
+}
+
+// The definition restated in plain C++ on the host (no context, no GPU), in place on
+// interleaved int16: mm_ceiling_host, mm_r128_host and the gain, under the same rule.
+int mm_level_host(int16_t *pcm, int64_t frames, int channels, int32_t rate, const double sos[2][5], int32_t level_clu,
+                  int32_t C, int32_t W, mm_level *out, mm_ceiling *ceil_out) {
+    if (!out || !sos || (frames > 0 && !pcm) || level_bad_args(frames, channels, rate, level_clu, C, W)) return MM_ERR_ARG;
+    level_clear(out, frames, channels, rate, level_clu, C, W);
+    mm_ceiling ce_own, ce_in;
+    mm_ceiling *ce = ceil_out ? ceil_out : &ce_own;
+    mm_r128 r;
+    RET(mm_r128_host(pcm, frames, channels, rate, sos, nullptr, 0, &r));
+    out->source_lufs = r.integrated;
+    if (!std::isfinite(r.integrated)) {
+        out->status = MM_LEVEL_UNMEASURABLE;
+        if (C) {
+            RET(mm_ceiling_host(pcm, frames, channels, C, W, ce));
+            out->limited_frames = ce->limited_frames;
+            out->min_gain_q16 = ce->min_gain_q16;
+        }
+        return MM_OK;
+    }
+    const size_t n = (size_t)(frames * channels);
+    const std::vector<int16_t> src(pcm, pcm + n);
+    int32_t peak = 0;
+    for (size_t i = 0; i < n; ++i) peak = std::max(peak, std::abs((int32_t)src[i]));
+    const int32_t g_peak = level_peak_cap(peak);
+    int64_t clipped = 0;
+    auto gain = [&](const int16_t *from, int32_t g) {  // gain(x, g) as the definition writes it
+        clipped = 0;
+        for (size_t i = 0; i < n; ++i) {
+            const int64_t v = (int64_t)from[i] * g + (1 << 15);
+            const int64_t y = v >= 0 ? v >> 16 : -((-v + 65535) >> 16);  // floor(v / 2^16): the arithmetic shift
+            const int64_t d = std::min<int64_t>(32767, std::max<int64_t>(-32768, y));
+            clipped += d != y;
+            pcm[i] = (int16_t)d;
+        }
+    };
+    int32_t g = level_first(out);
+    while (g) {
+        bool capped = false, boost = false;
+        if (!C) {
+            if (g > g_peak) g = g_peak, capped = true;
+            gain(src.data(), g);
+        } else if (g <= LEVEL_ONE) {
+            gain(src.data(), g);
+        } else {
+            const int32_t g_cap = level_boost_cap(C);
+            if (g > g_cap) g = g_cap, capped = true;
+            boost = true;
+            memcpy(pcm, src.data(), n * sizeof(int16_t));
+            RET(mm_ceiling_host(pcm, frames, channels, level_inner_ceiling(C, g), W, &ce_in));
+            gain(pcm, g);
+        }
+        if (C) {
+            RET(mm_ceiling_host(pcm, frames, channels, C, W, ce));
+            if (!boost) ce_in = *ce;
+        }
+        RET(mm_r128_host(pcm, frames, channels, rate, sos, nullptr, 0, &r));
+        const int k = out->passes++;
+        out->pass_gain_q16[k] = g;
+        out->pass_lufs[k] = r.integrated;
+        out->clipped = clipped;
+        if (C) {
+            out->limited_frames = ce_in.limited_frames;
+            out->min_gain_q16 = ce_in.min_gain_q16;
+        }
+        g = level_next(out, capped);
+    }
+    return MM_OK;
+}
+
+}  // extern "C"

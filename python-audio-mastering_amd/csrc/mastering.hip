@@ -5,8 +5,8 @@
 // both context.h, followed by decode.hip (24/32-bit PCM input).  ops.hip (the
 // per-stage operators) and loudness.hip (the loudness tail, its operator and the
 // time-sharded entry points) follow the chain, before the units that call
-// line_loudness; wav.hip, comm.hip, then pcm16.h, meter.hip, r128.hip, ceiling.hip and resample.hip
-// (with mm_master* / mm_deliver*: a master call with or without a delivery) come at the end.
+// line_loudness; wav.hip, comm.hip, then pcm16.h, meter.hip, r128.hip, ceiling.hip, level.hip and
+// resample.hip (with mm_master* / mm_deliver*: a master call with or without a delivery) come at the end.
 #include <rccl/rccl.h>
 
 #include <algorithm>
@@ -31,9 +31,10 @@ using namespace mm;
 #include "context.h"
 #include "decode.hip"
 
-// ceiling.hip: the end of a master call for delivered buffer i, the ceiling and then the report
+// ceiling.hip: the end of a master call for delivered buffer i, the level (a delivery's) or the
+// ceiling and then the report
 static int finish_delivered(mm_ctx *c, void *d_out, int kind, int64_t frames, int channels, int i, int32_t ceiling_q28,
-                            int32_t window, int meter_on, const mm_job *loud);
+                            int32_t window, int meter_on, const mm_job *loud, int32_t level_clu = 0);
 
 // ------------------------------------------------------- look-back plumbing
 // Transition tables of one filter stage (uploaded only when they change).
@@ -951,12 +952,13 @@ static int unit_complete(mm_ctx *c, const Unit &u, mm_result *res) {
 }
 
 // The per-call results of a master call (mm_last_meters, mm_last_r128, mm_last_ceilings,
-// mm_last_resample): none at its start; before its end one entry for each of the n delivered
-// buffers of what any of them asked for (meter_on: the reports asked for, bits or-ed).
-static void results_reset(mm_ctx *c, int n = 0, bool ceiling = false, int meter_on = 0) {
+// mm_last_levels, mm_last_resample): none at its start; before its end one entry for each of
+// the n delivered buffers of what any of them asked for (meter_on: the reports asked for, bits or-ed).
+static void results_reset(mm_ctx *c, int n = 0, bool ceiling = false, int meter_on = 0, bool level = false) {
     c->meters.assign(meter_on & MM_REPORT_METER ? (size_t)n : 0, mm_meter{});
     c->r128s.assign(meter_on & MM_REPORT_R128 ? (size_t)n : 0, mm_r128{});
     c->ceilings.assign(ceiling ? (size_t)n : 0, mm_ceiling{});
+    c->levels.assign(level ? (size_t)n : 0, mm_level{});
     c->resample_valid = false;
 }
 
@@ -1283,4 +1285,5 @@ int mm_kernel_stats(mm_ctx *c, char *names, int names_cap, double *total_ms, int
 #include "meter.hip"
 #include "r128.hip"
 #include "ceiling.hip"
+#include "level.hip"
 #include "resample.hip"

@@ -311,41 +311,53 @@ static int resample_device(mm_ctx *c, const void *d_in, int kind, int64_t frames
 
 // why (job, delivery) is refused, or null
 static const char *deliver_bad_args(const mm_job *j, const mm_delivery *dl) {
-    if (!j || !dl || !dl->rs) return "null job, delivery or resampler";
+    if (!j || !dl) return "null job or delivery";
     if (j->ceiling_q28 || j->meter_on) return "the job's ceiling_q28 and meter_on act at the source rate: set the delivery's";
     if (j->channels != 1 && j->channels != 2) return "channels must be 1 or 2";
-    if (const char *why = resample_bad_geometry(dl->rs->L, dl->rs->M, dl->rs->K)) return why;
-    if (dl->rs->rate_in != j->rate) return "the resampler's rate_in is not the job's rate";
-    if (const char *why = resample_bad_signal(j->frames_proc, j->channels, dl->rs->L, dl->rs->M)) return why;
-    if (dl->ceiling_q28)
-        return ceiling_bad_args(rs_frames(j->frames_proc, dl->rs->L, dl->rs->M), j->channels, dl->ceiling_q28, dl->window);
+    int64_t frames = j->frames_proc;
+    if (dl->rs) {
+        if (const char *why = resample_bad_geometry(dl->rs->L, dl->rs->M, dl->rs->K)) return why;
+        if (dl->rs->rate_in != j->rate) return "the resampler's rate_in is not the job's rate";
+        if (const char *why = resample_bad_signal(j->frames_proc, j->channels, dl->rs->L, dl->rs->M)) return why;
+        frames = rs_frames(j->frames_proc, dl->rs->L, dl->rs->M);
+    }
+    if (dl->level_clu) {
+        if (!dl->loud || dl->loud->kweight.nsec != 2)
+            return "a loudness target (level_clu) needs `loud`, a job with the K-weighting sections and the rate of the output";
+        return level_bad_args(frames, j->channels, dl->loud->rate, dl->level_clu, dl->ceiling_q28, dl->window);
+    }
+    if (dl->ceiling_q28) return ceiling_bad_args(frames, j->channels, dl->ceiling_q28, dl->window);
     return nullptr;
 }
 
-// what mm_deliver* take a null delivery for: it is refused as one without a resampler
-static const mm_delivery NO_DELIVERY{};
-
-// frames a master call delivers (dl null: no delivery at another rate; else checked)
+// frames a master call delivers (dl null or without a converter: the chain's; else checked)
 static int64_t delivered_frames(const mm_job *j, const mm_delivery *dl) {
-    return dl ? rs_frames(j->frames_proc, dl->rs->L, dl->rs->M) : j->frames_proc;
+    return dl && dl->rs ? rs_frames(j->frames_proc, dl->rs->L, dl->rs->M) : j->frames_proc;
 }
 
 // A master call on device-resident buffers.  Without a delivery (dl null) the plain chain:
-// master_device.  With one, the chain into a context buffer, the converter into d_out, then
-// the ceiling and the report on what is delivered (slot 0 of mm_last_ceilings / _meters).
+// master_device.  With one, the chain into a context buffer and the converter into d_out (no
+// converter: the chain into d_out), then the level or the ceiling and the report on what is
+// delivered (slot 0 of mm_last_levels / _ceilings / _meters).
 static int deliver_device(mm_ctx *c, const mm_job *j, const mm_delivery *dl, const void *d_in, void *d_out,
                           mm_result *res) {
     if (!dl) return master_device(c, j, d_in, d_out, res);
     if (const char *why = deliver_bad_args(j, dl)) return set_err(c, MM_ERR_ARG, "delivery: %s", why);
     const int kind = j->out_kind;
-    char *mid;
-    RET(get_buf(c, "deliver_mid", std::max<size_t>(pcm_bytes(kind, j->frames_proc, j->channels), 1), &mid));
-    RET(master_device(c, j, d_in, mid, res));  // (the job asks for neither: its results stay empty)
-    RET(resample_device(c, mid, kind, j->frames_proc, j->channels, dl->rs, d_out, &c->resample));
-    results_reset(c, 1, dl->ceiling_q28, dl->meter_on);
-    c->resample_valid = true;
-    return finish_delivered(c, d_out, kind, c->resample.frames_out, j->channels, 0, dl->ceiling_q28, dl->window, dl->meter_on,
-                            dl->loud);
+    int64_t frames = j->frames_proc;
+    if (dl->rs) {
+        char *mid;
+        RET(get_buf(c, "deliver_mid", std::max<size_t>(pcm_bytes(kind, j->frames_proc, j->channels), 1), &mid));
+        RET(master_device(c, j, d_in, mid, res));  // (the job asks for neither: its results stay empty)
+        RET(resample_device(c, mid, kind, j->frames_proc, j->channels, dl->rs, d_out, &c->resample));
+        frames = c->resample.frames_out;
+    } else {
+        RET(master_device(c, j, d_in, d_out, res));
+    }
+    results_reset(c, 1, dl->ceiling_q28, dl->meter_on, dl->level_clu);
+    c->resample_valid = dl->rs != nullptr;
+    return finish_delivered(c, d_out, kind, frames, j->channels, 0, dl->ceiling_q28, dl->window, dl->meter_on, dl->loud,
+                            dl->level_clu);
 }
 
 // mm_master and mm_deliver: upload, the call on the device, download.
@@ -382,7 +394,7 @@ static int master_wav(mm_ctx *c, const mm_job *jin, const mm_delivery *dl, const
     RET(wav_stream_in(c, in.f, in_path, &j, &wi, &d_in));
     RET(get_buf(c, "host_out", std::max<size_t>(out_bytes, 1), &d_out));
     RET(deliver_device(c, &j, dl, d_in, d_out, res));
-    return wav_stream_out(c, out_path, j.out_kind, j.channels, dl ? dl->rs->rate_out : j.rate, d_out, out_bytes);
+    return wav_stream_out(c, out_path, j.out_kind, j.channels, dl && dl->rs ? dl->rs->rate_out : j.rate, d_out, out_bytes);
 }
 
 extern "C" {
@@ -456,8 +468,9 @@ int mm_last_resample(mm_ctx *c, mm_resample *out) {
 
 int mm_deliver_device(mm_ctx *c, const mm_job *j, const mm_delivery *dl, const void *d_in, void *d_out, mm_result *res) {
     if (!c) return MM_ERR_ARG;
+    if (!dl) return set_err(c, MM_ERR_ARG, "delivery: null job or delivery");
     HIPCHK(c, hipSetDevice(c->device));
-    return deliver_device(c, j, dl ? dl : &NO_DELIVERY, d_in, d_out, res);
+    return deliver_device(c, j, dl, d_in, d_out, res);
 }
 
 int mm_master(mm_ctx *c, const mm_job *j, const void *in, void *out, mm_result *res) {
@@ -465,7 +478,9 @@ int mm_master(mm_ctx *c, const mm_job *j, const void *in, void *out, mm_result *
 }
 
 int mm_deliver(mm_ctx *c, const mm_job *j, const mm_delivery *dl, const void *in, void *out, mm_result *res) {
-    return c ? master_host(c, j, dl ? dl : &NO_DELIVERY, in, out, res) : MM_ERR_ARG;
+    if (!c) return MM_ERR_ARG;
+    if (!dl) return set_err(c, MM_ERR_ARG, "delivery: null job or delivery");
+    return master_host(c, j, dl, in, out, res);
 }
 
 int mm_master_wav(mm_ctx *c, const mm_job *jin, const char *in_path, const char *out_path, mm_result *res) {

@@ -209,6 +209,15 @@ def ceiling_window(rate: int) -> int:
     return min(CEILING_MAX_WINDOW, max(1, q))
 
 
+def level_clu(lufs: float) -> int:
+    """A delivery's loudness target in LUFS as mm_delivery.level_clu: round(100 * lufs)
+    centi-LU, for lufs in [-40, -5] (include/mastering.h: mm_level; 0 means off there)."""
+    lufs = float(lufs)
+    if not -40.0 <= lufs <= -5.0:  # (NaN fails both comparisons)
+        raise ValueError(f"loudness target {lufs!r} LUFS outside [-40, -5]")
+    return int(round(100.0 * lufs))
+
+
 # The sample-rate converter (include/mastering.h: mm_resampler).  The library convolves
 # integers with the integer taps designed here and never evaluates a window.
 RESAMPLE_MAX_PHASES = 640   # L and M

@@ -68,7 +68,8 @@ class Job:
     def __init__(self, frames_in: int, rate: int, channels: int, params: dict, out_kind: int = native.MM_OUT_I16,
                  seg_bounds=None, check_length: bool = True, single_chunk: bool = False,
                  crossover=(design.LOW_CROSSOVER, design.HIGH_CROSSOVER), report: bool = False,
-                 ceiling_dbtp: float | None = None, output_rate: int | None = None, r128: bool = False):
+                 ceiling_dbtp: float | None = None, output_rate: int | None = None, r128: bool = False,
+                 deliver_lufs: float | None = None):
         """`seg_bounds` (time-sharded ranks, distributed.py): this range's loudness
         segment bounds relative to its first frame; the whole-track gating then
         happens on the host after the all-reduce.  `check_length=False` skips
@@ -90,7 +91,18 @@ class Job:
         converter's limits.  `r128`: the EBU R 128 report of the delivered output (bit 1 of
         meter_on, mm_last_r128; independent of `report`): kweight.sos is then filled whatever
         else is planned; with `output_rate` the bit moves to the delivery, as `report` does;
-        not on a time-sharded range, whose rank does not hold the whole track."""
+        not on a time-sharded range, whose rank does not hold the whole track.
+        `deliver_lufs` (in [-40, -5]): level the delivered output to that EBU R 128 integrated
+        loudness under the ceiling (mm_delivery.level_clu, design.level_clu; mm_level): it plans
+        a delivery, with `output_rate` or without (then without a converter: self.resampler and
+        self.output_rate stay None), to which the ceiling and the reports move, and the `loud`
+        job with the sections of the delivered rate; not on a time-sharded range or a per-stage
+        operator."""
+        if deliver_lufs is not None and (seg_bounds is not None or single_chunk):
+            raise ValueError("a loudness target (deliver_lufs) needs the whole chain: not available on a "
+                             "time-sharded range or a per-stage operator")
+        level = 0 if deliver_lufs is None else design.level_clu(deliver_lufs)
+        self.deliver_lufs = None if deliver_lufs is None else level / 100.0
         if ceiling_dbtp is not None and seg_bounds is not None:
             raise ValueError("the true-peak ceiling needs the whole track: not available on a time-sharded range")
         if r128 and seg_bounds is not None:
@@ -102,8 +114,9 @@ class Job:
                              "range or a per-stage operator")
         self.output_rate = None if output_rate is None else int(output_rate)
         self.resampler = Resampler(rate, output_rate) if output_rate is not None else None
-        plan_report, report = report, bool(report) and output_rate is None  # (a delivery's report is planned below)
-        plan_r128, r128 = bool(r128), bool(r128) and output_rate is None
+        delivers = output_rate is not None or level != 0
+        plan_report, report = report, bool(report) and not delivers  # (a delivery's report is planned below)
+        plan_r128, r128 = bool(r128), bool(r128) and not delivers
         if channels not in (1, 2):
             raise ValueError("only mono and stereo are supported (AME:119,137,152)")
         params = dict(params or {})
@@ -196,17 +209,22 @@ class Job:
             j.block_scale = scale
         self.job = j
         self.frames_out, self.delivery = self.frames_proc, None
-        if self.resampler is not None:  # the ceiling and the report move behind the converter
-            self.frames_out = self.resampler.frames_out(self.frames_proc)
+        if delivers:  # the ceiling and the report move behind the converter and the level
             d = native.MMDelivery()
-            d.rs = ctypes.pointer(self.resampler.rs)
+            out_rate = self.rate
+            if self.resampler is not None:
+                self.frames_out = self.resampler.frames_out(self.frames_proc)
+                d.rs = ctypes.pointer(self.resampler.rs)
+                out_rate = self.output_rate
             d.ceiling_q28, j.ceiling_q28 = j.ceiling_q28, 0
-            d.window = design.ceiling_window(self.output_rate)
+            d.window = design.ceiling_window(out_rate)
             d.meter_on = (native.REPORT_METER if plan_report else 0) | (native.REPORT_R128 if plan_r128 else 0)
-            # the output's loudness, as meter_pcm plans it, and the sections of the output's rate for the R 128 report
-            if (plan_report and self.frames_out >= 0.4 * self.output_rate) or plan_r128:
-                self._loud = Job(self.frames_out, self.output_rate, self.channels, {}, single_chunk=True,
-                                 report=bool(plan_report), r128=plan_r128)
+            d.level_clu = level
+            # the output's loudness, as meter_pcm plans it, and the sections of the output's rate for the
+            # R 128 report and the level
+            if (plan_report and self.frames_out >= 0.4 * out_rate) or plan_r128 or level:
+                self._loud = Job(self.frames_out, out_rate, self.channels, {}, single_chunk=True,
+                                 report=bool(plan_report), r128=plan_r128 or bool(level))
                 d.loud = ctypes.pointer(self._loud.job)
             self.delivery = d
 
@@ -364,6 +382,54 @@ def ceilings(ctx: native.Context, cap: int = native.BATCH_STREAMS) -> list:
     return _last(ctx, "mm_last_ceilings", native.MMCeiling, cap)
 
 
+def level_dict(m: native.MMLevel) -> dict:
+    """An mm_level as `info["level"]`: the struct's integers, the status as a word
+    (native.LEVEL_STATUS), the target, the source's and the delivered loudness in LUFS (None
+    where the struct holds NaN or -inf: unmeasurable), the delivered gain and the limiter's
+    largest reduction in dB, and the per-pass gains (dB) and loudness cut to `passes`.
+    No reference counterpart."""
+    def val(x):
+        return float(x) if math.isfinite(x) else None
+    n = int(m.passes)
+    d = {f: int(getattr(m, f)) for f in ("frames", "channels", "rate", "target_clu", "ceiling_q28", "window", "passes",
+                                         "gain_q16", "min_gain_q16", "clipped", "limited_frames")}
+    d["status"] = native.LEVEL_STATUS[int(m.status)]
+    d["target_lufs"] = d["target_clu"] / 100.0
+    d["source_lufs"], d["loudness"] = val(m.source_lufs), val(m.loudness)
+    d["gain_db"] = _db(d["gain_q16"] / 65536.0)
+    d["max_reduction_db"] = -_db(d["min_gain_q16"] / 65536.0)
+    d["pass_gain_q16"] = [int(m.pass_gain_q16[k]) for k in range(n)]
+    d["pass_gain_db"] = [_db(g / 65536.0) for g in d["pass_gain_q16"]]
+    d["pass_lufs"] = [val(m.pass_lufs[k]) for k in range(n)]
+    return d
+
+
+def levels(ctx: native.Context, cap: int = 1) -> list:
+    """The mm_level of the context's last master call (mm_last_levels): one for a call planned
+    with `deliver_lufs`.  RuntimeError if that call set no loudness target."""
+    return _last(ctx, "mm_last_levels", native.MMLevel, cap)
+
+
+def level_pcm(pcm: np.ndarray, rate: int, target_lufs: float, ceiling_dbtp: float | None = None,
+              window: int | None = None, device: int = 0):
+    """Level an int16 (or float32 = int16 / 32768) array [N] or [N, ch] to `target_lufs` (EBU
+    R 128 integrated, in [-40, -5]) under the true-peak ceiling `ceiling_dbtp` (None: no
+    ceiling, the gain is then capped where a sample would clip) without mastering it
+    (mm_level_pcm): returns (a new array, level_dict).  `window`: the ceiling's look-ahead
+    frames (default design.ceiling_window(rate))."""
+    ch = 1 if pcm.ndim == 1 else pcm.shape[1]
+    x, kind = _out_kind(pcm)
+    x = x.copy()
+    C = 0 if ceiling_dbtp is None else design.ceiling_q28(ceiling_dbtp)
+    w = design.ceiling_window(rate) if window is None else int(window)
+    ctx = native.context(device)
+    m = native.MMLevel()
+    ctx.check(ctx.lib.mm_level_pcm(ctx.ptr, x.ctypes.data_as(ctypes.c_void_p), kind, x.shape[0], ch, int(rate),
+                                   kweight_sos(rate), design.level_clu(target_lufs), C, w, ctypes.byref(m), None),
+              "mm_level_pcm")
+    return x, level_dict(m)
+
+
 def resample_dict(m: native.MMResample) -> dict:
     """An mm_resample as `info["resample"]`: the struct's integers (clipped and peak as
     per-channel lists) and the largest delivered sample in dBFS.  No reference counterpart."""
@@ -376,11 +442,13 @@ def resample_dict(m: native.MMResample) -> dict:
 
 
 def _finish_info(info: dict, job: "Job", ctx: native.Context) -> dict:
-    """The chain's info with what the end of the master call added: the ceiling and the
-    report of the delivered signal and, for a delivery at another rate, the delivered
-    frames and rate and the converter's statistics."""
+    """The chain's info with what the end of the master call added: the level, the ceiling
+    and the report of the delivered signal and, for a delivery at another rate, the
+    delivered frames and rate and the converter's statistics."""
     end = job.job if job.delivery is None else job.delivery  # who carries ceiling_q28 and meter_on
-    if job.delivery is not None:
+    if job.delivery is not None and job.delivery.level_clu:
+        info["level"] = level_dict(levels(ctx, 1)[0])
+    if job.resampler is not None:
         m = native.MMResample()
         ctx.check(ctx.lib.mm_last_resample(ctx.ptr, ctypes.byref(m)), "mm_last_resample")
         info["frames"], info["rate"], info["resample"] = job.frames_out, job.output_rate, resample_dict(m)
@@ -459,15 +527,19 @@ def master_pcm(pcm: np.ndarray, rate: int, params: dict, out_kind: int = native.
     the report then act on the converted signal, out_pcm has info['frames'] frames at
     info['rate'] and info['resample'] (resample_dict) is added; absent or equal to `rate`,
     the call is exactly the call without it.  params['r128'] (truthy; independent of
-    'report') adds info['r128'] (r128_dict): the EBU R 128 figures of the delivered output."""
+    'report') adds info['r128'] (r128_dict): the EBU R 128 figures of the delivered output.
+    params['deliver_lufs'] (in [-40, -5]) levels the delivered output, at either rate, to
+    that R 128 integrated loudness with the ceiling held and adds info['level']
+    (level_dict); absent or None, the call is exactly the call without it."""
     ch = 1 if pcm.ndim == 1 else pcm.shape[1]
     params = dict(params or {})
     report = bool(params.pop("report", False))
     ceiling = params.pop("ceiling_dbtp", None)
     output_rate = params.pop("output_rate", None)
     r128 = bool(params.pop("r128", False))
+    deliver_lufs = params.pop("deliver_lufs", None)
     job = Job(pcm.shape[0], rate, ch, params, out_kind, report=report, ceiling_dbtp=ceiling, output_rate=output_rate,
-              r128=r128)
+              r128=r128, deliver_lufs=deliver_lufs)
     x, job.job.in_kind = _device_input(pcm, wide=True)
     shape = (job.frames_out,) if ch == 1 else (job.frames_out, ch)
     out = np.empty(shape, np.int16 if out_kind == native.MM_OUT_I16 else np.float32)
@@ -497,7 +569,8 @@ def master_device(ctx: native.Context, job: Job, d_in: int, d_out: int, res: nat
     with `report=True` is metered: `meters(ctx)[0]` (see report_dict); one planned with
     `ceiling_dbtp` is held under it first: `ceilings(ctx)[0]` (see ceiling_dict).  One planned
     with `output_rate` is delivered at that rate (mm_deliver_device): `d_out` then holds
-    `job.frames_out` frames.  One planned with `r128=True`: `r128s(ctx)[0]` (see r128_dict)."""
+    `job.frames_out` frames.  One planned with `r128=True`: `r128s(ctx)[0]` (see r128_dict).
+    One planned with `deliver_lufs` is delivered too, levelled: `levels(ctx)[0]` (see level_dict)."""
     if job.delivery is not None:
         ctx.check(ctx.lib.mm_deliver_device(ctx.ptr, ctypes.byref(job.job), ctypes.byref(job.delivery),
                                             ctypes.c_void_p(d_in), ctypes.c_void_p(d_out),
@@ -519,6 +592,9 @@ def master_batch(ctx: native.Context, jobs, d_ins, d_outs, with_results: bool = 
     planned with `ceiling_dbtp` are held under it: `ceilings(ctx, len(jobs))`; jobs planned
     with `r128=True` get their R 128 report: `r128s(ctx, len(jobs))`."""
     n = len(jobs)
+    if any(j.delivery is not None and j.delivery.level_clu for j in jobs):
+        raise ValueError("a loudness target (deliver_lufs) re-measures one delivered track pass by pass: "
+                         "not available for a batch")
     if any(j.delivery is not None for j in jobs):
         raise ValueError("delivery at another rate (output_rate) is not available for a batch")
     arr = (native.MMJob * n)(*[j.job for j in jobs])
@@ -542,6 +618,8 @@ def process(input_path: str, output_path: str, params: dict, device: int = 0, ve
     the header carries it and info['frames'] / info['rate'] / info['resample'] describe the
     written file; the ceiling and the report act on the converted samples.
     params['r128'] (truthy) adds info['r128'] (r128_dict), the EBU R 128 figures of the written samples.
+    params['deliver_lufs'] levels the written samples to that R 128 integrated loudness under the
+    ceiling (info['level'], level_dict).
     Raises ValueError for unreadable/unsupported input and RuntimeError for device
     failures, like the reference (AME:110-113)."""
     params = dict(params or {})
@@ -550,12 +628,13 @@ def process(input_path: str, output_path: str, params: dict, device: int = 0, ve
     ceiling = params.pop("ceiling_dbtp", None)
     output_rate = params.pop("output_rate", None)
     r128 = bool(params.pop("r128", False))
+    deliver_lufs = params.pop("deliver_lufs", None)
     kind = native.MM_OUT_F32 if fmt == "f32" else native.MM_OUT_I16
     wi = wav_info(input_path, device)
     if verbose:
         print(f"Loaded {input_path}: {wi.frames} frames @ {wi.rate} Hz")
     job = Job(wi.frames, wi.rate, wi.channels, params, kind, report=report, ceiling_dbtp=ceiling,
-              output_rate=output_rate, r128=r128)
+              output_rate=output_rate, r128=r128, deliver_lufs=deliver_lufs)
     ctx = native.context(device)
     res = native.MMResult()
     if job.delivery is not None:

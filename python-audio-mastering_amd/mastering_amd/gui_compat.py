@@ -73,13 +73,23 @@ def ceiling_line(ceiling: dict) -> str:
             f"{ceiling['tp_out_dbtp']:+.2f} dBTP, up to {ceiling['max_reduction_db']:.2f} dB reduction")
 
 
+def level_line(level: dict) -> str:
+    """One status line for a loudness target (engine.level_dict):
+    `Level -14.00 LUFS: reached, delivered -14.02 LUFS with +3.41 dB in 2 passes`."""
+    loud = level.get("loudness")
+    got = f"delivered {loud:.2f} LUFS with {level['gain_db']:+.2f} dB in {level['passes']} passes" \
+        if loud is not None else "nothing to measure"
+    return f"Level {level['target_lufs']:.2f} LUFS: {level['status']}, {got}"
+
+
 def process_audio(settings: dict, status_callback=None, device: int = 0):
     """Master settings['input_file'] into settings['output_file'] (mastering_gui.py:192-206).
     Reports through `status_callback`; returns the engine's info dict, or None on error.
     With a truthy settings['report'] the delivered output is metered (info['report'])
     and one extra status line (report_line) precedes the completion message; with
     settings['ceiling_dbtp'] the output is held under that true-peak ceiling
-    (info['ceiling']) and ceiling_line is reported before it."""
+    (info['ceiling']) and ceiling_line is reported before it; with settings['deliver_lufs']
+    it is levelled to that R 128 loudness (info['level']) and level_line comes first."""
     cb = _status(status_callback)
     src, dst = (settings or {}).get("input_file"), (settings or {}).get("output_file")
     if not src or not dst:
@@ -91,6 +101,8 @@ def process_audio(settings: dict, status_callback=None, device: int = 0):
     except Exception as e:  # the GUI shows the message; AME:110-113 re-raises to its caller
         cb(f"Error: {e}")
         return None
+    if isinstance(info, dict) and info.get("level"):
+        cb(level_line(info["level"]))
     if isinstance(info, dict) and info.get("ceiling"):
         cb(ceiling_line(info["ceiling"]))
     if isinstance(info, dict) and info.get("report"):

@@ -193,6 +193,9 @@ def master_pcm(pcm: np.ndarray, rate: int, settings: dict, device: int = 0) -> n
     settings = dict(settings or {})
     if settings.get("r128"):
         raise ValueError("the R 128 report belongs to the mastering chain's delivery: not available in the legacy profile")
+    if settings.get("deliver_lufs") is not None:
+        raise ValueError("a loudness target (deliver_lufs) belongs to the mastering chain's delivery: not available "
+                         "in the legacy profile")
     n = pcm.shape[0]
     chunks = []
     bounds = design.chunk_bounds(n, rate)
@@ -222,6 +225,9 @@ def master_pcm(pcm: np.ndarray, rate: int, settings: dict, device: int = 0) -> n
 
 def process(input_path: str, output_path: str, settings: dict, device: int = 0) -> dict:
     """main.py:46-72 with local files: decode a 16-bit WAV, master, export WAV."""
+    if (settings or {}).get("deliver_lufs") is not None:  # (before the file is read)
+        raise ValueError("a loudness target (deliver_lufs) belongs to the mastering chain's delivery: not available "
+                         "in the legacy profile")
     pcm, rate = wavio.read_wav(input_path)
     if pcm.dtype != np.int16:
         raise ValueError("the legacy profile takes 16-bit PCM WAV (what pydub decodes it to)")

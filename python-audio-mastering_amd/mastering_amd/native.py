@@ -112,7 +112,20 @@ class MMResample(ctypes.Structure):
 
 class MMDelivery(ctypes.Structure):
     _fields_ = [("rs", ctypes.POINTER(MMResampler)), ("ceiling_q28", ctypes.c_int32), ("window", ctypes.c_int32),
-                ("meter_on", ctypes.c_int32), ("_pad", ctypes.c_int32), ("loud", ctypes.POINTER(MMJob))]
+                ("meter_on", ctypes.c_int32), ("level_clu", ctypes.c_int32), ("loud", ctypes.POINTER(MMJob))]
+
+
+LEVEL_PASSES = 5  # MM_LEVEL_PASSES
+LEVEL_STATUS = ("off", "reached", "capped", "saturated", "passes", "unmeasurable")  # MM_LEVEL_* by value
+
+
+class MMLevel(ctypes.Structure):
+    _fields_ = [("frames", ctypes.c_int64), ("channels", ctypes.c_int32), ("rate", ctypes.c_int32),
+                ("target_clu", ctypes.c_int32), ("ceiling_q28", ctypes.c_int32), ("window", ctypes.c_int32),
+                ("status", ctypes.c_int32), ("passes", ctypes.c_int32), ("gain_q16", ctypes.c_int32),
+                ("pass_gain_q16", ctypes.c_int32 * LEVEL_PASSES), ("min_gain_q16", ctypes.c_int32),
+                ("source_lufs", ctypes.c_double), ("pass_lufs", ctypes.c_double * LEVEL_PASSES),
+                ("loudness", ctypes.c_double), ("clipped", ctypes.c_int64), ("limited_frames", ctypes.c_int64)]
 
 
 ABI_VERSION = 5  # MM_ABI_VERSION of include/mastering.h
@@ -144,7 +157,8 @@ EXPORTS = ("mm_create", "mm_destroy", "mm_last_error", "mm_sync", "mm_version", 
            "mm_ceiling_max_window",
            "mm_pcm_decode_device", "mm_op_pcm_decode", "mm_pcm_decode_host", "mm_pcm_decode_span",
            "mm_resample_device", "mm_resample_pcm", "mm_resample_host", "mm_resample_frames", "mm_resample_span",
-           "mm_last_resample", "mm_deliver_device", "mm_deliver", "mm_deliver_wav")
+           "mm_last_resample", "mm_deliver_device", "mm_deliver", "mm_deliver_wav",
+           "mm_level_device", "mm_level_pcm", "mm_level_host", "mm_op_level_gain", "mm_last_levels", "mm_level_span")
 
 _lib = None
 _lock = threading.Lock()
@@ -269,6 +283,16 @@ def load():
             "mm_deliver": ([vp, P(MMJob), P(MMDelivery), vp, vp, P(MMResult)], ctypes.c_int),
             "mm_deliver_wav": ([vp, P(MMJob), P(MMDelivery), ctypes.c_char_p, ctypes.c_char_p, P(MMResult)],
                                ctypes.c_int),
+            "mm_level_device": ([vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int32, c_sos_p,
+                                 ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, P(MMLevel), P(MMCeiling)], ctypes.c_int),
+            "mm_level_pcm": ([vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int32, c_sos_p,
+                              ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, P(MMLevel), P(MMCeiling)], ctypes.c_int),
+            "mm_level_host": ([P(ctypes.c_int16), ctypes.c_int64, ctypes.c_int, ctypes.c_int32, c_sos_p,
+                               ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, P(MMLevel), P(MMCeiling)], ctypes.c_int),
+            "mm_op_level_gain": ([vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int32, vp,
+                                  c_int64_p, P(ctypes.c_int32)], ctypes.c_int),
+            "mm_last_levels": ([vp, ctypes.c_int, P(MMLevel)], ctypes.c_int),
+            "mm_level_span": ([], ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             fn = getattr(lib, name)

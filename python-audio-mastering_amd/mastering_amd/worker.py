@@ -10,7 +10,8 @@ written (renamed into place), so a poller never sees a partial file.  With a tru
 ``settings["report"]`` (no reference counterpart) the mastering report of the written
 file goes to ``<output>.report.json`` before the marker, and with
 ``settings["ceiling_dbtp"]`` what the true-peak ceiling did goes to
-``<output>.ceiling.json`` the same way.
+``<output>.ceiling.json`` the same way, and with ``settings["deliver_lufs"]`` what the
+levelling stage did (status, passes, achieved loudness) to ``<output>.level.json``.
 
 ``wsgi_app`` is the handler as a plain WSGI callable (what gunicorn serves the
 reference's Flask app as), so no web framework is needed; ``handle_push`` is the
@@ -84,7 +85,7 @@ def process_audio_from_gcs(gcs_uri: str, settings: dict, root: str | None = None
             if os.path.exists(tmp):
                 os.remove(tmp)
         print(f"Exporting and uploading processed audio to {out_name}...")
-        for key in ("ceiling", "report"):  # part, then replace: a poller never sees half a file
+        for key in ("level", "ceiling", "report"):  # part, then replace: a poller never sees half a file
             if isinstance(info, dict) and info.get(key):
                 with open(f"{dst}.{key}.json.part", "w") as f:
                     json.dump(_json_safe(info[key]), f, indent=1, sort_keys=True)
