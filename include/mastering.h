@@ -420,7 +420,10 @@ int mm_sync(mm_ctx *ctx);
    mm_delivery's pad (a caller that zeroed it gets what it got): mm_delivery.level_clu, a
    delivery without a converter (rs == NULL), mm_level and the level entry points
    (mm_level_device, mm_level_pcm, mm_level_host, mm_op_level_gain, mm_last_levels,
-   mm_level_span).  A caller built against an older header must
+   mm_level_span); and, as entry points only (no struct added or changed), the album
+   (mm_r128_album_from_hops, mm_album_level_host, mm_album_r128_device, mm_album_r128_pcm,
+   mm_op_r128_album_hops, mm_album_level_device, mm_album_level_pcm, mm_last_album).  A caller
+   built against an older header must
    refuse a library whose version differs from its own MM_ABI_VERSION. */
 #define MM_ABI_VERSION 5
 int mm_version(void);
@@ -571,6 +574,87 @@ int mm_last_levels(mm_ctx *ctx, int cap, mm_level *out);
 /* Samples one workgroup of the gain kernel covers in whole 16-byte vectors (its seams lie
  * at multiples of this past the first 16-byte boundary of the destination). */
 int mm_level_span(void);
+
+/* ---- an album levelled as one programme -------------------------------------- */
+/* One static gain for all tracks of an album: the album, measured as one programme, reads the
+ * target, every track is held under the true-peak ceiling, and the loudness differences
+ * between the tracks are kept (the album mode of ReplayGain 2.0 / EBU R 128 tools, which pool
+ * the gating blocks of several programmes and never form a block across two of them).  No
+ * reference counterpart.
+ * The tracks are s_0 .. s_(n-1) on the int16 grid, 1 <= n <= MM_ALBUM_TRACKS, of N_t frames,
+ * all of one rate, one channel count (1 or 2) and one PCM kind; mm_r128 / mm_ceiling accept
+ * each of them alone, and the total frame count is below 2^31.
+ *
+ * Album R 128 figures (they generalise mm_r128_from_hops):
+ *   - Track t has hop energies e_t[0 .. H_t) exactly as mm_r128 defines them (steps 1-2).
+ *   - For w = 4 and w = 30 its windows z_(t,w)[j], l_(t,w)[j], j < H_t - w + 1, are those of
+ *     step 3 on e_t alone: no window spans two tracks; a track with H_t < w contributes none.
+ *   - The pool P_w is the tracks' windows back to back in track order.
+ *   - momentary_max, relative_gate, integrated and momentary_blocks come from P_4 (steps 4-5);
+ *     short_term_max, short_term_blocks, lra, lra_low, lra_high and lra_blocks from P_30
+ *     (steps 4 and 6).  The gates and the percentile rule are mm_r128's, the sums running
+ *     sequentially over the pool in pool order.
+ *   - hops = sum H_t, frames = sum N_t.
+ *   - P_4 empty: integrated is NaN; nothing above -70: -inf (as step 7).
+ *   - With n = 1 every field equals mm_r128_from_hops' bit for bit.
+ *
+ * Album level: mm_level's rule with I(.) the album integrated loudness and y_k formed PER
+ * TRACK from that track's kept source by the one gain g_k:
+ *   - I_src not finite: UNMEASURABLE, each track then only gets its ceiling (ceil(s_t, C, W)).
+ *   - C = 0: g_k is capped at g_peak = min(floor(32767 * 2^16 / max_t max|s_t|), 2^21);
+ *     track t is gain(s_t, g_k).
+ *   - C != 0, g_k <= ONE: track t is ceil(gain(s_t, g_k), C, W).
+ *   - C != 0, g_k > ONE: track t is ceil(gain(ceil(s_t, C', W), g_k), C, W); C' and the cap on
+ *     g_k are mm_level's: they do not depend on the track.
+ *   - Steps 4 and 5 of mm_level decide, unchanged.
+ *   - A track too short to have a window of its own still gets the gain and the ceiling.
+ * In the resulting mm_level, frames, clipped and limited_frames are sums over the tracks and
+ * min_gain_q16 is the minimum; the two limiter figures come from the limiting ceil call of
+ * the delivered pass, as in mm_level. */
+#define MM_ALBUM_TRACKS 256
+/* The album R 128 figures from the tracks' hop energies back to back, e[0, sum track_hops), in
+ * plain C++ (no context, no GPU): every field but frames and channels.  MM_ERR_ARG for a null
+ * pointer, n outside [1, MM_ALBUM_TRACKS], a negative hop count or rate < 2000. */
+int mm_r128_album_from_hops(const double *e, const int64_t *track_hops, int n, int32_t rate, mm_r128 *out);
+/* The album level restated in plain C++ on the host (no context, no GPU), in place on n
+ * interleaved int16 tracks: mm_ceiling_host, mm_r128_host and the gain composed as
+ * mm_level_host composes them.  *album and track_r128[n] (may be NULL) describe what was
+ * delivered; track_ceil[n] (may be NULL) receives, when C != 0, every track's final
+ * mm_ceiling call at C.  MM_ERR_ARG as mm_album_level_device. */
+int mm_album_level_host(int16_t *const *pcm, const int64_t *frames, int n, int channels, int32_t rate,
+                        const double sos[2][5], int32_t level_clu, int32_t ceiling_q28, int32_t window, mm_level *out,
+                        mm_r128 *album, mm_r128 *track_r128, mm_ceiling *track_ceil);
+/* The album R 128 report of n device-resident tracks, interleaved [frames[t]][channels] of
+ * `kind`: every track is K-weighted in ONE launch and all hops are reduced in one more, with
+ * one read-back.  The per-track reports are left behind mm_last_r128 (n, in track order).
+ * MM_ERR_ARG, with words in mm_last_error and before anything is queued, for n outside
+ * [1, MM_ALBUM_TRACKS], a track mm_r128_device refuses or a total of 2^31 frames or more.
+ * The audio is never altered.  Synchronous on return. */
+int mm_album_r128_device(mm_ctx *ctx, const void *const *d_pcm, int kind, const int64_t *frames, int n, int channels,
+                         int32_t rate, const double sos[2][5], mm_r128 *out);
+/* The same on host buffers. */
+int mm_album_r128_pcm(mm_ctx *ctx, const void *const *pcm, int kind, const int64_t *frames, int n, int channels,
+                      int32_t rate, const double sos[2][5], mm_r128 *out);
+/* The album pass's hop energies themselves for host buffers, track after track (a per-stage
+ * operator, for parity checks): copies the first min(sum H_t, cap) and returns sum H_t.  A
+ * track's hops equal mm_op_r128_hops' of that track alone. */
+int mm_op_r128_album_hops(mm_ctx *ctx, const void *const *pcm, int kind, const int64_t *frames, int n, int channels,
+                          int32_t rate, const double sos[2][5], double *hops_host, int64_t cap);
+/* Level n device-resident tracks in place as one album (the album level above) to level_clu
+ * under ceiling_q28 (0: none; window as mm_ceiling_device).  The mm_level and the album's
+ * mm_r128 are left behind mm_last_album, the per-track reports of the delivered tracks behind
+ * mm_last_r128 and, with a ceiling, mm_last_ceilings (n each, in track order).  MM_ERR_ARG,
+ * with words in mm_last_error, before anything is queued and with the context still usable,
+ * for n outside [1, MM_ALBUM_TRACKS], a track mm_level_device refuses, level_clu outside
+ * [-4000, -500] or a total of 2^31 frames or more.  Synchronous on return. */
+int mm_album_level_device(mm_ctx *ctx, void *const *d_pcm, int kind, const int64_t *frames, int n, int channels,
+                          int32_t rate, const double sos[2][5], int32_t level_clu, int32_t ceiling_q28, int32_t window);
+/* The same on host buffers, in place. */
+int mm_album_level_pcm(mm_ctx *ctx, void *const *pcm, int kind, const int64_t *frames, int n, int channels, int32_t rate,
+                       const double sos[2][5], int32_t level_clu, int32_t ceiling_q28, int32_t window);
+/* The result of the last mm_album_level_* call on this context.  MM_ERR_STATE if the last
+ * call levelled no album. */
+int mm_last_album(mm_ctx *ctx, mm_level *level, mm_r128 *album);
 
 /* ---- delivery at another sample rate ----------------------------------------- */
 /* Convert a device-resident signal, interleaved [frames][channels] of `kind` (MM_OUT_I16,

@@ -75,6 +75,10 @@ struct mm_ctx {
     std::vector<mm_ceiling> ceilings;
     // levels of the last master call (mm_last_levels; empty: its delivery set no loudness target)
     std::vector<mm_level> levels;
+    // the album level of the last call (mm_last_album; empty: it levelled no album): the level and
+    // the album's R 128 report; the per-track reports are r128s and ceilings above
+    std::vector<mm_level> albums;
+    std::vector<mm_r128> album_r128s;
     // the converter's taps on the device ("rs_taps": content key and geometry; key 0: none)
     // and the statistics of the last delivery (mm_last_resample)
     uint64_t rs_key = 0;

@@ -203,9 +203,9 @@ const char *level_bad_args(int64_t frames, int channels, int rate, int32_t clu, 
     return C ? ceiling_bad_args(frames, channels, C, W) : nullptr;
 }
 
-// src -> dst by g, queued; the statistics land in *st (zeroed here)
-int level_gain_launch(mm_ctx *c, const void *src, void *dst, int kind, int64_t n, int32_t g, LevelDev *st) {
-    HIPCHK(c, hipMemsetAsync(st, 0, sizeof(LevelDev), c->stream));
+// src -> dst by g, queued; the statistics are folded into *st, which the caller zeroed on the
+// stream (album.hip zeroes one array of them once a pass)
+int level_gain_queue(mm_ctx *c, const void *src, void *dst, int kind, int64_t n, int32_t g, LevelDev *st) {
     if (n == 0) return MM_OK;
     const size_t sb = pcm_sample_bytes(kind);
     const int head = (int)std::min<int64_t>(n, (int64_t)(((16 - ((uintptr_t)dst & 15)) & 15) / sb));
@@ -217,6 +217,12 @@ int level_gain_launch(mm_ctx *c, const void *src, void *dst, int kind, int64_t n
         return launch(c, "level_gain", level_gain_kernel<T>, grid, block, 0, static_cast<const T *>(src), static_cast<T *>(dst), n,
                       head, src_vec, (int)g, st);
     });
+}
+
+// the same with *st zeroed here
+int level_gain_launch(mm_ctx *c, const void *src, void *dst, int kind, int64_t n, int32_t g, LevelDev *st) {
+    HIPCHK(c, hipMemsetAsync(st, 0, sizeof(LevelDev), c->stream));
+    return level_gain_queue(c, src, dst, kind, n, g, st);
 }
 
 }  // namespace

@@ -5,8 +5,9 @@
 // both context.h, followed by decode.hip (24/32-bit PCM input).  ops.hip (the
 // per-stage operators) and loudness.hip (the loudness tail, its operator and the
 // time-sharded entry points) follow the chain, before the units that call
-// line_loudness; wav.hip, comm.hip, then pcm16.h, meter.hip, r128.hip, ceiling.hip, level.hip and
-// resample.hip (with mm_master* / mm_deliver*: a master call with or without a delivery) come at the end.
+// line_loudness; wav.hip, comm.hip, then pcm16.h, meter.hip, r128.hip, ceiling.hip, level.hip,
+// resample.hip (with mm_master* / mm_deliver*: a master call with or without a delivery) and album.hip
+// come at the end.
 #include <rccl/rccl.h>
 
 #include <algorithm>
@@ -959,6 +960,8 @@ static void results_reset(mm_ctx *c, int n = 0, bool ceiling = false, int meter_
     c->r128s.assign(meter_on & MM_REPORT_R128 ? (size_t)n : 0, mm_r128{});
     c->ceilings.assign(ceiling ? (size_t)n : 0, mm_ceiling{});
     c->levels.assign(level ? (size_t)n : 0, mm_level{});
+    c->albums.clear();
+    c->album_r128s.clear();
     c->resample_valid = false;
 }
 
@@ -1287,3 +1290,4 @@ int mm_kernel_stats(mm_ctx *c, char *names, int names_cap, double *total_ms, int
 #include "ceiling.hip"
 #include "level.hip"
 #include "resample.hip"
+#include "album.hip"

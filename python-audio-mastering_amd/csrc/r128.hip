@@ -6,7 +6,8 @@
 //
 // The definition has one tail, mm_r128_from_hops (steps 3-7 on the 0.1 s hop energies),
 // which the host restatement (mm_r128_host: the sequential filter) and the GPU path both
-// end in: they differ in e[] only.
+// end in: they differ in e[] only.  Its steps 4-7 are r128_figures, which an album's pooled
+// windows end in too (album.hip).
 //
 // The GPU pass is ONE launch of the K-weighting with lookback.h's carry, a lane per tile of
 // R128_TILE frames, followed by a fixed-order reduction of the tile partials to the hops
@@ -110,14 +111,17 @@ __device__ __forceinline__ void r128_pass(const R128Args &a, const T *__restrict
     }
 }
 
+// One workgroup of the K-weighting pass on one line (a track): `blk` its logical block of the
+// launch (the look-back's index), g0 its first tile counted from the line's start, a.part /
+// a.part_hop the line's own partials.  The line's first tile resets the carry, so a block
+// waits on predecessors back to the line's first block only, which publishes an inclusive
+// prefix at once: what a workgroup computes depends on its line alone, wherever the line
+// lies in the launch (the album pass below puts many lines into one).
 template <int CH, typename T>
-__global__ void __launch_bounds__(LB_THREADS) r128_kweight_kernel(R128Args a, const T *__restrict__ in, LbArgs lb) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    uint32_t *stage = reinterpret_cast<uint32_t *>(smem + lb_lds_bytes<8, 1>() / sizeof(double));
-    __shared__ int ticket_slot;
-    const int blk = lb_ticket(lb, &ticket_slot);
+__device__ __forceinline__ void r128_kweight_block(const R128Args &a, const T *__restrict__ in, const LbArgs &lb, int blk,
+                                                   int64_t g0, double *smem, uint32_t *stage) {
     const int t = threadIdx.x;
-    const int64_t g0 = (int64_t)blk * LB_THREADS, g = g0 + t;
+    const int64_t g = g0 + t;
     const bool valid = g < a.G;
     const int len = valid ? (int)min((int64_t)R128_TILE, a.N - g * R128_TILE) : 0;
     double zs[2 * CH][2];
@@ -135,21 +139,95 @@ __global__ void __launch_bounds__(LB_THREADS) r128_kweight_kernel(R128Args a, co
     a.part_hop[g] = h0;
 }
 
+template <int CH, typename T>
+__global__ void __launch_bounds__(LB_THREADS) r128_kweight_kernel(R128Args a, const T *__restrict__ in, LbArgs lb) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    uint32_t *stage = reinterpret_cast<uint32_t *>(smem + lb_lds_bytes<8, 1>() / sizeof(double));
+    __shared__ int ticket_slot;
+    const int blk = lb_ticket(lb, &ticket_slot);
+    r128_kweight_block<CH, T>(a, in, lb, blk, (int64_t)blk * LB_THREADS, smem, stage);
+}
+
+// Hop s of a line from its tile partials: lane k takes tiles g0 + k, g0 + k + 64, ..., then
+// a butterfly; the order is fixed by the line's geometry alone.
+__device__ __forceinline__ double r128_hop_sum(const double *part, const int64_t *part_hop, int64_t s, int rate, int lane) {
+    const int64_t g0 = r128_bound(s, rate) / R128_TILE, g1 = (r128_bound(s + 1, rate) - 1) / R128_TILE;
+    double acc = 0.0;
+    for (int64_t g = g0 + lane; g <= g1; g += 64) {  // (g1 < G: B[s + 1] <= N)
+        const int64_t ph = part_hop[g];
+        acc += ph == s ? part[2 * g] : (ph == s - 1 ? part[2 * g + 1] : 0.0);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
+    return acc;
+}
+
 // Tile partials to hop energies, e[s] for s < H (so frames at or after B[H] belong to no
-// hop): one wave per hop, lane k takes tiles g0 + k, g0 + k + 64, ..., then a butterfly;
-// the order is fixed by the geometry alone.
+// hop): one wave per hop.
 __global__ void __launch_bounds__(256) r128_reduce_kernel(R128Args a, double *e) {
     const int64_t s = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (s >= a.H) return;  // wave-uniform
-    const int64_t g0 = r128_bound(s, a.rate) / R128_TILE, g1 = (r128_bound(s + 1, a.rate) - 1) / R128_TILE;
-    double acc = 0.0;
-    for (int64_t g = g0 + lane; g <= g1; g += 64) {  // (g1 < G: B[s + 1] <= N)
-        const int64_t ph = a.part_hop[g];
-        acc += ph == s ? a.part[2 * g] : (ph == s - 1 ? a.part[2 * g + 1] : 0.0);
-    }
+    const double acc = r128_hop_sum(a.part, a.part_hop, s, a.rate, lane);
+    if (lane == 0) e[s] = acc;
+}
+
+// ---- the album pass: every track of an album in ONE launch of either kernel (album.hip).
+// The tracks stay where they are.  Track t owns ceil(G_t / LB_THREADS) consecutive
+// workgroups from wg0 and the partials of wg0 * LB_THREADS tiles on; its hops are
+// e[hop0 .. hop0 + H_t).  Inside its track a workgroup is r128_kweight_block as the
+// stand-alone launch runs it: the same tiles, staging and chain of predecessors back to
+// the block that resets, so a track's hop energies are those of r128_hops on it alone.
+struct R128Track {
+    const void *pcm;
+    int64_t N;     // frames
+    int64_t wg0;   // first workgroup
+    int64_t hop0;  // first hop
+};
+
+struct R128AlbumArgs {
+    const R128Track *tracks;  // [n]
+    const int *wg_track;      // [workgroups] the track a workgroup belongs to
+    int n, rate;
+    int64_t H;                // hops of the album
+    double sos[2][5];
+    double *part;             // [workgroups * LB_THREADS][2]
+    int64_t *part_hop;        // [workgroups * LB_THREADS]
+};
+
+template <int CH, typename T>
+__global__ void __launch_bounds__(LB_THREADS) r128_album_kweight_kernel(R128AlbumArgs al, LbArgs lb) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    uint32_t *stage = reinterpret_cast<uint32_t *>(smem + lb_lds_bytes<8, 1>() / sizeof(double));
+    __shared__ int ticket_slot;
+    const int blk = __builtin_amdgcn_readfirstlane(lb_ticket(lb, &ticket_slot));  // (uniform: the table reads are scalar)
+    const R128Track tr = al.tracks[al.wg_track[blk]];
+    R128Args a;
+    a.N = tr.N;
+    a.G = (tr.N + R128_TILE - 1) / R128_TILE;
+    a.H = 0;  // (the reduction's)
+    a.rate = al.rate;
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
+    for (int k = 0; k < 10; ++k) a.sos[k / 5][k % 5] = al.sos[k / 5][k % 5];
+    a.part = al.part + 2 * tr.wg0 * LB_THREADS;
+    a.part_hop = al.part_hop + tr.wg0 * LB_THREADS;
+    r128_kweight_block<CH, T>(a, static_cast<const T *>(tr.pcm), lb, blk, ((int64_t)blk - tr.wg0) * LB_THREADS, smem, stage);
+}
+
+// e[s] for s < H: a wave finds the track of its hop in the prefix hop0 (the last track that
+// starts at or before s: a track without hops is never found), then sums as r128_reduce_kernel.
+__global__ void __launch_bounds__(256) r128_album_reduce_kernel(R128AlbumArgs al, double *e) {
+    const int64_t s = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (s >= al.H) return;  // wave-uniform
+    int lo = 0, hi = al.n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (al.tracks[mid].hop0 <= s) lo = mid;
+        else hi = mid - 1;
+    }
+    const R128Track tr = al.tracks[lo];
+    const double acc = r128_hop_sum(al.part + 2 * tr.wg0 * LB_THREADS, al.part_hop + tr.wg0 * LB_THREADS, s - tr.hop0, al.rate, lane);
     if (lane == 0) e[s] = acc;
 }
 
@@ -204,6 +282,38 @@ double r128_gate(const std::vector<double> &z, const std::vector<double> &l, dou
     for (size_t j = 0; j < l.size(); ++j)
         if (l[j] > -70.0 && l[j] > gamma) keep.push_back((int64_t)j);
     return gamma;
+}
+
+// Steps 4-7 on the momentary (w = 4) and short-term (w = 30) windows of one programme, or on
+// an album's pools of them (album.hip): the one tail of every figure.  No window of a kind:
+// its figures stay NaN.
+void r128_figures(const std::vector<double> &z4, const std::vector<double> &l4, const std::vector<double> &z30,
+                  const std::vector<double> &l30, mm_r128 *out) {
+    std::vector<int64_t> keep;
+    if (!l4.empty()) {  // momentary windows: the maximum and the integrated loudness
+        out->momentary_blocks = (int64_t)l4.size();
+        out->momentary_max = *std::max_element(l4.begin(), l4.end());
+        out->relative_gate = r128_gate(z4, l4, 10.0, keep);
+        double sum = 0.0;
+        for (int64_t j : keep) sum += z4[(size_t)j];
+        out->integrated = keep.empty() ? -INFINITY : r128_level(sum / (double)keep.size());
+    }
+    if (!l30.empty()) {  // short-term windows: the maximum and the loudness range
+        out->short_term_blocks = (int64_t)l30.size();
+        out->short_term_max = *std::max_element(l30.begin(), l30.end());
+        r128_gate(z30, l30, 20.0, keep);
+        std::vector<double> k;
+        for (int64_t j : keep) k.push_back(l30[(size_t)j]);
+        std::sort(k.begin(), k.end());
+        const int64_t n = (int64_t)k.size();
+        out->lra_blocks = n;
+        out->lra = 0.0;
+        if (n > 0) {
+            out->lra_low = k[(size_t)(((n - 1) * 10 + 50) / 100)];
+            out->lra_high = k[(size_t)(((n - 1) * 95 + 50) / 100)];
+            out->lra = out->lra_high - out->lra_low;
+        }
+    }
 }
 
 // The transition tables of the pass for these sections (row-major 8 x 8; mono uses the
@@ -335,34 +445,10 @@ int mm_r128_from_hops(const double *e, int64_t hops, int32_t rate, mm_r128 *out)
     if (!out || hops < 0 || (hops > 0 && !e) || rate < R128_MIN_RATE) return MM_ERR_ARG;
     r128_clear(out, 0, 0, rate);
     out->hops = hops;
-    std::vector<double> z, l;
-    std::vector<int64_t> keep;
-    if (hops >= 4) {  // momentary windows: the maximum and the integrated loudness
-        r128_windows(e, hops, rate, 4, z, l);
-        out->momentary_blocks = (int64_t)l.size();
-        out->momentary_max = *std::max_element(l.begin(), l.end());
-        out->relative_gate = r128_gate(z, l, 10.0, keep);
-        double sum = 0.0;
-        for (int64_t j : keep) sum += z[(size_t)j];
-        out->integrated = keep.empty() ? -INFINITY : r128_level(sum / (double)keep.size());
-    }
-    if (hops >= 30) {  // short-term windows: the maximum and the loudness range
-        r128_windows(e, hops, rate, 30, z, l);
-        out->short_term_blocks = (int64_t)l.size();
-        out->short_term_max = *std::max_element(l.begin(), l.end());
-        r128_gate(z, l, 20.0, keep);
-        std::vector<double> k;
-        for (int64_t j : keep) k.push_back(l[(size_t)j]);
-        std::sort(k.begin(), k.end());
-        const int64_t n = (int64_t)k.size();
-        out->lra_blocks = n;
-        out->lra = 0.0;
-        if (n > 0) {
-            out->lra_low = k[(size_t)(((n - 1) * 10 + 50) / 100)];
-            out->lra_high = k[(size_t)(((n - 1) * 95 + 50) / 100)];
-            out->lra = out->lra_high - out->lra_low;
-        }
-    }
+    std::vector<double> z4, l4, z30, l30;
+    r128_windows(e, hops, rate, 4, z4, l4);
+    r128_windows(e, hops, rate, 30, z30, l30);
+    r128_figures(z4, l4, z30, l30, out);
     return MM_OK;
 }
 

@@ -30,12 +30,18 @@ Public surface (mirrors worker/audio_mastering_engine.py):
                                delivery to an R 128 loudness target under the true-peak ceiling
                                (no reference counterpart): the static gain that makes the
                                delivered file read the target, re-measured after every limiter pass
+  album_level_pcm(tracks, rate, lufs, ceiling_dbtp), album_r128_pcm(tracks, rate),
+  master_album(ctx, jobs, d_ins, d_outs, lufs, ceiling_dbtp), process_album(ins, outs, params)
+                               an album levelled as one programme (no reference counterpart):
+                               one static gain for all tracks to an R 128 album target, every
+                               track under the ceiling, the balance between the tracks kept
   legacy.master_pcm / legacy.process and main.py's helpers
                                the older monolithic engine (root main.py:46-192) as an
                                alternate DSP profile on the same HIP operators
 """
-from .engine import (EQ_PRESETS, Job, ceiling_pcm, ceilings, level_pcm, levels, master_batch, master_device,  # noqa: F401
-                     master_pcm, meter_pcm, meters, process, r128_pcm, r128s, resample_pcm)
+from .engine import (EQ_PRESETS, Job, album_level_pcm, album_r128_pcm, ceiling_pcm, ceilings, level_pcm, levels,  # noqa: F401
+                     master_album, master_batch, master_device, master_pcm, meter_pcm, meters, process, process_album,
+                     r128_pcm, r128s, resample_pcm)
 from . import legacy  # noqa: F401
 from .gui_compat import batch_process_audio, process_audio  # noqa: F401
 from .ops import (apply_eq_to_samples, apply_multiband_compressor, apply_peak_filter, apply_saturation,  # noqa: F401
@@ -46,4 +52,5 @@ __all__ = ["legacy", "EQ_PRESETS", "Job", "master_pcm", "master_device", "master
            "apply_saturation", "apply_eq_to_samples", "apply_shelf_filter", "apply_peak_filter", "apply_stereo_width",
            "apply_multiband_compressor", "normalize_to_lufs", "soft_limiter", "audio_segment_to_float_array",
            "float_array_to_audio_segment", "integrated_loudness", "true_peak", "meter_pcm", "meters", "ceiling_pcm",
-           "ceilings", "resample_pcm", "r128_pcm", "r128s", "level_pcm", "levels"]
+           "ceilings", "resample_pcm", "r128_pcm", "r128s", "level_pcm", "levels", "album_level_pcm", "album_r128_pcm",
+           "master_album", "process_album"]

@@ -430,6 +430,79 @@ def level_pcm(pcm: np.ndarray, rate: int, target_lufs: float, ceiling_dbtp: floa
     return x, level_dict(m)
 
 
+def _album_tracks(tracks):
+    """The tracks of an album as the album entries take them: (arrays, kind, channels, the
+    pointer array's element addresses, frames as a c_int64 array).  ValueError for what is
+    not an album: no track or more than native.ALBUM_TRACKS, or tracks that differ in
+    channel count or sample type."""
+    tracks = list(tracks)
+    if not 1 <= len(tracks) <= native.ALBUM_TRACKS:
+        raise ValueError(f"an album has 1 to {native.ALBUM_TRACKS} tracks, not {len(tracks)}")
+    xs, kinds, chs = [], set(), set()
+    for t in tracks:
+        x, kind = _out_kind(np.asarray(t))
+        xs.append(x)
+        kinds.add(kind)
+        chs.add(1 if x.ndim == 1 else x.shape[1])
+    if len(chs) != 1:
+        raise ValueError("the tracks of an album must have one channel count")
+    if len(kinds) != 1:
+        raise ValueError("the tracks of an album must have one sample type (all int16 or all float32)")
+    frames = (ctypes.c_int64 * len(xs))(*[x.shape[0] for x in xs])
+    return xs, kinds.pop(), chs.pop(), frames
+
+
+def _pointers(addresses):
+    return (ctypes.c_void_p * len(addresses))(*[ctypes.c_void_p(int(a)) for a in addresses])
+
+
+def _album_dict(ctx: native.Context, n: int, ceiling: bool) -> dict:
+    """The result of the context's last album level (mm_last_album): level_dict's fields, the
+    album's r128_dict under "r128" and, under "tracks", one dict a track with its own "r128"
+    and, when a ceiling was set, "ceiling"."""
+    lv, alb = native.MMLevel(), native.MMR128()
+    ctx.check(ctx.lib.mm_last_album(ctx.ptr, ctypes.byref(lv), ctypes.byref(alb)), "mm_last_album")
+    d = level_dict(lv)
+    d["r128"] = r128_dict(alb)
+    d["tracks"] = [{"r128": r128_dict(r)} for r in r128s(ctx, n)]
+    if ceiling:
+        for t, ce in zip(d["tracks"], ceilings(ctx, n)):
+            t["ceiling"] = ceiling_dict(ce)
+    return d
+
+
+def album_r128_pcm(tracks, rate: int, device: int = 0) -> dict:
+    """The album EBU R 128 report (r128_dict) of int16 (or float32 = int16 / 32768) arrays [N]
+    or [N, ch], measured as one programme whose gating blocks never span two tracks
+    (mm_album_r128_pcm: one K-weighting launch for all tracks).  `r128s(ctx)` then holds the
+    per-track reports."""
+    xs, kind, ch, frames = _album_tracks(tracks)
+    ctx = native.context(device)
+    m = native.MMR128()
+    ctx.check(ctx.lib.mm_album_r128_pcm(ctx.ptr, _pointers([x.ctypes.data for x in xs]), kind, frames, len(xs), ch,
+                                        int(rate), kweight_sos(rate), ctypes.byref(m)), "mm_album_r128_pcm")
+    return r128_dict(m)
+
+
+def album_level_pcm(tracks, rate: int, target_lufs: float, ceiling_dbtp: float | None = None,
+                    window: int | None = None, device: int = 0):
+    """Level the tracks of an album (int16 or float32 = int16 / 32768 arrays [N] or [N, ch], one
+    rate, channel count and sample type) by ONE static gain, so that the album measured as one
+    programme reads `target_lufs` with every track under `ceiling_dbtp` (None: no ceiling, the
+    gain is capped where a sample of any track would clip): mm_album_level_pcm.  Returns (new
+    arrays, album dict): level_dict's fields plus "r128" (the album's r128_dict) and "tracks"
+    (per track "r128" and, with a ceiling, "ceiling")."""
+    xs, kind, ch, frames = _album_tracks(tracks)
+    xs = [x.copy() for x in xs]
+    C = 0 if ceiling_dbtp is None else design.ceiling_q28(ceiling_dbtp)
+    w = design.ceiling_window(rate) if window is None else int(window)
+    clu = design.level_clu(target_lufs)
+    ctx = native.context(device)
+    ctx.check(ctx.lib.mm_album_level_pcm(ctx.ptr, _pointers([x.ctypes.data for x in xs]), kind, frames, len(xs), ch,
+                                         int(rate), kweight_sos(rate), clu, C, w), "mm_album_level_pcm")
+    return xs, _album_dict(ctx, len(xs), bool(C))
+
+
 def resample_dict(m: native.MMResample) -> dict:
     """An mm_resample as `info["resample"]`: the struct's integers (clipped and peak as
     per-channel lists) and the largest delivered sample in dBFS.  No reference counterpart."""
@@ -603,6 +676,94 @@ def master_batch(ctx: native.Context, jobs, d_ins, d_outs, with_results: bool = 
     res = (native.MMResult * n)() if with_results else None
     ctx.check(ctx.lib.mm_master_batch(ctx.ptr, n, arr, ins, outs, res), "mm_master_batch")
     return list(res) if with_results else None
+
+
+def master_album(ctx: native.Context, jobs, d_ins, d_outs, deliver_lufs: float, ceiling_dbtp: float | None = None):
+    """Master the tracks of an album as a batch (master_batch) and level the album in place on
+    `d_outs` (mm_album_level_device): one static gain for all tracks to `deliver_lufs` (the
+    album's EBU R 128 integrated loudness), every track under `ceiling_dbtp`.  The jobs are
+    planned without ceiling, delivery, level, report or r128 (the album call resets the
+    context's per-call results, so a batch's meters would be lost without a word) and share
+    one rate, channel count and output kind: anything else is a ValueError before anything runs.  Returns (the batch's results,
+    album dict as album_level_pcm's); `r128s(ctx)` / `ceilings(ctx)` then hold the per-track
+    reports of the levelled tracks, as after a batch."""
+    jobs = list(jobs)
+    if not 1 <= len(jobs) <= native.ALBUM_TRACKS:
+        raise ValueError(f"an album has 1 to {native.ALBUM_TRACKS} tracks, not {len(jobs)}")
+    if any(j.delivery is not None for j in jobs):
+        raise ValueError("the jobs of an album are planned without a delivery (output_rate, deliver_lufs): "
+                         "the album call levels them")
+    if any(j.job.ceiling_q28 for j in jobs):
+        raise ValueError("the jobs of an album are planned without ceiling_dbtp: the album call holds the ceiling")
+    if any(j.job.meter_on for j in jobs):
+        raise ValueError("the jobs of an album are planned without report or r128: they would describe the tracks "
+                         "before the level, and the album call's own per-track reports replace them")
+    if len({j.rate for j in jobs}) != 1:
+        raise ValueError("the tracks of an album must have one sample rate")
+    if len({j.channels for j in jobs}) != 1:
+        raise ValueError("the tracks of an album must have one channel count")
+    if len({int(j.job.out_kind) for j in jobs}) != 1:
+        raise ValueError("the tracks of an album must have one output kind")
+    rate, ch, kind = jobs[0].rate, jobs[0].channels, int(jobs[0].job.out_kind)
+    clu = design.level_clu(deliver_lufs)
+    C = 0 if ceiling_dbtp is None else design.ceiling_q28(ceiling_dbtp)
+    res = master_batch(ctx, jobs, d_ins, d_outs)
+    frames = (ctypes.c_int64 * len(jobs))(*[j.frames_proc for j in jobs])
+    ctx.check(ctx.lib.mm_album_level_device(ctx.ptr, _pointers(d_outs), kind, frames, len(jobs), ch, rate,
+                                            kweight_sos(rate), clu, C, design.ceiling_window(rate)),
+              "mm_album_level_device")
+    return res, _album_dict(ctx, len(jobs), bool(C))
+
+
+def process_album(input_paths, output_paths, params: dict, device: int = 0):
+    """Master the WAV files of an album with the same `params` and level them as one album
+    (master_album): params['deliver_lufs'] (required) is the album's target, params['ceiling_dbtp']
+    (optional) the true-peak ceiling of every track; params['output_format']='f32' writes
+    float.  The files share one rate and channel count.  Returns (one info dict a file, album
+    dict).  params['output_rate'] is refused: delivery at another rate is not available for a
+    batch; params['report'] and params['r128'] are refused too: the album dict carries every
+    levelled file's R 128 report and ceiling."""
+    from . import wavio
+    params = dict(params or {})
+    if params.get("deliver_lufs") is None:
+        raise ValueError("process_album needs params['deliver_lufs']: the album's loudness target")
+    deliver_lufs = params.pop("deliver_lufs")
+    ceiling = params.pop("ceiling_dbtp", None)
+    if params.pop("output_rate", None) is not None:
+        raise ValueError("delivery at another rate (output_rate) is not available for a batch")
+    fmt = params.pop("output_format", "pcm16")
+    for key in ("report", "r128"):
+        if params.get(key):
+            raise ValueError(f"process_album takes no params['{key}']: the album dict carries the R 128 report and "
+                             "the ceiling of every levelled file (meter one with meter_pcm)")
+        params.pop(key, None)
+    input_paths, output_paths = list(input_paths), list(output_paths)
+    if len(input_paths) != len(output_paths):
+        raise ValueError("process_album needs one output path for every input path")
+    kind = native.MM_OUT_F32 if fmt == "f32" else native.MM_OUT_I16
+    pcms, rates = zip(*[wavio.read_wav(p) for p in input_paths]) if input_paths else ((), ())
+    if len(set(rates)) > 1:
+        raise ValueError("the tracks of an album must have one sample rate")
+    jobs, xs = [], []
+    for pcm in pcms:
+        job = Job(pcm.shape[0], rates[0], 1 if pcm.ndim == 1 else pcm.shape[1], params, kind)
+        x, job.job.in_kind = _device_input(pcm, wide=True)
+        jobs.append(job)
+        xs.append(x)
+    import torch  # (plumbing only: the device buffers of the batch)
+    ctx = native.context(device)
+    dev = torch.device("cuda", device)
+    d_ins = [torch.from_numpy(x).to(dev) for x in xs]
+    d_outs = [torch.empty((j.frames_proc, j.channels), dtype=torch.int16 if kind == native.MM_OUT_I16 else torch.float32,
+                          device=dev) for j in jobs]
+    torch.cuda.synchronize(dev)
+    res, album = master_album(ctx, jobs, [t.data_ptr() for t in d_ins], [t.data_ptr() for t in d_outs], deliver_lufs, ceiling)
+    infos = []
+    for job, r, out, path in zip(jobs, res, d_outs, output_paths):
+        y = out.cpu().numpy()
+        wavio.write_wav(path, y[:, 0] if job.channels == 1 else y, job.rate)
+        infos.append(dict(_info(job, r), output_path=os.path.abspath(path)))
+    return infos, album
 
 
 def process(input_path: str, output_path: str, params: dict, device: int = 0, verbose: bool = False) -> dict:

@@ -129,6 +129,7 @@ class MMLevel(ctypes.Structure):
 
 
 ABI_VERSION = 5  # MM_ABI_VERSION of include/mastering.h
+ALBUM_TRACKS = 256  # MM_ALBUM_TRACKS
 
 
 class MMWavInfo(ctypes.Structure):
@@ -158,7 +159,9 @@ EXPORTS = ("mm_create", "mm_destroy", "mm_last_error", "mm_sync", "mm_version", 
            "mm_pcm_decode_device", "mm_op_pcm_decode", "mm_pcm_decode_host", "mm_pcm_decode_span",
            "mm_resample_device", "mm_resample_pcm", "mm_resample_host", "mm_resample_frames", "mm_resample_span",
            "mm_last_resample", "mm_deliver_device", "mm_deliver", "mm_deliver_wav",
-           "mm_level_device", "mm_level_pcm", "mm_level_host", "mm_op_level_gain", "mm_last_levels", "mm_level_span")
+           "mm_level_device", "mm_level_pcm", "mm_level_host", "mm_op_level_gain", "mm_last_levels", "mm_level_span",
+           "mm_r128_album_from_hops", "mm_album_level_host", "mm_album_r128_device", "mm_album_r128_pcm",
+           "mm_op_r128_album_hops", "mm_album_level_device", "mm_album_level_pcm", "mm_last_album")
 
 _lib = None
 _lock = threading.Lock()
@@ -293,6 +296,21 @@ def load():
                                   c_int64_p, P(ctypes.c_int32)], ctypes.c_int),
             "mm_last_levels": ([vp, ctypes.c_int, P(MMLevel)], ctypes.c_int),
             "mm_level_span": ([], ctypes.c_int),
+            "mm_r128_album_from_hops": ([c_double_p, c_int64_p, ctypes.c_int, ctypes.c_int32, P(MMR128)], ctypes.c_int),
+            "mm_album_level_host": ([P(P(ctypes.c_int16)), c_int64_p, ctypes.c_int, ctypes.c_int, ctypes.c_int32, c_sos_p,
+                                     ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, P(MMLevel), P(MMR128), P(MMR128),
+                                     P(MMCeiling)], ctypes.c_int),
+            "mm_album_r128_device": ([vp, P(vp), ctypes.c_int, c_int64_p, ctypes.c_int, ctypes.c_int, ctypes.c_int32,
+                                      c_sos_p, P(MMR128)], ctypes.c_int),
+            "mm_album_r128_pcm": ([vp, P(vp), ctypes.c_int, c_int64_p, ctypes.c_int, ctypes.c_int, ctypes.c_int32,
+                                   c_sos_p, P(MMR128)], ctypes.c_int),
+            "mm_op_r128_album_hops": ([vp, P(vp), ctypes.c_int, c_int64_p, ctypes.c_int, ctypes.c_int, ctypes.c_int32,
+                                       c_sos_p, c_double_p, ctypes.c_int64], ctypes.c_int),
+            "mm_album_level_device": ([vp, P(vp), ctypes.c_int, c_int64_p, ctypes.c_int, ctypes.c_int, ctypes.c_int32,
+                                       c_sos_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32], ctypes.c_int),
+            "mm_album_level_pcm": ([vp, P(vp), ctypes.c_int, c_int64_p, ctypes.c_int, ctypes.c_int, ctypes.c_int32,
+                                    c_sos_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32], ctypes.c_int),
+            "mm_last_album": ([vp, P(MMLevel), P(MMR128)], ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             fn = getattr(lib, name)
