@@ -422,7 +422,9 @@ int mm_sync(mm_ctx *ctx);
    (mm_level_device, mm_level_pcm, mm_level_host, mm_op_level_gain, mm_last_levels,
    mm_level_span); and, as entry points only (no struct added or changed), the album
    (mm_r128_album_from_hops, mm_album_level_host, mm_album_r128_device, mm_album_r128_pcm,
-   mm_op_r128_album_hops, mm_album_level_device, mm_album_level_pcm, mm_last_album).  A caller
+   mm_op_r128_album_hops, mm_album_level_device, mm_album_level_pcm, mm_last_album); and, again
+   as entry points only, the batch (mm_batch_ceiling_device, mm_batch_ceiling_pcm,
+   mm_batch_level_device, mm_batch_level_pcm).  A caller
    built against an older header must
    refuse a library whose version differs from its own MM_ABI_VERSION. */
 #define MM_ABI_VERSION 5
@@ -655,6 +657,46 @@ int mm_album_level_pcm(mm_ctx *ctx, void *const *pcm, int kind, const int64_t *f
 /* The result of the last mm_album_level_* call on this context.  MM_ERR_STATE if the last
  * call levelled no album. */
 int mm_last_album(mm_ctx *ctx, mm_level *level, mm_r128 *album);
+
+/* ---- a batch levelled track by track ----------------------------------------- */
+/* The tracks of a batch are independent deliveries: every track t gets its OWN ceiling
+ * ceiling_q28[t] and its OWN target level_clu[t], and what it receives is what the single-track
+ * entry gives on that track alone, bit for bit, samples and statistics:
+ *
+ *   batch ceiling:  out[t] and track t as mm_ceiling_device(track t, ceiling_q28[t], window)
+ *   batch level:    mm_level, mm_ceiling and track t as mm_level_device(track t, level_clu[t],
+ *                   ceiling_q28[t], window); ceiling_q28[t] == 0: no ceiling for that track
+ *                   (its gain is capped at its own sample peak); the R 128 report of track t
+ *                   is mm_r128_device's of its delivered samples
+ *
+ * The tracks share one kind, channel count, rate and window.  Only the launch structure
+ * differs from n calls: the need, apply, peak, trim, gain and K-weighting launches each cover
+ * all tracks (csrc/tracks.hip), the tracks of a level advance one pass at a time, and the
+ * launches and synchronisations of a pass do not depend on n. */
+
+/* Hold n device-resident tracks, interleaved [frames[t]][channels] of `kind`, under their
+ * ceilings in place; out[n] receives every track's mm_ceiling.  At most two synchronisations
+ * (one when no track is trimmed).  MM_ERR_ARG, with words in mm_last_error that name the
+ * track, before anything is queued and with the context still usable, for n outside
+ * [1, MM_ALBUM_TRACKS], a track mm_ceiling_device refuses or a total of 2^31 frames or more.
+ * Synchronous on return. */
+int mm_batch_ceiling_device(mm_ctx *ctx, void *const *d_pcm, int kind, const int64_t *frames, int n, int channels,
+                            const int32_t *ceiling_q28, int32_t window, mm_ceiling *out);
+/* The same on host buffers, in place (an untouched track is not copied back). */
+int mm_batch_ceiling_pcm(mm_ctx *ctx, void *const *pcm, int kind, const int64_t *frames, int n, int channels,
+                         const int32_t *ceiling_q28, int32_t window, mm_ceiling *out);
+/* Level n device-resident tracks in place, track t to level_clu[t] under ceiling_q28[t] (0:
+ * none).  The results are left behind mm_last_levels, mm_last_r128 (the delivered tracks') and,
+ * when a track has a ceiling, mm_last_ceilings (n each, in track order; a track without a
+ * ceiling leaves a cleared mm_ceiling with its channels).  MM_ERR_ARG as above, for n outside
+ * [1, MM_ALBUM_TRACKS], a track mm_level_device refuses or a total of 2^31 frames or more.
+ * Synchronous on return. */
+int mm_batch_level_device(mm_ctx *ctx, void *const *d_pcm, int kind, const int64_t *frames, int n, int channels,
+                          int32_t rate, const double sos[2][5], const int32_t *level_clu, const int32_t *ceiling_q28,
+                          int32_t window);
+/* The same on host buffers, in place. */
+int mm_batch_level_pcm(mm_ctx *ctx, void *const *pcm, int kind, const int64_t *frames, int n, int channels, int32_t rate,
+                       const double sos[2][5], const int32_t *level_clu, const int32_t *ceiling_q28, int32_t window);
 
 /* ---- delivery at another sample rate ----------------------------------------- */
 /* Convert a device-resident signal, interleaved [frames][channels] of `kind` (MM_OUT_I16,

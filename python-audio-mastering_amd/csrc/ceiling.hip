@@ -51,17 +51,18 @@ __device__ __forceinline__ int ceil_ratio(int Ct, int P) {
     return q;
 }
 
-// One workgroup per span of METER_SPAN frames m; a thread owns METER_FPT consecutive m
-// (the meter's window layout).  It writes r[m] - 1 for all its m as one 16-byte store:
-// the plane holds whole spans, so every entry up to the plane's end is written (2^16 - 1
-// beyond N + 11, where P = 0).  TP0 is folded into st->tp0 with one atomic per workgroup.
-template <int CH, typename T>
-__global__ void __launch_bounds__(METER_THREADS) ceil_need_kernel(const T *__restrict__ in, int64_t N, int Ct,
-                                                                  uint16_t *__restrict__ plane, CeilDev *st) {
+// One workgroup on the span of METER_SPAN frames m at `base`; a thread owns METER_FPT
+// consecutive m (the meter's window layout).  With STORE it writes r[m] - 1 for all its m as
+// one 16-byte store at span[thread * METER_FPT] (`span`: the plane at `base`, a 16-byte
+// boundary): the plane holds whole spans, so every entry up to the plane's end is written
+// (2^16 - 1 beyond N + 11, where P = 0).  The span's max P is folded into *tp with one atomic
+// per workgroup.  Without STORE it is the linked true peak alone (tracks.hip: ceil_tracks_peak).
+template <int CH, typename T, bool STORE>
+__device__ __forceinline__ void ceil_need_span(const T *__restrict__ in, int64_t N, int64_t base, int Ct,
+                                               uint16_t *__restrict__ span, unsigned *tp) {
     __shared__ __attribute__((aligned(16))) int16_t line[CH][METER_LINE];
     __shared__ int red[METER_THREADS / 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t base = (int64_t)blockIdx.x * METER_SPAN;
     tp_stage<CH, T>(line, in, N, base);
     int pm[METER_FPT];
 #pragma unroll
@@ -81,22 +82,32 @@ __global__ void __launch_bounds__(METER_THREADS) ceil_need_kernel(const T *__res
 #pragma unroll
     for (int j = 0; j < METER_FPT; ++j) {
         best = max(best, pm[j]);
-        r1[j] = pm[j] > Ct ? (uint32_t)(ceil_ratio(Ct, pm[j]) - 1) : (uint32_t)(CEIL_ONE - 1);
+        if (STORE) r1[j] = pm[j] > Ct ? (uint32_t)(ceil_ratio(Ct, pm[j]) - 1) : (uint32_t)(CEIL_ONE - 1);
     }
-    uint4 o;
-    o.x = r1[0] | (r1[1] << 16);
-    o.y = r1[2] | (r1[3] << 16);
-    o.z = r1[4] | (r1[5] << 16);
-    o.w = r1[6] | (r1[7] << 16);
-    static_assert(METER_FPT == 8, "one 16-byte store of eight uint16 per thread");
-    *reinterpret_cast<uint4 *>(plane + base + (int64_t)threadIdx.x * METER_FPT) = o;
+    if (STORE) {
+        uint4 o;
+        o.x = r1[0] | (r1[1] << 16);
+        o.y = r1[2] | (r1[3] << 16);
+        o.z = r1[4] | (r1[5] << 16);
+        o.w = r1[6] | (r1[7] << 16);
+        static_assert(METER_FPT == 8, "one 16-byte store of eight uint16 per thread");
+        *reinterpret_cast<uint4 *>(span + (int64_t)threadIdx.x * METER_FPT) = o;
+    }
     best = wave_max_i32(best);
     if (lane == 0) red[wave] = best;
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int w = 1; w < METER_THREADS / 64; ++w) best = max(best, red[w]);
-        if (best) atomicMax(&st->tp0, (unsigned)best);
+        if (best) atomicMax(tp, (unsigned)best);
     }
+}
+
+// One workgroup per span: TP0 is folded into st->tp0.
+template <int CH, typename T>
+__global__ void __launch_bounds__(METER_THREADS) ceil_need_kernel(const T *__restrict__ in, int64_t N, int Ct,
+                                                                  uint16_t *__restrict__ plane, CeilDev *st) {
+    const int64_t base = (int64_t)blockIdx.x * METER_SPAN;
+    ceil_need_span<CH, T, true>(in, N, base, Ct, plane + base, &st->tp0);
 }
 
 typedef unsigned short ceil_u16x2 __attribute__((ext_vector_type(2)));
@@ -150,23 +161,22 @@ __device__ __forceinline__ void ceil_scale(T *pcm, int64_t n, int g) {
     store_frame<CH, T>(pcm, n, s);
 }
 
-// One workgroup per CEIL_SPAN frames n in [base, base + CEIL_SPAN).  It needs h on
+// One workgroup on the CEIL_SPAN frames n in [base, base + CEIL_SPAN) of one signal.  It needs h on
 // [base - W, base + span + W), so R on [base - 2W, base + span + 2W) and r on 11 more:
-// those r - 1 are staged in LDS as uint16 (2^16 - 1 outside the plane).  The whole grid
-// exits at once when TP0 <= C, and a workgroup whose staged r are all 2^16 writes
+// those r - 1 are staged in LDS as uint16 (2^16 - 1 outside the plane).  The signal's
+// workgroups exit at once when TP0 <= C, and a workgroup whose staged r are all 2^16 writes
 // nothing.  The box sums come from one exclusive scan of h in uint32
 // ((span + 2W) * 2^16 < 2^32), divided by 2W + 1 with a multiply-high reciprocal
 // rcp = floor(2^32 / (2W + 1)) and one correction.
 template <int CH, typename T>
-__global__ void __launch_bounds__(CEIL_THREADS) ceil_apply_kernel(T *__restrict__ pcm, int64_t N, int64_t plane_len,
-                                                                  const uint16_t *__restrict__ plane, int C, int W,
-                                                                  unsigned rcp, CeilDev *st) {
+__device__ __forceinline__ void ceil_apply_span(T *__restrict__ pcm, int64_t N, int64_t plane_len,
+                                                const uint16_t *__restrict__ plane, int C, int W, unsigned rcp, CeilDev *st,
+                                                int64_t base) {
     __shared__ __attribute__((aligned(16))) uint16_t buf_a[CEIL_BUF], buf_b[CEIL_BUF];
     __shared__ uint32_t ps[CEIL_HLEN + 1];
     __shared__ uint32_t wsum[CEIL_THREADS / 64], wred[CEIL_THREADS / 64];
     if (st->tp0 <= (unsigned)C) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t base = (int64_t)blockIdx.x * CEIL_SPAN;
     const int D = 2 * W + 1;
     const int n_r = CEIL_SPAN + 4 * W + 11, n_R = CEIL_SPAN + 4 * W, n_h = CEIL_SPAN + 2 * W;
     const int64_t m_first = base - 2 * W;  // m (and j) of LDS index 0
@@ -235,6 +245,13 @@ __global__ void __launch_bounds__(CEIL_THREADS) ceil_apply_kernel(T *__restrict_
         if (count) atomicAdd(&st->limited, (unsigned long long)count);
         if (red) atomicMax(&st->max_red, (unsigned)red);
     }
+}
+
+template <int CH, typename T>
+__global__ void __launch_bounds__(CEIL_THREADS) ceil_apply_kernel(T *__restrict__ pcm, int64_t N, int64_t plane_len,
+                                                                  const uint16_t *__restrict__ plane, int C, int W,
+                                                                  unsigned rcp, CeilDev *st) {
+    ceil_apply_span<CH, T>(pcm, N, plane_len, plane, C, W, rcp, st, (int64_t)blockIdx.x * CEIL_SPAN);
 }
 
 // The static trim: every sample by g (pointwise, in place).

@@ -67,17 +67,17 @@ struct LevelVec<float> {
 
 // Workgroup b takes the whole vectors [b * VPB, (b + 1) * VPB) of dst + head; workgroup 0
 // also the `head` samples before them (lanes 0 ..) and the tail after the last (lanes 64 ..).
+// (`blk`: the workgroup's index within the signal; tracks.hip runs the same body over n signals.)
 template <typename T>
-__global__ void __launch_bounds__(LEVEL_THREADS) level_gain_kernel(const T *__restrict__ src, T *__restrict__ dst,
-                                                                    int64_t n, int head, int src_vec, int g,
-                                                                    LevelDev *st) {
+__device__ __forceinline__ void level_gain_span(const T *__restrict__ src, T *__restrict__ dst, int64_t n, int head,
+                                                int src_vec, int g, LevelDev *st, unsigned blk) {
     constexpr int VEC = 16 / (int)sizeof(T);                   // samples per 16-byte vector
     constexpr int VPL = LEVEL_SPAN / (LEVEL_THREADS * VEC);    // vectors per lane
     typedef typename LevelVec<T>::type V;
     static_assert(sizeof(V) == 16 && VPL * LEVEL_THREADS * VEC == LEVEL_SPAN, "a workgroup covers LEVEL_SPAN samples");
     const int tid = threadIdx.x, gh = g >> 16, gl = g & 0xFFFF;
     const int64_t nvec = (n - head) / VEC;
-    const int64_t v0 = (int64_t)blockIdx.x * (LEVEL_THREADS * VPL) + tid;
+    const int64_t v0 = (int64_t)blk * (LEVEL_THREADS * VPL) + tid;
     unsigned clipped = 0;
     int peak = 0;
     V v[VPL];
@@ -104,7 +104,7 @@ __global__ void __launch_bounds__(LEVEL_THREADS) level_gain_kernel(const T *__re
             __builtin_nontemporal_store(o, reinterpret_cast<V *>(dst + head + vi * VEC));
         }
     }
-    if (blockIdx.x == 0) {  // the single samples: fewer than VEC at either end
+    if (blk == 0) {  // the single samples: fewer than VEC at either end
         const int64_t tail0 = head + nvec * VEC;
         int64_t i = -1;
         if (tid < head) i = tid;
@@ -120,6 +120,13 @@ __global__ void __launch_bounds__(LEVEL_THREADS) level_gain_kernel(const T *__re
         if (clipped) atomicAdd(&st->clipped, (unsigned long long)clipped);
         if ((unsigned)peak > __atomic_load_n(&st->peak, __ATOMIC_RELAXED)) atomicMax(&st->peak, (unsigned)peak);
     }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(LEVEL_THREADS) level_gain_kernel(const T *__restrict__ src, T *__restrict__ dst,
+                                                                    int64_t n, int head, int src_vec, int g,
+                                                                    LevelDev *st) {
+    level_gain_span<T>(src, dst, n, head, src_vec, g, st, blockIdx.x);
 }
 
 }  // namespace mm

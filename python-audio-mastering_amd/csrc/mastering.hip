@@ -1291,3 +1291,4 @@ int mm_kernel_stats(mm_ctx *c, char *names, int names_cap, double *total_ms, int
 #include "level.hip"
 #include "resample.hip"
 #include "album.hip"
+#include "tracks.hip"

@@ -1,0 +1,539 @@
+// tracks.hip — the ceiling and the level's gain over n tracks at once, each track with its
+// own parameters, and on them the level of a batch: every track to its OWN R 128 target under
+// its own true-peak ceiling (the batch entries in include/mastering.h).  No reference
+// counterpart.
+//
+// No numerics are defined here.  Per track the ceiling is mm_ceiling and the level mm_level,
+// bit for bit: the kernels run the single-track bodies (ceiling.hip: ceil_need_span,
+// ceil_apply_span, ceil_scale; level.hip: level_gain_span) and the decisions are level.hip's
+// level_first / level_next / level_boost_cap / level_inner_ceiling / level_peak_cap.  What is
+// new is the launch structure: one launch covers the spans of all tracks (tracks.h: a track
+// owns a run of workgroups, a workgroup finds its track by a search over at most 257 prefix
+// sums, which are uniform reads), so a pass of the batch costs the same launches and
+// synchronisations for 2 tracks as for 256, where a call a track pays both n times.
+//   ceil_tracks_need   ceil_need over all METER_SPAN spans; track t's r - 1 plane at a
+//                      multiple of METER_SPAN of one plane buffer, TP0 into its CeilDev
+//   ceil_tracks_apply  ceil_apply over all CEIL_SPAN spans; the early exit, the plane mask and
+//                      the R mask are the track's own
+//   ceil_tracks_peak   the linked true peak of every track: the need body with the plane
+//                      store switched off (a track whose TP0 <= C was not touched: skipped)
+//   ceil_tracks_trim   pointwise, the tracks with a residue only, each by its own g_t
+//   level_tracks_gain  level_gain; head and tail single samples by a track's first workgroup
+// The per-track parameters of a launch are one small array uploaded per pass; a workgroup of
+// a track that takes no part exits on one uniform read of it.
+//
+// Included at the end of mastering.hip after album.hip (album_pass_prepare, album_pass_hops,
+// album_reports measure the tracks of a pass; album_upload packs host tracks).
+
+#include "tracks.h"
+
+namespace mm {
+
+static_assert(TRACKS_METER_SPAN == METER_SPAN && TRACKS_CEIL_SPAN == CEIL_SPAN && TRACKS_MAX == MM_ALBUM_TRACKS,
+              "tracks.h restates the spans");
+
+struct TrackDev {  // one a track, uploaded once a call
+    void *pcm;
+    int64_t frames;
+};
+
+struct TrackPar {  // one a track, uploaded once a launch sequence
+    int C, Ct;     // the ceiling and C - CEIL_GUARD
+    int g;         // the trim
+    int active;    // 0: the track's workgroups exit at once
+};
+
+struct TracksArgs {
+    const TrackDev *tr;
+    const uint32_t *first_need, *first_apply;  // [n + 1] prefix sums of the two grids
+    const TrackPar *par;
+    uint16_t *plane;
+    CeilDev *st;     // [n]
+    unsigned *peak;  // [n] the linked true peak after the limiter / the trim
+    int n, W;
+    unsigned rcp;
+};
+
+template <int CH, typename T>
+__global__ void __launch_bounds__(METER_THREADS) ceil_tracks_need_kernel(TracksArgs a) {
+    const int t = tracks_find(a.first_need, a.n, blockIdx.x);
+    const TrackPar p = a.par[t];
+    if (!p.active) return;
+    const TrackDev tr = a.tr[t];
+    const int64_t base = (int64_t)(blockIdx.x - a.first_need[t]) * METER_SPAN;
+    ceil_need_span<CH, T, true>(static_cast<const T *>(tr.pcm), tr.frames, base, p.Ct,
+                                a.plane + tracks_plane_off(a.first_need, t) + base, &a.st[t].tp0);
+}
+
+template <int CH, typename T>
+__global__ void __launch_bounds__(METER_THREADS) ceil_tracks_peak_kernel(TracksArgs a) {
+    const int t = tracks_find(a.first_need, a.n, blockIdx.x);
+    const TrackPar p = a.par[t];
+    if (!p.active || a.st[t].tp0 <= (unsigned)p.C) return;
+    const TrackDev tr = a.tr[t];
+    const int64_t base = (int64_t)(blockIdx.x - a.first_need[t]) * METER_SPAN;
+    ceil_need_span<CH, T, false>(static_cast<const T *>(tr.pcm), tr.frames, base, 0, nullptr, &a.peak[t]);
+}
+
+template <int CH, typename T>
+__global__ void __launch_bounds__(CEIL_THREADS) ceil_tracks_apply_kernel(TracksArgs a) {
+    const int t = tracks_find(a.first_apply, a.n, blockIdx.x);
+    const TrackPar p = a.par[t];
+    if (!p.active) return;
+    const TrackDev tr = a.tr[t];
+    const int64_t base = (int64_t)(blockIdx.x - a.first_apply[t]) * CEIL_SPAN;
+    ceil_apply_span<CH, T>(static_cast<T *>(tr.pcm), tr.frames, tracks_plane_len(tr.frames),
+                           a.plane + tracks_plane_off(a.first_need, t), p.C, a.W, a.rcp, &a.st[t], base);
+}
+
+// the samples of the span's frames as one mono line
+template <typename T>
+__global__ void __launch_bounds__(CEIL_THREADS) ceil_tracks_trim_kernel(TracksArgs a, int channels) {
+    const int t = tracks_find(a.first_apply, a.n, blockIdx.x);
+    const TrackPar p = a.par[t];
+    if (!p.active) return;
+    const TrackDev tr = a.tr[t];
+    const int64_t base = (int64_t)(blockIdx.x - a.first_apply[t]) * CEIL_SPAN;
+    const int64_t s1 = (tr.frames < base + CEIL_SPAN ? tr.frames : base + CEIL_SPAN) * channels;
+    for (int64_t i = base * channels + threadIdx.x; i < s1; i += CEIL_THREADS) ceil_scale<1, T>(static_cast<T *>(tr.pcm), i, p.g);
+}
+
+struct GainTrack {  // one a track, uploaded once a launch
+    const void *src;
+    void *dst;
+    int64_t n;  // samples
+    int head, src_vec, g, active;
+};
+
+template <typename T>
+__global__ void __launch_bounds__(LEVEL_THREADS) level_tracks_gain_kernel(const GainTrack *tr, const uint32_t *first, int n,
+                                                                           LevelDev *st) {
+    const int t = tracks_find(first, n, blockIdx.x);
+    const GainTrack k = tr[t];
+    if (!k.active) return;
+    level_gain_span<T>(static_cast<const T *>(k.src), static_cast<T *>(k.dst), k.n, k.head, k.src_vec, k.g, st + t,
+                       blockIdx.x - first[t]);
+}
+
+}  // namespace mm
+
+// ======================================================= host
+namespace {
+
+// The tracks of one call and the grids over them, laid out and uploaded once.  The host
+// tables live as long as the call, so the uploads need no synchronisation of their own.
+struct TracksLayout {
+    int n = 0, kind = 0, channels = 0;
+    std::vector<TrackDev> tr;
+    std::vector<uint32_t> first_need, first_apply, first_gain;
+    TracksArgs a{};
+    const uint32_t *d_first_gain = nullptr;
+    // the parameters of the queued launches: untouched until the synchronisation behind them
+    std::vector<TrackPar> par, par_trim;
+    std::vector<GainTrack> gain[2];
+};
+
+int64_t gain_wgs(const void *dst, int kind, int64_t n) {
+    if (n == 0) return 0;
+    const int64_t sb = (int64_t)pcm_sample_bytes(kind);
+    const int64_t head = std::min<int64_t>(n, (int64_t)((16 - ((uintptr_t)dst & 15)) & 15) / sb);
+    const int64_t nvec = (n - head) / (16 / sb), vpb = LEVEL_SPAN / (16 / sb);
+    return std::max<int64_t>(1, (nvec + vpb - 1) / vpb);
+}
+
+int tracks_prepare(mm_ctx *c, void *const *d_pcm, int kind, const int64_t *frames, int n, int channels, TracksLayout &L) {
+    L.n = n;
+    L.kind = kind;
+    L.channels = channels;
+    L.tr.resize((size_t)n);
+    std::vector<int64_t> need((size_t)n), apply((size_t)n), gain((size_t)n);
+    for (int t = 0; t < n; ++t) {
+        L.tr[(size_t)t] = TrackDev{d_pcm[t], frames[t]};
+        need[(size_t)t] = tracks_need_spans(frames[t]);
+        apply[(size_t)t] = tracks_apply_spans(frames[t]);
+        gain[(size_t)t] = gain_wgs(d_pcm[t], kind, frames[t] * channels);
+    }
+    L.first_need.resize((size_t)n + 1);
+    L.first_apply.resize((size_t)n + 1);
+    L.first_gain.resize((size_t)n + 1);
+    tracks_prefix(need.data(), n, L.first_need.data());
+    tracks_prefix(apply.data(), n, L.first_apply.data());
+    tracks_prefix(gain.data(), n, L.first_gain.data());
+    TrackDev *d_tr;
+    uint32_t *d_first;
+    RET(get_buf(c, "tracks_tr", (size_t)n, &d_tr));
+    RET(get_buf(c, "tracks_first", 3 * ((size_t)n + 1), &d_first));
+    RET(get_buf(c, "tracks_r", (size_t)std::max<int64_t>(1, tracks_plane_total(L.first_need.data(), n)), &L.a.plane));
+    RET(get_buf(c, "tracks_st", (size_t)n, &L.a.st));
+    RET(get_buf(c, "tracks_peak", (size_t)n, &L.a.peak));
+    const size_t fb = ((size_t)n + 1) * sizeof(uint32_t);
+    HIPCHK(c, hipMemcpyAsync(d_tr, L.tr.data(), (size_t)n * sizeof(TrackDev), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_first, L.first_need.data(), fb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_first + n + 1, L.first_apply.data(), fb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_first + 2 * (n + 1), L.first_gain.data(), fb, hipMemcpyHostToDevice, c->stream));
+    L.a.tr = d_tr;
+    L.a.first_need = d_first;
+    L.a.first_apply = d_first + n + 1;
+    L.d_first_gain = d_first + 2 * (n + 1);
+    L.a.n = n;
+    return MM_OK;
+}
+
+// The segmented ceiling, in place: every track t with Cs[t] != 0 held under Cs[t], out[t]
+// filled as ceiling_device fills it; the other tracks and their out[t] are not touched.
+// Need, apply and the peak behind one synchronisation; the trims and their peak behind one
+// more, when a track is left with a residue.  Synchronous on return.
+int tracks_ceiling(mm_ctx *c, TracksLayout &L, const int32_t *Cs, int32_t W, mm_ceiling *out) {
+    const int n = L.n;
+    bool any = false;
+    L.par.assign((size_t)n, TrackPar{});
+    for (int t = 0; t < n; ++t) {
+        if (!Cs[t]) continue;
+        ceiling_clear(&out[t], L.tr[(size_t)t].frames, L.channels, Cs[t], W);
+        if (L.tr[(size_t)t].frames == 0) continue;
+        L.par[(size_t)t] = TrackPar{Cs[t], Cs[t] - CEIL_GUARD, 0, 1};
+        any = true;
+    }
+    if (!any) {  // nothing to queue; the layout's uploads may still be on the stream
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return MM_OK;
+    }
+    TrackPar *d_par, *d_par_trim;
+    RET(get_buf(c, "tracks_par", (size_t)n, &d_par));
+    RET(get_buf(c, "tracks_par_trim", (size_t)n, &d_par_trim));
+    HIPCHK(c, hipMemcpyAsync(d_par, L.par.data(), (size_t)n * sizeof(TrackPar), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(L.a.st, 0, (size_t)n * sizeof(CeilDev), c->stream));
+    HIPCHK(c, hipMemsetAsync(L.a.peak, 0, (size_t)n * sizeof(unsigned), c->stream));
+    TracksArgs a = L.a;
+    a.par = d_par;
+    a.W = W;
+    a.rcp = (unsigned)(((uint64_t)1 << 32) / (uint64_t)(2 * W + 1));
+    const dim3 gn(L.first_need[(size_t)n]), bn(METER_THREADS), ga(L.first_apply[(size_t)n]), ba(CEIL_THREADS);
+    auto peak = [&]() {
+        return dispatch_pcm(L.kind, L.channels, [&](auto ch, auto t) {
+            using T = decltype(t);
+            return launch(c, "ceil_tracks_peak", ceil_tracks_peak_kernel<ch, T>, gn, bn, 0, a);
+        });
+    };
+    RET(dispatch_pcm(L.kind, L.channels, [&](auto ch, auto t) {
+        using T = decltype(t);
+        RET(launch(c, "ceil_tracks_need", ceil_tracks_need_kernel<ch, T>, gn, bn, 0, a));
+        return launch(c, "ceil_tracks_apply", ceil_tracks_apply_kernel<ch, T>, ga, ba, 0, a);
+    }));
+    RET(peak());
+    std::vector<CeilDev> hs((size_t)n);
+    std::vector<unsigned> hp((size_t)n);
+    HIPCHK(c, hipMemcpyAsync(hs.data(), L.a.st, (size_t)n * sizeof(CeilDev), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hp.data(), L.a.peak, (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    bool trim = false;
+    L.par_trim.assign((size_t)n, TrackPar{});
+    for (int t = 0; t < n; ++t) {
+        if (!L.par[(size_t)t].active) continue;
+        const int32_t C = Cs[t];
+        mm_ceiling *o = &out[t];
+        o->tp_in_q28 = (int32_t)hs[(size_t)t].tp0;
+        o->tp_limited_q28 = o->tp_out_q28 = o->tp_in_q28 <= C ? o->tp_in_q28 : (int32_t)hp[(size_t)t];
+        o->min_gain_q16 = CEIL_ONE - (int32_t)hs[(size_t)t].max_red;
+        o->limited_frames = (int64_t)hs[(size_t)t].limited;
+        if (o->tp_limited_q28 > C) {  // the residue: one static trim, provably under C
+            const int gt = (int)(((int64_t)(C - CEIL_GUARD) << 16) / o->tp_limited_q28);
+            L.par_trim[(size_t)t] = TrackPar{C, C - CEIL_GUARD, gt, 1};
+            o->trim_q16 = gt;
+            trim = true;
+        }
+    }
+    if (trim) {
+        HIPCHK(c, hipMemcpyAsync(d_par_trim, L.par_trim.data(), (size_t)n * sizeof(TrackPar), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemsetAsync(L.a.peak, 0, (size_t)n * sizeof(unsigned), c->stream));
+        a.par = d_par_trim;
+        RET(dispatch_pcm(L.kind, 1, [&](auto, auto t) {
+            using T = decltype(t);
+            return launch(c, "ceil_tracks_trim", ceil_tracks_trim_kernel<T>, ga, ba, 0, a, L.channels);
+        }));
+        RET(peak());
+        HIPCHK(c, hipMemcpyAsync(hp.data(), L.a.peak, (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (int t = 0; t < n; ++t)
+            if (L.par_trim[(size_t)t].active) out[t].tp_out_q28 = (int32_t)hp[(size_t)t];
+    }
+    resolve_events(c);
+    return MM_OK;
+}
+
+// One segmented gain, queued: every track t with g[t] != 0 from from[t] to to[t] (to[t] at its
+// delivered buffer's offset within 16 bytes: the grid was laid out for it) by g[t], the
+// statistics folded into st[t], which the caller zeroed on the stream.  `slot`: which of the
+// layout's two parameter tables the launch keeps until the next synchronisation.
+int tracks_gain_queue(mm_ctx *c, TracksLayout &L, int slot, const void *const *from, void *const *to, const int32_t *g,
+                      LevelDev *st) {
+    const int n = L.n;
+    const size_t sb = pcm_sample_bytes(L.kind);
+    std::vector<GainTrack> &tab = L.gain[slot];
+    tab.assign((size_t)n, GainTrack{});
+    bool any = false;
+    for (int t = 0; t < n; ++t) {
+        const int64_t ns = L.tr[(size_t)t].frames * L.channels;
+        if (!g[t] || ns == 0) continue;
+        const int head = (int)std::min<int64_t>(ns, (int64_t)(((16 - ((uintptr_t)to[t] & 15)) & 15) / sb));
+        const int src_vec = ((((uintptr_t)from[t]) ^ ((uintptr_t)to[t])) & 15) == 0;
+        tab[(size_t)t] = GainTrack{from[t], to[t], ns, head, src_vec, (int)g[t], 1};
+        any = true;
+    }
+    if (!any) return MM_OK;
+    GainTrack *d_tab;
+    RET(get_buf(c, slot ? "tracks_gain_b" : "tracks_gain_a", (size_t)n, &d_tab));
+    HIPCHK(c, hipMemcpyAsync(d_tab, tab.data(), (size_t)n * sizeof(GainTrack), hipMemcpyHostToDevice, c->stream));
+    const dim3 grid(L.first_gain[(size_t)n]), block(LEVEL_THREADS);
+    return dispatch_pcm(L.kind, 1, [&](auto, auto t) {  // (pointwise: the samples as one mono line)
+        using T = decltype(t);
+        return launch(c, "level_tracks_gain", level_tracks_gain_kernel<T>, grid, block, 0, (const GainTrack *)d_tab,
+                      L.d_first_gain, n, st);
+    });
+}
+
+// Refuses what is not a batch (MM_ERR_ARG, the sentence in mm_last_error names the track),
+// before anything is queued.  clu == null: a ceiling alone, which every track then has.
+int batch_check(mm_ctx *c, const void *const *pcm, int kind, const int64_t *frames, int n, int channels, int rate,
+                const double sos[2][5], const int32_t *clu, const int32_t *C, int32_t W) {
+    if (n < 1 || n > MM_ALBUM_TRACKS) return set_err(c, MM_ERR_ARG, "batch: %d tracks out of range [1, %d]", n, MM_ALBUM_TRACKS);
+    if (!pcm || !frames || !C || (clu && !sos)) return set_err(c, MM_ERR_ARG, "bad arguments");
+    if (!pcm_kind_ok(kind)) return set_err(c, MM_ERR_ARG, PCM_BAD_KIND, kind);
+    int64_t total = 0;
+    for (int t = 0; t < n; ++t) {
+        const char *why = clu ? level_bad_args(frames[t], channels, rate, clu[t], C[t], W) : ceiling_bad_args(frames[t], channels, C[t], W);
+        if (why) return set_err(c, MM_ERR_ARG, "batch: track %d: %s", t, why);
+        if (frames[t] > 0 && !pcm[t]) return set_err(c, MM_ERR_ARG, "batch: track %d: null pointer", t);
+        total += frames[t];
+        if (total >= R128_MAX_FRAMES) return set_err(c, MM_ERR_ARG, "batch: track %d: 2^31 frames or more in all", t);
+    }
+    return MM_OK;
+}
+
+// The level of a batch on device-resident tracks, in place (synchronous on return): every
+// track runs level_device's state machine, all of them one pass at a time, and a track
+// leaves the passes when its status is decided.  Arguments already checked.  The results go
+// behind mm_last_levels, mm_last_ceilings and mm_last_r128.
+int batch_level_device(mm_ctx *c, void *const *d_pcm, int kind, const int64_t *frames, int n, int channels, int32_t rate,
+                       const double sos[2][5], const int32_t *clu, const int32_t *C, int32_t W) {
+    results_reset(c);
+    const size_t N = (size_t)n;
+    std::vector<mm_level> lv(N);
+    std::vector<mm_ceiling> ceil(N), ce_in(N);
+    std::vector<mm_r128> rep(N);
+    bool any_ceiling = false;
+    for (int t = 0; t < n; ++t) {
+        level_clear(&lv[(size_t)t], frames[t], channels, rate, clu[t], C[t], W);
+        memset(&ceil[(size_t)t], 0, sizeof(mm_ceiling));
+        ceil[(size_t)t].channels = channels;
+        any_ceiling |= C[t] != 0;
+    }
+    TracksLayout L;
+    RET(tracks_prepare(c, d_pcm, kind, frames, n, channels, L));
+    // one segmented measurement of the tracks `set`: their reports into rep
+    auto measure = [&](const std::vector<int> &set) -> int {
+        std::vector<const void *> p;
+        std::vector<int64_t> f;
+        for (int t : set) {
+            p.push_back(d_pcm[t]);
+            f.push_back(frames[t]);
+        }
+        AlbumPass pass;
+        std::vector<double> e;
+        std::vector<mm_r128> tr;
+        mm_r128 pooled;
+        RET(album_pass_prepare(c, p.data(), kind, f.data(), (int)set.size(), channels, rate, sos, pass));
+        RET(album_pass_hops(c, pass, e));
+        album_reports(e, pass, f.data(), &pooled, tr);
+        for (size_t i = 0; i < set.size(); ++i) rep[(size_t)set[i]] = tr[i];
+        return MM_OK;
+    };
+    auto done = [&]() {
+        c->levels = lv;
+        if (any_ceiling) c->ceilings = ceil;
+        c->r128s = rep;
+        return MM_OK;
+    };
+    std::vector<int> active((size_t)n);
+    for (int t = 0; t < n; ++t) active[(size_t)t] = t;
+    RET(measure(active));
+    active.clear();
+    std::vector<int32_t> Cs(N, 0);
+    std::vector<int> again;
+    for (int t = 0; t < n; ++t) {
+        lv[(size_t)t].source_lufs = rep[(size_t)t].integrated;
+        if (std::isfinite(rep[(size_t)t].integrated)) {
+            active.push_back(t);
+            continue;
+        }
+        lv[(size_t)t].status = MM_LEVEL_UNMEASURABLE;  // fewer than 4 hops, or silence: only its ceiling
+        Cs[(size_t)t] = C[t];
+    }
+    if (std::any_of(Cs.begin(), Cs.end(), [](int32_t v) { return v != 0; })) {
+        RET(tracks_ceiling(c, L, Cs.data(), W, ceil.data()));
+        for (int t = 0; t < n; ++t) {
+            if (!Cs[(size_t)t]) continue;
+            lv[(size_t)t].limited_frames = ceil[(size_t)t].limited_frames;
+            lv[(size_t)t].min_gain_q16 = ceil[(size_t)t].min_gain_q16;
+            if (ceil[(size_t)t].tp_in_q28 > Cs[(size_t)t]) again.push_back(t);
+        }
+        if (!again.empty()) RET(measure(again));  // the reports describe what is delivered
+    }
+    if (active.empty()) return done();
+    // the sources, kept in one buffer, each at its delivered buffer's offset within 16 bytes
+    std::vector<const void *> src(N, nullptr), from(N, nullptr);
+    std::vector<void *> keep_at(N, nullptr), to(N, nullptr);
+    size_t keep_bytes = 0;
+    for (int t = 0; t < n; ++t) keep_bytes += ((pcm_bytes(kind, frames[t], channels) + 15) & ~(size_t)15) + 16;
+    char *keep;
+    LevelDev *st, *st_copy;
+    std::vector<LevelDev> hs(N), hs_copy(N);
+    RET(get_buf(c, "batch_src", keep_bytes, &keep));
+    RET(get_buf(c, "batch_res", N, &st));
+    RET(get_buf(c, "batch_res_copy", N, &st_copy));
+    for (int t = 0; t < n; ++t) {
+        keep_at[(size_t)t] = keep + ((uintptr_t)d_pcm[t] & 15);
+        src[(size_t)t] = keep_at[(size_t)t];
+        keep += ((pcm_bytes(kind, frames[t], channels) + 15) & ~(size_t)15) + 16;
+    }
+    // the copies through the kernel at ONE (the identity), all tracks in one launch: they bring
+    // max |s| of every track, which caps the gain of a track without a ceiling
+    std::vector<int32_t> g(N, 0), g_copy(N, 0), g_peak(N, LEVEL_GMAX);
+    for (int t : active) {
+        g_copy[(size_t)t] = LEVEL_ONE;
+        from[(size_t)t] = d_pcm[t];
+    }
+    HIPCHK(c, hipMemsetAsync(st_copy, 0, N * sizeof(LevelDev), c->stream));
+    RET(tracks_gain_queue(c, L, 0, from.data(), keep_at.data(), g_copy.data(), st_copy));
+    HIPCHK(c, hipMemcpyAsync(hs_copy.data(), st_copy, N * sizeof(LevelDev), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int t : active) {
+        if (!C[t]) g_peak[(size_t)t] = level_peak_cap((int32_t)hs_copy[(size_t)t].peak);
+        g[(size_t)t] = level_first(&lv[(size_t)t]);
+    }
+    std::vector<char> capped(N), boost(N);
+    while (!active.empty()) {
+        bool any_boost = false, any_C = false;
+        std::fill(Cs.begin(), Cs.end(), 0);
+        std::fill(g_copy.begin(), g_copy.end(), 0);
+        for (int t : active) {
+            const size_t i = (size_t)t;
+            capped[i] = boost[i] = 0;
+            from[i] = src[i];
+            to[i] = d_pcm[t];
+            if (!C[t]) {
+                if (g[i] > g_peak[i]) g[i] = g_peak[i], capped[i] = 1;
+            } else if (g[i] > LEVEL_ONE) {  // the limiter before the boost, so that the boost cannot clip first
+                const int32_t g_cap = level_boost_cap(C[t]);
+                if (g[i] > g_cap) g[i] = g_cap, capped[i] = 1;
+                boost[i] = 1;
+                any_boost = true;
+                g_copy[i] = LEVEL_ONE;
+                Cs[i] = level_inner_ceiling(C[t], g[i]);
+                from[i] = d_pcm[t];
+            }
+            any_C |= C[t] != 0;
+        }
+        if (any_boost) {  // source -> delivered (the identity again), then the inner ceilings
+            HIPCHK(c, hipMemsetAsync(st_copy, 0, N * sizeof(LevelDev), c->stream));
+            RET(tracks_gain_queue(c, L, 0, src.data(), to.data(), g_copy.data(), st_copy));
+            RET(tracks_ceiling(c, L, Cs.data(), W, ce_in.data()));
+        }
+        HIPCHK(c, hipMemsetAsync(st, 0, N * sizeof(LevelDev), c->stream));
+        RET(tracks_gain_queue(c, L, 1, from.data(), to.data(), g.data(), st));
+        HIPCHK(c, hipMemcpyAsync(hs.data(), st, N * sizeof(LevelDev), hipMemcpyDeviceToHost, c->stream));  // (behind the next sync)
+        if (any_C) {
+            std::fill(Cs.begin(), Cs.end(), 0);
+            for (int t : active) Cs[(size_t)t] = C[t];
+            RET(tracks_ceiling(c, L, Cs.data(), W, ceil.data()));
+            for (int t : active)
+                if (C[t] && !boost[(size_t)t]) ce_in[(size_t)t] = ceil[(size_t)t];
+        }
+        RET(measure(active));
+        std::vector<int> next;
+        for (int t : active) {
+            const size_t i = (size_t)t;
+            mm_level *o = &lv[i];
+            const int k = o->passes++;
+            o->pass_gain_q16[k] = g[i];
+            o->pass_lufs[k] = rep[i].integrated;
+            o->clipped = (int64_t)hs[i].clipped;
+            if (C[t]) {
+                o->limited_frames = ce_in[i].limited_frames;
+                o->min_gain_q16 = ce_in[i].min_gain_q16;
+            }
+            g[i] = level_next(o, capped[i] != 0);
+            if (g[i]) next.push_back(t);
+        }
+        active.swap(next);
+    }
+    return done();
+}
+
+// d[t] back into pcm[t] for the tracks `pick` names (null: all), synchronous
+int batch_download(mm_ctx *c, void *const *pcm, const std::vector<void *> &d, int kind, const int64_t *frames, int n,
+                   int channels, const char *pick) {
+    for (int t = 0; t < n; ++t) {
+        const size_t bytes = pcm_bytes(kind, frames[t], channels);
+        if (bytes && (!pick || pick[t])) HIPCHK(c, hipMemcpyAsync(pcm[t], d[(size_t)t], bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MM_OK;
+}
+
+int batch_ceiling_device(mm_ctx *c, void *const *d_pcm, int kind, const int64_t *frames, int n, int channels,
+                         const int32_t *C, int32_t W, mm_ceiling *out) {
+    TracksLayout L;
+    RET(tracks_prepare(c, d_pcm, kind, frames, n, channels, L));
+    return tracks_ceiling(c, L, C, W, out);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mm_batch_ceiling_device(mm_ctx *c, void *const *d_pcm, int kind, const int64_t *frames, int n, int channels,
+                            const int32_t *ceiling_q28, int32_t window, mm_ceiling *out) {
+    if (!c) return MM_ERR_ARG;
+    if (!out) return set_err(c, MM_ERR_ARG, "bad arguments");
+    RET(batch_check(c, d_pcm, kind, frames, n, channels, 0, nullptr, nullptr, ceiling_q28, window));
+    HIPCHK(c, hipSetDevice(c->device));
+    return batch_ceiling_device(c, d_pcm, kind, frames, n, channels, ceiling_q28, window, out);
+}
+
+int mm_batch_ceiling_pcm(mm_ctx *c, void *const *pcm, int kind, const int64_t *frames, int n, int channels,
+                         const int32_t *ceiling_q28, int32_t window, mm_ceiling *out) {
+    if (!c) return MM_ERR_ARG;
+    if (!out) return set_err(c, MM_ERR_ARG, "bad arguments");
+    RET(batch_check(c, pcm, kind, frames, n, channels, 0, nullptr, nullptr, ceiling_q28, window));
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<void *> d;
+    RET(album_upload(c, "batch_io", pcm, kind, frames, n, channels, d));
+    RET(batch_ceiling_device(c, d.data(), kind, frames, n, channels, ceiling_q28, window, out));
+    std::vector<char> pick((size_t)n);  // (an untouched track is not copied back)
+    for (int t = 0; t < n; ++t) pick[(size_t)t] = out[t].tp_in_q28 > ceiling_q28[t];
+    return batch_download(c, pcm, d, kind, frames, n, channels, pick.data());
+}
+
+int mm_batch_level_device(mm_ctx *c, void *const *d_pcm, int kind, const int64_t *frames, int n, int channels, int32_t rate,
+                          const double sos[2][5], const int32_t *level_clu, const int32_t *ceiling_q28, int32_t window) {
+    if (!c) return MM_ERR_ARG;
+    if (!level_clu) return set_err(c, MM_ERR_ARG, "bad arguments");
+    RET(batch_check(c, d_pcm, kind, frames, n, channels, rate, sos, level_clu, ceiling_q28, window));
+    HIPCHK(c, hipSetDevice(c->device));
+    return batch_level_device(c, d_pcm, kind, frames, n, channels, rate, sos, level_clu, ceiling_q28, window);
+}
+
+int mm_batch_level_pcm(mm_ctx *c, void *const *pcm, int kind, const int64_t *frames, int n, int channels, int32_t rate,
+                       const double sos[2][5], const int32_t *level_clu, const int32_t *ceiling_q28, int32_t window) {
+    if (!c) return MM_ERR_ARG;
+    if (!level_clu) return set_err(c, MM_ERR_ARG, "bad arguments");
+    RET(batch_check(c, pcm, kind, frames, n, channels, rate, sos, level_clu, ceiling_q28, window));
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<void *> d;
+    RET(album_upload(c, "batch_io", pcm, kind, frames, n, channels, d));
+    RET(batch_level_device(c, d.data(), kind, frames, n, channels, rate, sos, level_clu, ceiling_q28, window));
+    return batch_download(c, pcm, d, kind, frames, n, channels, nullptr);
+}
+
+}  // extern "C"

@@ -430,14 +430,13 @@ def level_pcm(pcm: np.ndarray, rate: int, target_lufs: float, ceiling_dbtp: floa
     return x, level_dict(m)
 
 
-def _album_tracks(tracks):
-    """The tracks of an album as the album entries take them: (arrays, kind, channels, the
-    pointer array's element addresses, frames as a c_int64 array).  ValueError for what is
-    not an album: no track or more than native.ALBUM_TRACKS, or tracks that differ in
-    channel count or sample type."""
+def _album_tracks(tracks, what: str = "an album"):
+    """The tracks of an album (or of `what`) as the album entries take them: (arrays, kind,
+    channels, frames as a c_int64 array).  ValueError for what is not an album: no track or
+    more than native.ALBUM_TRACKS, or tracks that differ in channel count or sample type."""
     tracks = list(tracks)
     if not 1 <= len(tracks) <= native.ALBUM_TRACKS:
-        raise ValueError(f"an album has 1 to {native.ALBUM_TRACKS} tracks, not {len(tracks)}")
+        raise ValueError(f"{what} has 1 to {native.ALBUM_TRACKS} tracks, not {len(tracks)}")
     xs, kinds, chs = [], set(), set()
     for t in tracks:
         x, kind = _out_kind(np.asarray(t))
@@ -445,9 +444,9 @@ def _album_tracks(tracks):
         kinds.add(kind)
         chs.add(1 if x.ndim == 1 else x.shape[1])
     if len(chs) != 1:
-        raise ValueError("the tracks of an album must have one channel count")
+        raise ValueError(f"the tracks of {what} must have one channel count")
     if len(kinds) != 1:
-        raise ValueError("the tracks of an album must have one sample type (all int16 or all float32)")
+        raise ValueError(f"the tracks of {what} must have one sample type (all int16 or all float32)")
     frames = (ctypes.c_int64 * len(xs))(*[x.shape[0] for x in xs])
     return xs, kinds.pop(), chs.pop(), frames
 
@@ -501,6 +500,74 @@ def album_level_pcm(tracks, rate: int, target_lufs: float, ceiling_dbtp: float |
     ctx.check(ctx.lib.mm_album_level_pcm(ctx.ptr, _pointers([x.ctypes.data for x in xs]), kind, frames, len(xs), ch,
                                          int(rate), kweight_sos(rate), clu, C, w), "mm_album_level_pcm")
     return xs, _album_dict(ctx, len(xs), bool(C))
+
+
+def _per_track(value, n: int, what: str) -> list:
+    """A scalar, or one value per track, as a list of n.  ValueError for a sequence of another length."""
+    if isinstance(value, (list, tuple, np.ndarray)):
+        if len(value) != n:
+            raise ValueError(f"{what}: {len(value)} values for {n} tracks")
+        return list(value)
+    return [value] * n
+
+
+def _batch_targets(n: int, target_lufs, ceiling_dbtp, name: str = "target_lufs"):
+    """Per-track targets and ceilings as the batch level takes them: (level_clu, ceiling_q28) as
+    c_int32 arrays (a ceiling of None: 0, no ceiling for that track)."""
+    clu = [design.level_clu(v) for v in _per_track(target_lufs, n, name)]
+    C = [0 if v is None else design.ceiling_q28(v) for v in _per_track(ceiling_dbtp, n, "ceiling_dbtp")]
+    return (ctypes.c_int32 * n)(*clu), (ctypes.c_int32 * n)(*C)
+
+
+def _batch_dicts(ctx: native.Context, C) -> list:
+    """The results of the context's last batch level: one level_dict a track with its "r128"
+    (r128_dict of the delivered samples) and, where that track has a ceiling, "ceiling"."""
+    n = len(C)
+    out = [level_dict(m) for m in levels(ctx, n)]
+    for d, r in zip(out, r128s(ctx, n)):
+        d["r128"] = r128_dict(r)
+    if any(C):
+        for d, q, ce in zip(out, C, ceilings(ctx, n)):
+            if q:
+                d["ceiling"] = ceiling_dict(ce)
+    return out
+
+
+def ceiling_batch_pcm(tracks, rate: int, ceiling_dbtp, window: int | None = None, device: int = 0):
+    """Hold the tracks of a batch (int16 or float32 = int16 / 32768 arrays [N] or [N, ch], one
+    channel count and sample type) under their true-peak ceilings, `ceiling_dbtp` a scalar or one
+    value per track, without mastering them (mm_batch_ceiling_pcm: the ceiling's launches each
+    cover all tracks).  Every track receives what ceiling_pcm gives on it alone.  Returns (new
+    arrays, [ceiling_dict ...])."""
+    xs, kind, ch, frames = _album_tracks(tracks, "a batch")
+    n = len(xs)
+    C = (ctypes.c_int32 * n)(*[design.ceiling_q28(v) for v in _per_track(ceiling_dbtp, n, "ceiling_dbtp")])
+    xs = [x.copy() for x in xs]
+    w = design.ceiling_window(rate) if window is None else int(window)
+    ctx = native.context(device)
+    out = (native.MMCeiling * n)()
+    ctx.check(ctx.lib.mm_batch_ceiling_pcm(ctx.ptr, _pointers([x.ctypes.data for x in xs]), kind, frames, n, ch, C, w, out),
+              "mm_batch_ceiling_pcm")
+    return xs, [ceiling_dict(m) for m in out]
+
+
+def level_batch_pcm(tracks, rate: int, target_lufs, ceiling_dbtp=None, window: int | None = None, device: int = 0):
+    """Level the tracks of a batch (int16 or float32 = int16 / 32768 arrays [N] or [N, ch], one
+    rate, channel count and sample type), every track to its OWN `target_lufs` under its own
+    `ceiling_dbtp` (each a scalar or one value per track; a ceiling of None: none for that track):
+    mm_batch_level_pcm.  Every track receives what level_pcm gives on it alone, bit for bit; the
+    passes of all tracks run in lockstep, every launch over all tracks.  Returns (new arrays,
+    [level_dict ...]), each dict with "r128" (the delivered samples' r128_dict) and, where that
+    track has a ceiling, "ceiling"."""
+    xs, kind, ch, frames = _album_tracks(tracks, "a batch")
+    n = len(xs)
+    clu, C = _batch_targets(n, target_lufs, ceiling_dbtp)
+    xs = [x.copy() for x in xs]
+    w = design.ceiling_window(rate) if window is None else int(window)
+    ctx = native.context(device)
+    ctx.check(ctx.lib.mm_batch_level_pcm(ctx.ptr, _pointers([x.ctypes.data for x in xs]), kind, frames, n, ch, int(rate),
+                                         kweight_sos(rate), clu, C, w), "mm_batch_level_pcm")
+    return xs, _batch_dicts(ctx, list(C))
 
 
 def resample_dict(m: native.MMResample) -> dict:
@@ -764,6 +831,98 @@ def process_album(input_paths, output_paths, params: dict, device: int = 0):
         wavio.write_wav(path, y[:, 0] if job.channels == 1 else y, job.rate)
         infos.append(dict(_info(job, r), output_path=os.path.abspath(path)))
     return infos, album
+
+
+def deliver_batch(ctx: native.Context, jobs, d_ins, d_outs, deliver_lufs, ceiling_dbtp=None):
+    """Master the tracks of a batch (master_batch) and level every track in place on `d_outs` to
+    its own target (mm_batch_level_device): `deliver_lufs` and `ceiling_dbtp` are each a scalar
+    or one value per job (a ceiling of None: none for that job).  The jobs are planned without
+    ceiling, delivery, level, report or r128 (the batch level resets the context's per-call
+    results, so a batch's meters would be lost without a word) and share one rate, channel count
+    and output kind: anything else is a ValueError before anything runs.  Returns (the batch's
+    results, [level_dict ...] as level_batch_pcm's); `levels(ctx)` / `r128s(ctx)` / `ceilings(ctx)`
+    then hold the per-track results of the levelled tracks, as after a batch."""
+    jobs = list(jobs)
+    if not 1 <= len(jobs) <= native.ALBUM_TRACKS:
+        raise ValueError(f"a batch to deliver has 1 to {native.ALBUM_TRACKS} tracks, not {len(jobs)}")
+    if any(j.delivery is not None for j in jobs):
+        raise ValueError("the jobs of a batch to deliver are planned without a delivery (output_rate, deliver_lufs): "
+                         "the batch call levels them")
+    if any(j.job.ceiling_q28 for j in jobs):
+        raise ValueError("the jobs of a batch to deliver are planned without ceiling_dbtp: the batch call holds the ceiling")
+    if any(j.job.meter_on for j in jobs):
+        raise ValueError("the jobs of a batch to deliver are planned without report or r128: they would describe the "
+                         "tracks before the level, and the batch call's own per-track reports replace them")
+    if len({j.rate for j in jobs}) != 1:
+        raise ValueError("the tracks of a batch to deliver must have one sample rate")
+    if len({j.channels for j in jobs}) != 1:
+        raise ValueError("the tracks of a batch to deliver must have one channel count")
+    if len({int(j.job.out_kind) for j in jobs}) != 1:
+        raise ValueError("the tracks of a batch to deliver must have one output kind")
+    n, rate, ch, kind = len(jobs), jobs[0].rate, jobs[0].channels, int(jobs[0].job.out_kind)
+    clu, C = _batch_targets(n, deliver_lufs, ceiling_dbtp, "deliver_lufs")
+    res = master_batch(ctx, jobs, d_ins, d_outs)
+    frames = (ctypes.c_int64 * n)(*[j.frames_proc for j in jobs])
+    ctx.check(ctx.lib.mm_batch_level_device(ctx.ptr, _pointers(d_outs), kind, frames, n, ch, rate, kweight_sos(rate), clu, C,
+                                            design.ceiling_window(rate)), "mm_batch_level_device")
+    return res, _batch_dicts(ctx, list(C))
+
+
+def process_batch(input_paths, output_paths, params: dict, device: int = 0):
+    """Master the WAV files of a batch with the same `params` and deliver every file to its own
+    loudness target (deliver_batch): params['deliver_lufs'] (required) is a scalar or one value
+    per file, params['ceiling_dbtp'] (optional) likewise; params['output_format']='f32' writes
+    float.  The files share one rate and channel count.  Returns one info dict a file, with the
+    file's level_dict under "level" (and in it "r128" and, with a ceiling, "ceiling").
+    params['output_rate'] is refused: delivery at another rate is not available for a batch;
+    params['report'] and params['r128'] are refused too: the level dict carries every delivered
+    file's R 128 report and ceiling."""
+    from . import wavio
+    params = dict(params or {})
+    if params.get("deliver_lufs") is None:
+        raise ValueError("process_batch needs params['deliver_lufs']: the loudness target of every file")
+    deliver_lufs = params.pop("deliver_lufs")
+    ceiling = params.pop("ceiling_dbtp", None)
+    if params.pop("output_rate", None) is not None:
+        raise ValueError("delivery at another rate (output_rate) is not available for a batch")
+    fmt = params.pop("output_format", "pcm16")
+    for key in ("report", "r128"):
+        if params.get(key):
+            raise ValueError(f"process_batch takes no params['{key}']: the level dict carries the R 128 report and "
+                             "the ceiling of every delivered file (meter one with meter_pcm)")
+        params.pop(key, None)
+    input_paths, output_paths = list(input_paths), list(output_paths)
+    if len(input_paths) != len(output_paths):
+        raise ValueError("process_batch needs one output path for every input path")
+    _batch_targets(len(input_paths), deliver_lufs, ceiling, "deliver_lufs")  # (refused before a file is read)
+    kind = native.MM_OUT_F32 if fmt == "f32" else native.MM_OUT_I16
+    pcms, rates = zip(*[wavio.read_wav(p) for p in input_paths]) if input_paths else ((), ())
+    if len(set(rates)) > 1:
+        raise ValueError("the tracks of a batch to deliver must have one sample rate")
+    jobs, xs = [], []
+    for pcm in pcms:
+        job = Job(pcm.shape[0], rates[0], 1 if pcm.ndim == 1 else pcm.shape[1], params, kind)
+        x, job.job.in_kind = _device_input(pcm, wide=True)
+        jobs.append(job)
+        xs.append(x)
+    if len({j.channels for j in jobs}) > 1:
+        raise ValueError("the tracks of a batch to deliver must have one channel count")
+    if not 1 <= len(jobs) <= native.ALBUM_TRACKS:
+        raise ValueError(f"a batch to deliver has 1 to {native.ALBUM_TRACKS} tracks, not {len(jobs)}")
+    import torch  # (plumbing only: the device buffers of the batch)
+    ctx = native.context(device)
+    dev = torch.device("cuda", device)
+    d_ins = [torch.from_numpy(x).to(dev) for x in xs]
+    d_outs = [torch.empty((j.frames_proc, j.channels), dtype=torch.int16 if kind == native.MM_OUT_I16 else torch.float32,
+                          device=dev) for j in jobs]
+    torch.cuda.synchronize(dev)
+    res, lvs = deliver_batch(ctx, jobs, [t.data_ptr() for t in d_ins], [t.data_ptr() for t in d_outs], deliver_lufs, ceiling)
+    infos = []
+    for job, r, lv, out, path in zip(jobs, res, lvs, d_outs, output_paths):
+        y = out.cpu().numpy()
+        wavio.write_wav(path, y[:, 0] if job.channels == 1 else y, job.rate)
+        infos.append(dict(_info(job, r), level=lv, output_path=os.path.abspath(path)))
+    return infos
 
 
 def process(input_path: str, output_path: str, params: dict, device: int = 0, verbose: bool = False) -> dict:

@@ -24,6 +24,7 @@ MAX_DIM, TILE_POW, BLK_POW = 8, 8, 65
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int64_p = ctypes.POINTER(ctypes.c_int64)
+c_int32_p = ctypes.POINTER(ctypes.c_int32)
 
 
 class MMIir(ctypes.Structure):
@@ -161,7 +162,8 @@ EXPORTS = ("mm_create", "mm_destroy", "mm_last_error", "mm_sync", "mm_version", 
            "mm_last_resample", "mm_deliver_device", "mm_deliver", "mm_deliver_wav",
            "mm_level_device", "mm_level_pcm", "mm_level_host", "mm_op_level_gain", "mm_last_levels", "mm_level_span",
            "mm_r128_album_from_hops", "mm_album_level_host", "mm_album_r128_device", "mm_album_r128_pcm",
-           "mm_op_r128_album_hops", "mm_album_level_device", "mm_album_level_pcm", "mm_last_album")
+           "mm_op_r128_album_hops", "mm_album_level_device", "mm_album_level_pcm", "mm_last_album",
+           "mm_batch_ceiling_device", "mm_batch_ceiling_pcm", "mm_batch_level_device", "mm_batch_level_pcm")
 
 _lib = None
 _lock = threading.Lock()
@@ -311,6 +313,14 @@ def load():
             "mm_album_level_pcm": ([vp, P(vp), ctypes.c_int, c_int64_p, ctypes.c_int, ctypes.c_int, ctypes.c_int32,
                                     c_sos_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32], ctypes.c_int),
             "mm_last_album": ([vp, P(MMLevel), P(MMR128)], ctypes.c_int),
+            "mm_batch_ceiling_device": ([vp, P(vp), ctypes.c_int, c_int64_p, ctypes.c_int, ctypes.c_int, c_int32_p,
+                                         ctypes.c_int32, P(MMCeiling)], ctypes.c_int),
+            "mm_batch_ceiling_pcm": ([vp, P(vp), ctypes.c_int, c_int64_p, ctypes.c_int, ctypes.c_int, c_int32_p,
+                                      ctypes.c_int32, P(MMCeiling)], ctypes.c_int),
+            "mm_batch_level_device": ([vp, P(vp), ctypes.c_int, c_int64_p, ctypes.c_int, ctypes.c_int, ctypes.c_int32,
+                                       c_sos_p, c_int32_p, c_int32_p, ctypes.c_int32], ctypes.c_int),
+            "mm_batch_level_pcm": ([vp, P(vp), ctypes.c_int, c_int64_p, ctypes.c_int, ctypes.c_int, ctypes.c_int32,
+                                    c_sos_p, c_int32_p, c_int32_p, ctypes.c_int32], ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             fn = getattr(lib, name)
