@@ -424,7 +424,8 @@ int mm_sync(mm_ctx *ctx);
    (mm_r128_album_from_hops, mm_album_level_host, mm_album_r128_device, mm_album_r128_pcm,
    mm_op_r128_album_hops, mm_album_level_device, mm_album_level_pcm, mm_last_album); and, again
    as entry points only, the batch (mm_batch_ceiling_device, mm_batch_ceiling_pcm,
-   mm_batch_level_device, mm_batch_level_pcm).  A caller
+   mm_batch_level_device, mm_batch_level_pcm) and its converter (mm_batch_resample_device,
+   mm_batch_resample_pcm).  A caller
    built against an older header must
    refuse a library whose version differs from its own MM_ABI_VERSION. */
 #define MM_ABI_VERSION 5
@@ -716,6 +717,26 @@ int mm_resample_host(const int16_t *in, int64_t frames, int channels, const mm_r
 int mm_resample_frames(int64_t frames, int32_t L, int32_t M, int64_t *frames_out);
 /* Output frames per workgroup of the converter's kernel (where its seams lie). */
 int mm_resample_span(void);
+/* Convert n device-resident tracks of one kind, channel count and rate pair, track t from
+ * d_in[t] ([frames[t]][channels]) into d_out[t] ([ceil(frames[t] * L / M)][channels]); out[n]
+ * receives every track's mm_resample.  No numerics are new: track t and out[t] are exactly
+ * what mm_resample_device gives on that track alone; every position is relative to the
+ * track's own start, the zero padding outside [0, frames[t]) included, so tracks that lie back
+ * to back in one allocation never read or write a neighbour's frames (a pointer is aligned to
+ * a frame, as for every entry).  Only the launch structure differs from n calls: one launch
+ * covers the spans of all tracks (csrc/tracks.h), and a call costs one memset, one launch, one
+ * read-back and one synchronisation whatever n (plus the taps upload when the table is not
+ * the context's cached one); a call in which no track has frames launches nothing.
+ * frames[t] == 0 is valid and gives frames_out == 0 (d_in[t] and d_out[t] may then be NULL).
+ * MM_ERR_ARG, with words in mm_last_error that name the track, before anything is queued and
+ * with the context still usable, for n outside [1, MM_ALBUM_TRACKS], a track
+ * mm_resample_device refuses, a geometry or table it refuses, or a total of 2^31 input or
+ * output frames or more.  Synchronous on return. */
+int mm_batch_resample_device(mm_ctx *ctx, const void *const *d_in, int kind, const int64_t *frames, int n, int channels,
+                             const mm_resampler *rs, void *const *d_out, mm_resample *out);
+/* The same on host buffers. */
+int mm_batch_resample_pcm(mm_ctx *ctx, const void *const *in, int kind, const int64_t *frames, int n, int channels,
+                          const mm_resampler *rs, void *const *out_pcm, mm_resample *out);
 /* mm_master_device / mm_master / mm_master_wav with a delivery: the chain runs into a
  * context buffer, the converter writes the caller's output ([frames_out][channels] of
  * job->out_kind; the WAV header carries rate_out and frames_out), then the delivery's

@@ -294,7 +294,7 @@ int album_upload(mm_ctx *c, const char *name, const void *const *pcm, int kind, 
     for (int t = 0; t < n; ++t) {
         const size_t bytes = pcm_bytes(kind, frames[t], channels);
         d[(size_t)t] = base;
-        if (bytes) HIPCHK(c, hipMemcpyAsync(base, pcm[t], bytes, hipMemcpyHostToDevice, c->stream));
+        if (bytes && pcm) HIPCHK(c, hipMemcpyAsync(base, pcm[t], bytes, hipMemcpyHostToDevice, c->stream));
         base += (bytes + 15) & ~(size_t)15;
     }
     return MM_OK;

@@ -12,7 +12,9 @@
 // instruction), the host restatement in int64; the results are the same
 // integers, so nothing depends on the launch geometry.
 //
-// One kernel.  A workgroup owns RS_SPAN consecutive output frames and stages the input
+// One kernel body (resample_span; resample_kernel runs it on the one signal of a call, and
+// tracks.hip's resample_tracks_kernel on every track of a batch in one launch).  A workgroup
+// owns RS_SPAN consecutive output frames and stages the input
 // frames they read in LDS: a line of int16 for mono, and for stereo one dword a frame
 // (left in the low half).  Two de-interleaved int16 lines, as the meter stages its lines,
 // were measured 6.6 times slower for stereo int16: the compiler fuses the reads of two
@@ -62,8 +64,12 @@ struct RsArgs {
 // outputs are o = r + (jc + jj * nJC) * L < cnt, jj < RS_R (interleaved j, so that with
 // L = 1 the lanes of a wave are consecutive outputs).  An output beyond cnt computes on
 // the item's first output's samples (always in range) and is not stored.
+//
+// resample_span is that workgroup: one span of one signal, `n0` its first output frame and
+// every position relative to the signal's own start.  resample_kernel runs it on the one
+// signal of a call; resample_tracks_kernel (tracks.hip) on the span of a track of a batch.
 template <int CH, typename T>
-__global__ void __launch_bounds__(RS_THREADS) resample_kernel(const T *__restrict__ in, T *__restrict__ out, RsArgs a) {
+__device__ __forceinline__ void resample_span(const T *__restrict__ in, T *__restrict__ out, RsArgs a, int64_t n0) {
     // mono: int16 samples; stereo: one dword a frame, left in the low half
     __shared__ __attribute__((aligned(16))) uint32_t lds[CH == 2 ? RS_LINE : RS_LINE / 2];
     int16_t *const line = reinterpret_cast<int16_t *>(lds);
@@ -71,7 +77,6 @@ __global__ void __launch_bounds__(RS_THREADS) resample_kernel(const T *__restric
     __shared__ int red_pk[CH][RS_THREADS / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int L = a.L, M = a.M, K = a.K;
-    const int64_t n0 = (int64_t)blockIdx.x * RS_SPAN;
     const int span = a.Nout - n0 < RS_SPAN ? (int)(a.Nout - n0) : RS_SPAN;
     unsigned n_clip[CH];
     int pk[CH];
@@ -184,6 +189,11 @@ __global__ void __launch_bounds__(RS_THREADS) resample_kernel(const T *__restric
     }
 }
 
+template <int CH, typename T>
+__global__ void __launch_bounds__(RS_THREADS) resample_kernel(const T *__restrict__ in, T *__restrict__ out, RsArgs a) {
+    resample_span<CH, T>(in, out, a, (int64_t)blockIdx.x * RS_SPAN);
+}
+
 }  // namespace mm
 
 // ======================================================= host entry points
@@ -229,6 +239,12 @@ const char *resample_bad_table(const mm_resampler *rs) {
 const char *resample_bad_signal(int64_t frames, int channels, int L, int M) {
     if (const char *why = pcm_refusal(channels, frames, (int64_t)1 << 31)) return why;
     return rs_frames(frames, L, M) >= METER_MAX_FRAMES ? "output frames out of range" : nullptr;
+}
+
+// RsArgs.sub of a (checked) geometry: a piece of `sub` outputs reads
+// ((sub - 1) * M + p0) / L + K <= (sub - 1) * M / L + 1 + K frames
+int resample_sub(const mm_resampler *rs) {
+    return (int)std::min<int64_t>(RS_SPAN, 1 + (int64_t)(RS_LINE - rs->K - 1) * rs->L / rs->M);
 }
 
 void resample_clear(mm_resample *o, int64_t frames, int channels, const mm_resampler *rs) {
@@ -291,8 +307,7 @@ static int resample_device(mm_ctx *c, const void *d_in, int kind, int64_t frames
     a.L = rs->L;
     a.M = rs->M;
     a.K = rs->K;
-    // a piece of `sub` outputs reads ((sub - 1) * M + p0) / L + K <= (sub - 1) * M / L + 1 + K frames
-    a.sub = (int)std::min<int64_t>(RS_SPAN, 1 + (int64_t)(RS_LINE - rs->K - 1) * rs->L / rs->M);
+    a.sub = resample_sub(rs);
     const dim3 grid((unsigned)((a.Nout + RS_SPAN - 1) / RS_SPAN)), block(RS_THREADS);
     RET(dispatch_pcm(kind, channels, [&](auto ch, auto t) {
         using T = decltype(t);

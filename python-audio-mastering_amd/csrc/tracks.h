@@ -8,10 +8,11 @@
 //   track of workgroup w = the largest t with first[t] <= w   (w < first[n])
 // A track without a workgroup (no frames) has first[t] == first[t + 1] and is never found:
 // the largest such t is the track that follows, and after the last track with workgroups
-// first[t] == first[n] > w.  The need grid's prefix sums also place the planes: track t's
-// r - 1 plane holds whole spans at first_need[t] * TRACKS_METER_SPAN of one buffer of
-// first_need[n] * TRACKS_METER_SPAN entries, so planes neither overlap nor leave their
-// spans' 16-byte alignment.
+// first[t] == first[n] > w.  The converter's grid counts spans of OUTPUT frames
+// (tracks_resample_spans of ceil(frames * L / M)).  The need grid's prefix sums also place
+// the planes: track t's r - 1 plane holds whole spans at first_need[t] * TRACKS_METER_SPAN of
+// one buffer of first_need[n] * TRACKS_METER_SPAN entries, so planes neither overlap nor
+// leave their spans' 16-byte alignment.
 #pragma once
 
 #include <stdint.h>
@@ -27,6 +28,7 @@ namespace mm {
 constexpr int TRACKS_MAX = 256;           // MM_ALBUM_TRACKS
 constexpr int TRACKS_METER_SPAN = 2048;   // METER_SPAN: frames m of a need / peak workgroup
 constexpr int TRACKS_CEIL_SPAN = 4096;    // CEIL_SPAN: frames n of an apply / trim workgroup
+constexpr int TRACKS_RS_SPAN = 1024;      // RS_SPAN: output frames of a converter workgroup
 
 // workgroups of a track of `frames` frames on the need / peak grid (m in [0, frames + 11))
 MM_TRACKS_HD inline int64_t tracks_need_spans(int64_t frames) {
@@ -36,6 +38,11 @@ MM_TRACKS_HD inline int64_t tracks_need_spans(int64_t frames) {
 // on the apply / trim grid (n in [0, frames))
 MM_TRACKS_HD inline int64_t tracks_apply_spans(int64_t frames) {
     return frames > 0 ? (frames + TRACKS_CEIL_SPAN - 1) / TRACKS_CEIL_SPAN : 0;
+}
+
+// on the converter's grid (output frames n in [0, frames_out))
+MM_TRACKS_HD inline int64_t tracks_resample_spans(int64_t frames_out) {
+    return frames_out > 0 ? (frames_out + TRACKS_RS_SPAN - 1) / TRACKS_RS_SPAN : 0;
 }
 
 // first[0 .. n] from the workgroups of every track; returns the grid

@@ -1,11 +1,12 @@
-// tracks.hip — the ceiling and the level's gain over n tracks at once, each track with its
-// own parameters, and on them the level of a batch: every track to its OWN R 128 target under
-// its own true-peak ceiling (the batch entries in include/mastering.h).  No reference
-// counterpart.
+// tracks.hip — the ceiling, the level's gain and the sample-rate converter over n tracks at
+// once, each track with its own parameters, and on them the level of a batch: every track to
+// its OWN R 128 target under its own true-peak ceiling, and the conversion of a batch to
+// another rate (the batch entries in include/mastering.h).  No reference counterpart.
 //
 // No numerics are defined here.  Per track the ceiling is mm_ceiling and the level mm_level,
-// bit for bit: the kernels run the single-track bodies (ceiling.hip: ceil_need_span,
-// ceil_apply_span, ceil_scale; level.hip: level_gain_span) and the decisions are level.hip's
+// bit for bit, and the converter mm_resample: the kernels run the single-track bodies
+// (ceiling.hip: ceil_need_span, ceil_apply_span, ceil_scale; level.hip: level_gain_span;
+// resample.hip: resample_span) and the decisions are level.hip's
 // level_first / level_next / level_boost_cap / level_inner_ceiling / level_peak_cap.  What is
 // new is the launch structure: one launch covers the spans of all tracks (tracks.h: a track
 // owns a run of workgroups, a workgroup finds its track by a search over at most 257 prefix
@@ -19,6 +20,10 @@
 //                      store switched off (a track whose TP0 <= C was not touched: skipped)
 //   ceil_tracks_trim   pointwise, the tracks with a residue only, each by its own g_t
 //   level_tracks_gain  level_gain; head and tail single samples by a track's first workgroup
+//   resample_tracks    the converter (resample.hip: resample_span) over all RS_SPAN spans of
+//                      output frames; every position relative to the track's own start, the
+//                      statistics into the track's RsDev (mm_batch_resample_*: one memset,
+//                      one launch, one read-back whatever n)
 // The per-track parameters of a launch are one small array uploaded per pass; a workgroup of
 // a track that takes no part exits on one uniform read of it.
 //
@@ -29,7 +34,8 @@
 
 namespace mm {
 
-static_assert(TRACKS_METER_SPAN == METER_SPAN && TRACKS_CEIL_SPAN == CEIL_SPAN && TRACKS_MAX == MM_ALBUM_TRACKS,
+static_assert(TRACKS_METER_SPAN == METER_SPAN && TRACKS_CEIL_SPAN == CEIL_SPAN && TRACKS_RS_SPAN == RS_SPAN &&
+                  TRACKS_MAX == MM_ALBUM_TRACKS,
               "tracks.h restates the spans");
 
 struct TrackDev {  // one a track, uploaded once a call
@@ -113,6 +119,24 @@ __global__ void __launch_bounds__(LEVEL_THREADS) level_tracks_gain_kernel(const 
     if (!k.active) return;
     level_gain_span<T>(static_cast<const T *>(k.src), static_cast<T *>(k.dst), k.n, k.head, k.src_vec, k.g, st + t,
                        blockIdx.x - first[t]);
+}
+
+struct RsTrack {  // one a track, uploaded once a call
+    const void *in;
+    void *out;
+    int64_t N, Nout;  // the track's own input and output frames
+};
+
+// a.N, a.Nout and a.st are the launch's: st[n], and every workgroup takes N and Nout from its track
+template <int CH, typename T>
+__global__ void __launch_bounds__(RS_THREADS) resample_tracks_kernel(const RsTrack *tr, const uint32_t *first, int n, RsArgs a) {
+    const int t = tracks_find(first, n, blockIdx.x);
+    const RsTrack k = tr[t];
+    a.N = k.N;
+    a.Nout = k.Nout;
+    a.st += t;
+    resample_span<CH, T>(static_cast<const T *>(k.in), static_cast<T *>(k.out), a,
+                         (int64_t)(blockIdx.x - first[t]) * RS_SPAN);
 }
 
 }  // namespace mm
@@ -488,6 +512,76 @@ int batch_ceiling_device(mm_ctx *c, void *const *d_pcm, int kind, const int64_t 
     return tracks_ceiling(c, L, C, W, out);
 }
 
+// Refuses what is not a batch to convert (MM_ERR_ARG, the sentence names the track), before
+// anything is queued.  The table itself is checked where it is uploaded (resample_taps_device),
+// which queues nothing before it has refused.
+int batch_resample_check(mm_ctx *c, const void *const *in, int kind, const int64_t *frames, int n, int channels,
+                         const mm_resampler *rs, void *const *out_pcm, const mm_resample *out) {
+    if (n < 1 || n > MM_ALBUM_TRACKS) return set_err(c, MM_ERR_ARG, "batch: %d tracks out of range [1, %d]", n, MM_ALBUM_TRACKS);
+    if (!in || !frames || !rs || !out_pcm || !out) return set_err(c, MM_ERR_ARG, "bad arguments");
+    if (!pcm_kind_ok(kind)) return set_err(c, MM_ERR_ARG, PCM_BAD_KIND, kind);
+    if (const char *why = resample_bad_geometry(rs->L, rs->M, rs->K)) return set_err(c, MM_ERR_ARG, "resampler: %s", why);
+    int64_t total_in = 0, total_out = 0;
+    for (int t = 0; t < n; ++t) {
+        if (const char *why = resample_bad_signal(frames[t], channels, rs->L, rs->M))
+            return set_err(c, MM_ERR_ARG, "batch: track %d: %s", t, why);
+        if (frames[t] > 0 && (!in[t] || !out_pcm[t])) return set_err(c, MM_ERR_ARG, "batch: track %d: null pointer", t);
+        total_in += frames[t];
+        total_out += rs_frames(frames[t], rs->L, rs->M);
+        if (total_in >= R128_MAX_FRAMES || total_out >= R128_MAX_FRAMES)
+            return set_err(c, MM_ERR_ARG, "batch: track %d: 2^31 frames or more in all", t);
+    }
+    return MM_OK;
+}
+
+// Convert n device-resident tracks, track t from d_in[t] into d_out[t] (synchronous on return):
+// one memset of the n result blocks, one launch over the spans of all tracks, one read-back.
+// Arguments already checked, D the device copy of the taps (resample_taps_device).  The host
+// tables live until the synchronisation at the end.
+int batch_resample_device(mm_ctx *c, const void *const *d_in, int kind, const int64_t *frames, int n, int channels,
+                          const mm_resampler *rs, const int32_t *D, void *const *d_out, mm_resample *out) {
+    RsArgs a{};
+    a.D = D;
+    const size_t N = (size_t)n;
+    std::vector<RsTrack> tr(N);
+    std::vector<int64_t> wgs(N);
+    std::vector<uint32_t> first(N + 1);
+    for (int t = 0; t < n; ++t) {
+        resample_clear(&out[t], frames[t], channels, rs);
+        tr[(size_t)t] = RsTrack{d_in[t], d_out[t], frames[t], out[t].frames_out};
+        wgs[(size_t)t] = tracks_resample_spans(out[t].frames_out);
+    }
+    const uint32_t grid = tracks_prefix(wgs.data(), n, first.data());
+    if (grid == 0) return MM_OK;  // no track has frames
+    RsTrack *d_tr;
+    uint32_t *d_first;
+    RET(get_buf(c, "rs_tracks", N, &d_tr));
+    RET(get_buf(c, "rs_tracks_first", N + 1, &d_first));
+    RET(get_buf(c, "rs_tracks_res", N, &a.st));
+    HIPCHK(c, hipMemcpyAsync(d_tr, tr.data(), N * sizeof(RsTrack), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_first, first.data(), (N + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(a.st, 0, N * sizeof(RsDev), c->stream));
+    a.L = rs->L;
+    a.M = rs->M;
+    a.K = rs->K;
+    a.sub = resample_sub(rs);
+    RET(dispatch_pcm(kind, channels, [&](auto ch, auto t) {
+        using T = decltype(t);
+        return launch(c, "resample_tracks", resample_tracks_kernel<ch, T>, dim3(grid), dim3(RS_THREADS), 0,
+                      (const RsTrack *)d_tr, (const uint32_t *)d_first, n, a);
+    }));
+    std::vector<RsDev> h(N);
+    HIPCHK(c, hipMemcpyAsync(h.data(), a.st, N * sizeof(RsDev), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int t = 0; t < n; ++t)
+        for (int ch = 0; ch < channels; ++ch) {
+            out[t].clipped[ch] = (int64_t)h[(size_t)t].clipped[ch];
+            out[t].peak[ch] = h[(size_t)t].peak[ch];
+        }
+    resolve_events(c);
+    return MM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -534,6 +628,32 @@ int mm_batch_level_pcm(mm_ctx *c, void *const *pcm, int kind, const int64_t *fra
     RET(album_upload(c, "batch_io", pcm, kind, frames, n, channels, d));
     RET(batch_level_device(c, d.data(), kind, frames, n, channels, rate, sos, level_clu, ceiling_q28, window));
     return batch_download(c, pcm, d, kind, frames, n, channels, nullptr);
+}
+
+int mm_batch_resample_device(mm_ctx *c, const void *const *d_in, int kind, const int64_t *frames, int n, int channels,
+                             const mm_resampler *rs, void *const *d_out, mm_resample *out) {
+    if (!c) return MM_ERR_ARG;
+    RET(batch_resample_check(c, d_in, kind, frames, n, channels, rs, d_out, out));
+    HIPCHK(c, hipSetDevice(c->device));
+    const int32_t *D;
+    RET(resample_taps_device(c, rs, &D));
+    return batch_resample_device(c, d_in, kind, frames, n, channels, rs, D, d_out, out);
+}
+
+int mm_batch_resample_pcm(mm_ctx *c, const void *const *in, int kind, const int64_t *frames, int n, int channels,
+                          const mm_resampler *rs, void *const *out_pcm, mm_resample *out) {
+    if (!c) return MM_ERR_ARG;
+    RET(batch_resample_check(c, in, kind, frames, n, channels, rs, out_pcm, out));
+    HIPCHK(c, hipSetDevice(c->device));
+    const int32_t *D;
+    RET(resample_taps_device(c, rs, &D));  // (a table it refuses: before a track is uploaded)
+    std::vector<int64_t> frames_out((size_t)n);
+    for (int t = 0; t < n; ++t) frames_out[(size_t)t] = rs_frames(frames[t], rs->L, rs->M);
+    std::vector<void *> din, dout;
+    RET(album_upload(c, "batch_rs_in", in, kind, frames, n, channels, din));
+    RET(album_upload(c, "batch_rs_out", nullptr, kind, frames_out.data(), n, channels, dout));  // (laid out, nothing copied)
+    RET(batch_resample_device(c, din.data(), kind, frames, n, channels, rs, D, dout.data(), out));
+    return batch_download(c, out_pcm, dout, kind, frames_out.data(), n, channels, nullptr);
 }
 
 }  // extern "C"

@@ -40,13 +40,19 @@ Public surface (mirrors worker/audio_mastering_engine.py):
                                a batch delivered track by track (no reference counterpart):
                                every track to its own R 128 target under its own ceiling, as
                                level_pcm gives it, with every launch of a pass over all tracks
+  resample_batch_pcm(tracks, rate_in, rate_out), deliver_batch(..., output_rate=, d_mids=),
+  master_album(..., output_rate=, d_mids=), process_batch / process_album(..., output_rate=)
+                               a batch or an album delivered at another rate (no reference
+                               counterpart): every track as resample_pcm gives it, all tracks
+                               in one converter launch, then levelled at the new rate
   legacy.master_pcm / legacy.process and main.py's helpers
                                the older monolithic engine (root main.py:46-192) as an
                                alternate DSP profile on the same HIP operators
 """
 from .engine import (EQ_PRESETS, Job, album_level_pcm, album_r128_pcm, ceiling_batch_pcm, ceiling_pcm, ceilings,  # noqa: F401
                      deliver_batch, level_batch_pcm, level_pcm, levels, master_album, master_batch, master_device,
-                     master_pcm, meter_pcm, meters, process, process_album, process_batch, r128_pcm, r128s, resample_pcm)
+                     master_pcm, meter_pcm, meters, process, process_album, process_batch, r128_pcm, r128s, resample_batch_pcm,
+                     resample_pcm)
 from . import legacy  # noqa: F401
 from .gui_compat import batch_process_audio, process_audio  # noqa: F401
 from .ops import (apply_eq_to_samples, apply_multiband_compressor, apply_peak_filter, apply_saturation,  # noqa: F401
@@ -58,4 +64,5 @@ __all__ = ["legacy", "EQ_PRESETS", "Job", "master_pcm", "master_device", "master
            "apply_multiband_compressor", "normalize_to_lufs", "soft_limiter", "audio_segment_to_float_array",
            "float_array_to_audio_segment", "integrated_loudness", "true_peak", "meter_pcm", "meters", "ceiling_pcm",
            "ceilings", "resample_pcm", "r128_pcm", "r128s", "level_pcm", "levels", "album_level_pcm", "album_r128_pcm",
-           "master_album", "process_album", "ceiling_batch_pcm", "level_batch_pcm", "deliver_batch", "process_batch"]
+           "master_album", "process_album", "ceiling_batch_pcm", "level_batch_pcm", "deliver_batch", "process_batch",
+           "resample_batch_pcm"]

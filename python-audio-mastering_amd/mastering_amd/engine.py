@@ -625,6 +625,52 @@ def resample_pcm(pcm: np.ndarray, rate_in: int, rate_out: int, device: int = 0):
     return out, resample_dict(m)
 
 
+def resample_batch_pcm(tracks, rate_in: int, rate_out: int, device: int = 0):
+    """Convert the tracks of a batch (int16 or float32 = int16 / 32768 arrays [N] or [N, ch], one
+    channel count and sample type) to another sample rate without mastering them
+    (mm_batch_resample_pcm: ONE converter launch covers all tracks).  Every track receives what
+    resample_pcm gives on it alone, samples and statistics; a track without frames is valid.
+    Returns (new arrays, [resample_dict ...]).  ValueError for a rate pair outside the
+    converter's limits (design.resample_geometry)."""
+    xs, kind, ch, frames = _album_tracks(tracks, "a batch")
+    n = len(xs)
+    rs = Resampler(rate_in, rate_out)
+    outs = [np.empty((rs.frames_out(x.shape[0]),) + x.shape[1:], x.dtype) for x in xs]
+    ctx = native.context(device)
+    ms = (native.MMResample * n)()
+    ctx.check(ctx.lib.mm_batch_resample_pcm(ctx.ptr, _pointers([x.ctypes.data for x in xs]), kind, frames, n, ch,
+                                            ctypes.byref(rs.rs), _pointers([o.ctypes.data for o in outs]), ms),
+              "mm_batch_resample_pcm")
+    return outs, [resample_dict(m) for m in ms]
+
+
+def _batch_resampler(jobs, output_rate, d_mids, what: str):
+    """The converter of a batch or album call (`what`) whose jobs share one rate: None when
+    `output_rate` is None or that rate (the call is then exactly the call without it, and
+    `d_mids` is not looked at), else the Resampler.  ValueError, before any device work, for an
+    `output_rate` without one `d_mids` buffer per job or a rate pair outside the converter's
+    limits (design.resample_geometry)."""
+    if output_rate is None or int(output_rate) == jobs[0].rate:
+        return None
+    if d_mids is None:
+        raise ValueError(f"{what} at another rate (output_rate) is mastered into d_mids: one caller-owned buffer of "
+                         "frames_proc frames per job")
+    if len(d_mids) != len(jobs):
+        raise ValueError(f"d_mids: {len(d_mids)} buffers for {len(jobs)} jobs")
+    return Resampler(jobs[0].rate, int(output_rate))
+
+
+def _batch_convert(ctx: native.Context, jobs, rs: Resampler, d_mids, d_outs, kind: int, ch: int):
+    """All mastered tracks from `d_mids` into `d_outs` at the converter's rate_out in one
+    mm_batch_resample_device call: (the delivered frames as a c_int64 array, [resample_dict ...])."""
+    n = len(jobs)
+    frames = (ctypes.c_int64 * n)(*[j.frames_proc for j in jobs])
+    ms = (native.MMResample * n)()
+    ctx.check(ctx.lib.mm_batch_resample_device(ctx.ptr, _pointers(d_mids), kind, frames, n, ch, ctypes.byref(rs.rs),
+                                               _pointers(d_outs), ms), "mm_batch_resample_device")
+    return (ctypes.c_int64 * n)(*[int(m.frames_out) for m in ms]), [resample_dict(m) for m in ms]
+
+
 def ceiling_pcm(pcm: np.ndarray, rate: int, ceiling_dbtp: float, window: int | None = None, device: int = 0):
     """Hold an int16 (or float32 = int16 / 32768) array [N] or [N, ch] under a true-peak
     ceiling without mastering it (mm_ceiling_pcm): returns (a new array, ceiling_dict).
@@ -730,7 +776,10 @@ def master_batch(ctx: native.Context, jobs, d_ins, d_outs, with_results: bool = 
     Returns one MMResult per job (or None).  Jobs planned with `report=True` are
     metered: `meters(ctx, len(jobs))` holds one mm_meter per job, in job order; jobs
     planned with `ceiling_dbtp` are held under it: `ceilings(ctx, len(jobs))`; jobs planned
-    with `r128=True` get their R 128 report: `r128s(ctx, len(jobs))`."""
+    with `r128=True` get their R 128 report: `r128s(ctx, len(jobs))`.  A job planned with
+    `output_rate` or `deliver_lufs` is refused here: a batch is delivered at another rate by
+    deliver_batch / master_album (their `output_rate` keyword, not a job's plan), which master
+    with this call and convert all tracks afterwards."""
     n = len(jobs)
     if any(j.delivery is not None and j.delivery.level_clu for j in jobs):
         raise ValueError("a loudness target (deliver_lufs) re-measures one delivered track pass by pass: "
@@ -745,7 +794,8 @@ def master_batch(ctx: native.Context, jobs, d_ins, d_outs, with_results: bool = 
     return list(res) if with_results else None
 
 
-def master_album(ctx: native.Context, jobs, d_ins, d_outs, deliver_lufs: float, ceiling_dbtp: float | None = None):
+def master_album(ctx: native.Context, jobs, d_ins, d_outs, deliver_lufs: float, ceiling_dbtp: float | None = None,
+                 output_rate: int | None = None, d_mids=None):
     """Master the tracks of an album as a batch (master_batch) and level the album in place on
     `d_outs` (mm_album_level_device): one static gain for all tracks to `deliver_lufs` (the
     album's EBU R 128 integrated loudness), every track under `ceiling_dbtp`.  The jobs are
@@ -753,7 +803,17 @@ def master_album(ctx: native.Context, jobs, d_ins, d_outs, deliver_lufs: float, 
     context's per-call results, so a batch's meters would be lost without a word) and share
     one rate, channel count and output kind: anything else is a ValueError before anything runs.  Returns (the batch's results,
     album dict as album_level_pcm's); `r128s(ctx)` / `ceilings(ctx)` then hold the per-track
-    reports of the levelled tracks, as after a batch."""
+    reports of the levelled tracks, as after a batch.
+    `output_rate` other than the jobs' rate delivers the album at that rate: the batch is
+    mastered into `d_mids` (caller-owned device buffers, one per job, of frames_proc frames), all
+    tracks are converted in ONE mm_batch_resample_device call into `d_outs`
+    (Resampler.frames_out(frames_proc) frames each), and the album level runs on `d_outs` with the
+    K-weighting and the ceiling window of `output_rate`; the album dict gains "resample", one
+    resample_dict per track.  It is a keyword of this call on purpose: jobs planned with
+    `output_rate` and params['output_rate'] stay refused, here and by master_batch.  None or the
+    jobs' rate: the call is exactly the call without it.  An `output_rate` without `d_mids` (or
+    with another count of them), or a rate pair design.resample_geometry refuses, is a
+    ValueError before any device work."""
     jobs = list(jobs)
     if not 1 <= len(jobs) <= native.ALBUM_TRACKS:
         raise ValueError(f"an album has 1 to {native.ALBUM_TRACKS} tracks, not {len(jobs)}")
@@ -774,22 +834,53 @@ def master_album(ctx: native.Context, jobs, d_ins, d_outs, deliver_lufs: float, 
     rate, ch, kind = jobs[0].rate, jobs[0].channels, int(jobs[0].job.out_kind)
     clu = design.level_clu(deliver_lufs)
     C = 0 if ceiling_dbtp is None else design.ceiling_q28(ceiling_dbtp)
-    res = master_batch(ctx, jobs, d_ins, d_outs)
-    frames = (ctypes.c_int64 * len(jobs))(*[j.frames_proc for j in jobs])
+    rs = _batch_resampler(jobs, output_rate, d_mids, "an album")
+    res = master_batch(ctx, jobs, d_ins, d_outs if rs is None else d_mids)
+    frames, converted = (ctypes.c_int64 * len(jobs))(*[j.frames_proc for j in jobs]), None
+    if rs is not None:
+        frames, converted = _batch_convert(ctx, jobs, rs, d_mids, d_outs, kind, ch)
+        rate = int(output_rate)
     ctx.check(ctx.lib.mm_album_level_device(ctx.ptr, _pointers(d_outs), kind, frames, len(jobs), ch, rate,
                                             kweight_sos(rate), clu, C, design.ceiling_window(rate)),
               "mm_album_level_device")
-    return res, _album_dict(ctx, len(jobs), bool(C))
+    album = _album_dict(ctx, len(jobs), bool(C))
+    if converted is not None:
+        album["resample"] = converted
+    return res, album
 
 
-def process_album(input_paths, output_paths, params: dict, device: int = 0):
+def _batch_buffers(jobs, xs, kind: int, device: int, rs: "Resampler | None"):
+    """The device buffers of a batch of files (torch: plumbing only): (inputs, mids or None,
+    outputs).  With a converter the mids hold frames_proc frames and the outputs
+    rs.frames_out(frames_proc); without one there are no mids."""
+    import torch
+    dev = torch.device("cuda", device)
+    dtype = torch.int16 if kind == native.MM_OUT_I16 else torch.float32
+    d_ins = [torch.from_numpy(x).to(dev) for x in xs]
+    d_procs = [torch.empty((j.frames_proc, j.channels), dtype=dtype, device=dev) for j in jobs]
+    d_outs = d_procs if rs is None else [torch.empty((rs.frames_out(j.frames_proc), j.channels), dtype=dtype, device=dev)
+                                         for j in jobs]
+    torch.cuda.synchronize(dev)
+    return d_ins, None if rs is None else d_procs, d_outs
+
+
+def _pointers_of(tensors):
+    return None if tensors is None else [t.data_ptr() for t in tensors]
+
+
+def process_album(input_paths, output_paths, params: dict, device: int = 0, output_rate: int | None = None):
     """Master the WAV files of an album with the same `params` and level them as one album
     (master_album): params['deliver_lufs'] (required) is the album's target, params['ceiling_dbtp']
     (optional) the true-peak ceiling of every track; params['output_format']='f32' writes
     float.  The files share one rate and channel count.  Returns (one info dict a file, album
     dict).  params['output_rate'] is refused: delivery at another rate is not available for a
-    batch; params['report'] and params['r128'] are refused too: the album dict carries every
-    levelled file's R 128 report and ceiling."""
+    batch through the params; params['report'] and params['r128'] are refused too: the album
+    dict carries every levelled file's R 128 report and ceiling.
+    The keyword `output_rate` (not a params key, on purpose: the params key stays refused)
+    other than the files' rate delivers the album at that rate (master_album's `output_rate`):
+    the files are written with that rate in their headers and every info dict gains "frames",
+    "rate" and "resample" as process's does; None or the files' rate: exactly the call without
+    it.  ValueError for a rate pair design.resample_geometry refuses, before any device work."""
     from . import wavio
     params = dict(params or {})
     if params.get("deliver_lufs") is None:
@@ -817,23 +908,24 @@ def process_album(input_paths, output_paths, params: dict, device: int = 0):
         x, job.job.in_kind = _device_input(pcm, wide=True)
         jobs.append(job)
         xs.append(x)
-    import torch  # (plumbing only: the device buffers of the batch)
+    rs = Resampler(rates[0], int(output_rate)) if jobs and output_rate is not None and int(output_rate) != rates[0] else None
     ctx = native.context(device)
-    dev = torch.device("cuda", device)
-    d_ins = [torch.from_numpy(x).to(dev) for x in xs]
-    d_outs = [torch.empty((j.frames_proc, j.channels), dtype=torch.int16 if kind == native.MM_OUT_I16 else torch.float32,
-                          device=dev) for j in jobs]
-    torch.cuda.synchronize(dev)
-    res, album = master_album(ctx, jobs, [t.data_ptr() for t in d_ins], [t.data_ptr() for t in d_outs], deliver_lufs, ceiling)
+    d_ins, d_mids, d_outs = _batch_buffers(jobs, xs, kind, device, rs)
+    res, album = master_album(ctx, jobs, _pointers_of(d_ins), _pointers_of(d_outs), deliver_lufs, ceiling,
+                              None if rs is None else int(output_rate), _pointers_of(d_mids))
     infos = []
-    for job, r, out, path in zip(jobs, res, d_outs, output_paths):
+    for t, (job, r, out, path) in enumerate(zip(jobs, res, d_outs, output_paths)):
         y = out.cpu().numpy()
-        wavio.write_wav(path, y[:, 0] if job.channels == 1 else y, job.rate)
-        infos.append(dict(_info(job, r), output_path=os.path.abspath(path)))
+        wavio.write_wav(path, y[:, 0] if job.channels == 1 else y, job.rate if rs is None else int(output_rate))
+        info = dict(_info(job, r), output_path=os.path.abspath(path))
+        if rs is not None:
+            info["frames"], info["rate"], info["resample"] = y.shape[0], int(output_rate), album["resample"][t]
+        infos.append(info)
     return infos, album
 
 
-def deliver_batch(ctx: native.Context, jobs, d_ins, d_outs, deliver_lufs, ceiling_dbtp=None):
+def deliver_batch(ctx: native.Context, jobs, d_ins, d_outs, deliver_lufs, ceiling_dbtp=None,
+                  output_rate: int | None = None, d_mids=None):
     """Master the tracks of a batch (master_batch) and level every track in place on `d_outs` to
     its own target (mm_batch_level_device): `deliver_lufs` and `ceiling_dbtp` are each a scalar
     or one value per job (a ceiling of None: none for that job).  The jobs are planned without
@@ -841,7 +933,17 @@ def deliver_batch(ctx: native.Context, jobs, d_ins, d_outs, deliver_lufs, ceilin
     results, so a batch's meters would be lost without a word) and share one rate, channel count
     and output kind: anything else is a ValueError before anything runs.  Returns (the batch's
     results, [level_dict ...] as level_batch_pcm's); `levels(ctx)` / `r128s(ctx)` / `ceilings(ctx)`
-    then hold the per-track results of the levelled tracks, as after a batch."""
+    then hold the per-track results of the levelled tracks, as after a batch.
+    `output_rate` other than the jobs' rate delivers the batch at that rate: the batch is
+    mastered into `d_mids` (caller-owned device buffers, one per job, of frames_proc frames), all
+    tracks are converted in ONE mm_batch_resample_device call into `d_outs`
+    (Resampler.frames_out(frames_proc) frames each), and the batch level runs on `d_outs` with the
+    K-weighting and the ceiling window of `output_rate`; every level dict gains "resample"
+    (resample_dict).  It is a keyword of this call on purpose: jobs planned with `output_rate`
+    and params['output_rate'] stay refused, here and by master_batch.  None or the jobs' rate:
+    the call is exactly the call without it.  An `output_rate` without `d_mids` (or with another
+    count of them), or a rate pair design.resample_geometry refuses, is a ValueError before any
+    device work."""
     jobs = list(jobs)
     if not 1 <= len(jobs) <= native.ALBUM_TRACKS:
         raise ValueError(f"a batch to deliver has 1 to {native.ALBUM_TRACKS} tracks, not {len(jobs)}")
@@ -861,22 +963,35 @@ def deliver_batch(ctx: native.Context, jobs, d_ins, d_outs, deliver_lufs, ceilin
         raise ValueError("the tracks of a batch to deliver must have one output kind")
     n, rate, ch, kind = len(jobs), jobs[0].rate, jobs[0].channels, int(jobs[0].job.out_kind)
     clu, C = _batch_targets(n, deliver_lufs, ceiling_dbtp, "deliver_lufs")
-    res = master_batch(ctx, jobs, d_ins, d_outs)
-    frames = (ctypes.c_int64 * n)(*[j.frames_proc for j in jobs])
+    rs = _batch_resampler(jobs, output_rate, d_mids, "a batch to deliver")
+    res = master_batch(ctx, jobs, d_ins, d_outs if rs is None else d_mids)
+    frames, converted = (ctypes.c_int64 * n)(*[j.frames_proc for j in jobs]), None
+    if rs is not None:
+        frames, converted = _batch_convert(ctx, jobs, rs, d_mids, d_outs, kind, ch)
+        rate = int(output_rate)
     ctx.check(ctx.lib.mm_batch_level_device(ctx.ptr, _pointers(d_outs), kind, frames, n, ch, rate, kweight_sos(rate), clu, C,
                                             design.ceiling_window(rate)), "mm_batch_level_device")
-    return res, _batch_dicts(ctx, list(C))
+    lvs = _batch_dicts(ctx, list(C))
+    if converted is not None:
+        for d, r in zip(lvs, converted):
+            d["resample"] = r
+    return res, lvs
 
 
-def process_batch(input_paths, output_paths, params: dict, device: int = 0):
+def process_batch(input_paths, output_paths, params: dict, device: int = 0, output_rate: int | None = None):
     """Master the WAV files of a batch with the same `params` and deliver every file to its own
     loudness target (deliver_batch): params['deliver_lufs'] (required) is a scalar or one value
     per file, params['ceiling_dbtp'] (optional) likewise; params['output_format']='f32' writes
     float.  The files share one rate and channel count.  Returns one info dict a file, with the
     file's level_dict under "level" (and in it "r128" and, with a ceiling, "ceiling").
-    params['output_rate'] is refused: delivery at another rate is not available for a batch;
-    params['report'] and params['r128'] are refused too: the level dict carries every delivered
-    file's R 128 report and ceiling."""
+    params['output_rate'] is refused: delivery at another rate is not available for a batch
+    through the params; params['report'] and params['r128'] are refused too: the level dict
+    carries every delivered file's R 128 report and ceiling.
+    The keyword `output_rate` (not a params key, on purpose: the params key stays refused)
+    other than the files' rate delivers every file at that rate (deliver_batch's `output_rate`):
+    the files are written with that rate in their headers and every info dict gains "frames",
+    "rate" and "resample" as process's does; None or the files' rate: exactly the call without
+    it.  ValueError for a rate pair design.resample_geometry refuses, before any device work."""
     from . import wavio
     params = dict(params or {})
     if params.get("deliver_lufs") is None:
@@ -909,19 +1024,19 @@ def process_batch(input_paths, output_paths, params: dict, device: int = 0):
         raise ValueError("the tracks of a batch to deliver must have one channel count")
     if not 1 <= len(jobs) <= native.ALBUM_TRACKS:
         raise ValueError(f"a batch to deliver has 1 to {native.ALBUM_TRACKS} tracks, not {len(jobs)}")
-    import torch  # (plumbing only: the device buffers of the batch)
+    rs = Resampler(rates[0], int(output_rate)) if output_rate is not None and int(output_rate) != rates[0] else None
     ctx = native.context(device)
-    dev = torch.device("cuda", device)
-    d_ins = [torch.from_numpy(x).to(dev) for x in xs]
-    d_outs = [torch.empty((j.frames_proc, j.channels), dtype=torch.int16 if kind == native.MM_OUT_I16 else torch.float32,
-                          device=dev) for j in jobs]
-    torch.cuda.synchronize(dev)
-    res, lvs = deliver_batch(ctx, jobs, [t.data_ptr() for t in d_ins], [t.data_ptr() for t in d_outs], deliver_lufs, ceiling)
+    d_ins, d_mids, d_outs = _batch_buffers(jobs, xs, kind, device, rs)
+    res, lvs = deliver_batch(ctx, jobs, _pointers_of(d_ins), _pointers_of(d_outs), deliver_lufs, ceiling,
+                             None if rs is None else int(output_rate), _pointers_of(d_mids))
     infos = []
     for job, r, lv, out, path in zip(jobs, res, lvs, d_outs, output_paths):
         y = out.cpu().numpy()
-        wavio.write_wav(path, y[:, 0] if job.channels == 1 else y, job.rate)
-        infos.append(dict(_info(job, r), level=lv, output_path=os.path.abspath(path)))
+        wavio.write_wav(path, y[:, 0] if job.channels == 1 else y, job.rate if rs is None else int(output_rate))
+        info = dict(_info(job, r), level=lv, output_path=os.path.abspath(path))
+        if rs is not None:
+            info["frames"], info["rate"], info["resample"] = y.shape[0], int(output_rate), lv["resample"]
+        infos.append(info)
     return infos
 
 

@@ -163,7 +163,8 @@ EXPORTS = ("mm_create", "mm_destroy", "mm_last_error", "mm_sync", "mm_version", 
            "mm_level_device", "mm_level_pcm", "mm_level_host", "mm_op_level_gain", "mm_last_levels", "mm_level_span",
            "mm_r128_album_from_hops", "mm_album_level_host", "mm_album_r128_device", "mm_album_r128_pcm",
            "mm_op_r128_album_hops", "mm_album_level_device", "mm_album_level_pcm", "mm_last_album",
-           "mm_batch_ceiling_device", "mm_batch_ceiling_pcm", "mm_batch_level_device", "mm_batch_level_pcm")
+           "mm_batch_ceiling_device", "mm_batch_ceiling_pcm", "mm_batch_level_device", "mm_batch_level_pcm",
+           "mm_batch_resample_device", "mm_batch_resample_pcm")
 
 _lib = None
 _lock = threading.Lock()
@@ -321,6 +322,10 @@ def load():
                                        c_sos_p, c_int32_p, c_int32_p, ctypes.c_int32], ctypes.c_int),
             "mm_batch_level_pcm": ([vp, P(vp), ctypes.c_int, c_int64_p, ctypes.c_int, ctypes.c_int, ctypes.c_int32,
                                     c_sos_p, c_int32_p, c_int32_p, ctypes.c_int32], ctypes.c_int),
+            "mm_batch_resample_device": ([vp, P(vp), ctypes.c_int, c_int64_p, ctypes.c_int, ctypes.c_int, P(MMResampler),
+                                          P(vp), P(MMResample)], ctypes.c_int),
+            "mm_batch_resample_pcm": ([vp, P(vp), ctypes.c_int, c_int64_p, ctypes.c_int, ctypes.c_int, P(MMResampler),
+                                       P(vp), P(MMResample)], ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             fn = getattr(lib, name)

@@ -1,0 +1,148 @@
+"""DESIGN 4m's measurements of the converter over a batch (needs the GPU).
+Usage: python tools/study/batch_resample_study.py MODE [PACKAGE_DIR]
+  single  mm_resample_device on one 96 kHz 3 min stereo track -> 44.1 kHz: wall and kernel time
+          (PACKAGE_DIR: another tree's python-audio-mastering_amd, to alternate with a parent build)
+  a       16 tracks x 3 min: one mm_batch_resample_device call against 16 mm_resample_device calls
+  b       256 tracks x 5 s of the same
+  c       deliver_batch(output_rate=44100) to -14 LUFS / -1 dBTP on (a)'s batch against 16
+          mm_deliver_device calls with the same delivery
+a and b assert that outputs and statistics are byte-equal; the two paths are timed alternately in
+one process (wall: a host clock around the synchronous calls; kernel: mm_timing's events in rounds
+of their own).  Prints one JSON line."""
+import ctypes
+import json
+import os
+import statistics
+import sys
+import time
+
+mode = sys.argv[1]
+pkg = sys.argv[2] if len(sys.argv) > 2 else os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..",
+                                                    "python-audio-mastering_amd")
+sys.path.insert(0, pkg)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from mastering_amd import engine, native  # noqa: E402
+from mastering_amd.synth import pink_noise_pcm16  # noqa: E402
+
+RATE, OUT = 96000, 44100
+ctx = native.context(0)
+rs = engine.Resampler(RATE, OUT)
+
+
+def med(xs):
+    return dict(median=round(statistics.median(xs), 4), min=round(min(xs), 4), max=round(max(xs), 4), n=len(xs))
+
+
+def single_call(d_in, frames, d_out, m):
+    ctx.check(ctx.lib.mm_resample_device(ctx.ptr, ctypes.c_void_p(d_in), native.MM_OUT_I16, frames, 2, ctypes.byref(rs.rs),
+                                         ctypes.c_void_p(d_out), ctypes.byref(m)), "mm_resample_device")
+
+
+def timed(fn, reps):
+    wall = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        wall.append((time.perf_counter() - t0) * 1e3)
+    return wall
+
+
+def kernel_ms(fn, name):
+    ctx.timing(False)
+    ctx.timing(True)
+    fn()
+    st = ctx.kernel_stats()
+    ctx.timing(False)
+    return st[name][0], st[name][1]
+
+
+def tracks(n, seconds):
+    base = pink_noise_pcm16(seconds * RATE, RATE, 2, track=40, level_dbfs=-14.0)
+    out = []
+    for t in range(n):
+        g = 10 ** (-(t % 5) / 20.0)
+        out.append(np.ascontiguousarray(np.roll((base * g).astype(np.int16), 997 * t, axis=0)))
+    return out
+
+
+if mode == "single":
+    x = tracks(1, 180)[0]
+    d = torch.from_numpy(x).cuda()
+    o = torch.empty((rs.frames_out(len(x)), 2), dtype=torch.int16, device="cuda")
+    torch.cuda.synchronize()
+    m = native.MMResample()
+    call = lambda: single_call(d.data_ptr(), len(x), o.data_ptr(), m)  # noqa: E731
+    timed(call, 3)
+    wall = timed(call, 15)
+    ks = [kernel_ms(call, "resample")[0] for _ in range(10)]
+    print(json.dumps(dict(mode=mode, pkg=pkg, sha=native.library_sha(), wall_ms=med(wall), kernel_ms=med(ks),
+                          checksum=int(o.to(torch.int64).sum().item()))))
+
+elif mode in ("a", "b"):
+    n, seconds = (16, 180) if mode == "a" else (256, 5)
+    xs = tracks(n, seconds)
+    ds = [torch.from_numpy(x).cuda() for x in xs]
+    o1 = [torch.zeros((rs.frames_out(len(x)), 2), dtype=torch.int16, device="cuda") for x in xs]
+    o2 = [torch.zeros((rs.frames_out(len(x)), 2), dtype=torch.int16, device="cuda") for x in xs]
+    torch.cuda.synchronize()
+    frames = (ctypes.c_int64 * n)(*[len(x) for x in xs])
+    ms = (native.MMResample * n)()
+    m1 = [native.MMResample() for _ in range(n)]
+    pin, pout = engine._pointers([d.data_ptr() for d in ds]), engine._pointers([o.data_ptr() for o in o2])
+
+    def batch():
+        ctx.check(ctx.lib.mm_batch_resample_device(ctx.ptr, pin, native.MM_OUT_I16, frames, n, 2, ctypes.byref(rs.rs), pout, ms),
+                  "mm_batch_resample_device")
+
+    def singles():
+        for t in range(n):
+            single_call(ds[t].data_ptr(), len(xs[t]), o1[t].data_ptr(), m1[t])
+
+    batch(), singles()
+    for t in range(n):
+        assert torch.equal(o1[t], o2[t]), t
+        assert bytes(m1[t]) == bytes(ms[t]), t
+    rounds = dict(batch_wall=[], singles_wall=[], batch_kernel=[], singles_kernel=[])
+    for _ in range(5):  # alternately
+        rounds["batch_wall"] += timed(batch, 1)
+        rounds["singles_wall"] += timed(singles, 1)
+        rounds["batch_kernel"].append(kernel_ms(batch, "resample_tracks")[0])
+        rounds["singles_kernel"].append(kernel_ms(singles, "resample")[0])
+    print(json.dumps(dict(mode=mode, n=n, seconds=seconds, byte_equal=True, **{k: med(v) for k, v in rounds.items()})))
+
+elif mode == "c":
+    n, seconds = 16, 180
+    P = {"bass_boost": 4.0, "mid_cut": 3.0, "presence_boost": 1.0, "treble_boost": 3.0, "saturation": 30, "width": 1.3,
+         "multiband": True, "lufs": -14.0}
+    xs = tracks(n, seconds)
+    ds = [torch.from_numpy(x).cuda() for x in xs]
+    jobs = [engine.Job(len(x), RATE, 2, P) for x in xs]
+    djobs = [engine.Job(len(x), RATE, 2, P, output_rate=OUT, deliver_lufs=-14.0, ceiling_dbtp=-1.0) for x in xs]
+    for j in jobs + djobs:
+        j.job.in_kind = native.MM_IN_I16
+    mids = [torch.zeros((j.frames_proc, 2), dtype=torch.int16, device="cuda") for j in jobs]
+    o1 = [torch.zeros((rs.frames_out(j.frames_proc), 2), dtype=torch.int16, device="cuda") for j in jobs]
+    o2 = [torch.zeros((rs.frames_out(j.frames_proc), 2), dtype=torch.int16, device="cuda") for j in jobs]
+    torch.cuda.synchronize()
+    ins = [d.data_ptr() for d in ds]
+
+    def batch():
+        return engine.deliver_batch(ctx, jobs, ins, [o.data_ptr() for o in o2], -14.0, -1.0, OUT, [m.data_ptr() for m in mids])
+
+    def singles():
+        for t in range(n):
+            engine.master_device(ctx, djobs[t], ins[t], o1[t].data_ptr(), native.MMResult())
+
+    lv = batch()[1]
+    singles()
+    differ = [int((o1[t] != o2[t]).sum().item()) for t in range(n)]
+    rounds = dict(batch_wall=[], singles_wall=[])
+    for _ in range(3):
+        rounds["batch_wall"] += timed(batch, 1)
+        rounds["singles_wall"] += timed(singles, 1)
+    print(json.dumps(dict(mode=mode, n=n, seconds=seconds, differing_samples=differ,
+                          loudness=[round(d["loudness"], 3) for d in lv], status=[d["status"] for d in lv],
+                          **{k: med(v) for k, v in rounds.items()})))
