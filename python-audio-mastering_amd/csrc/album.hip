@@ -3,9 +3,10 @@
 // (the album R 128 figures and the album level in include/mastering.h).  Loudness differences
 // between the tracks are kept.  No reference counterpart.
 //
-// Nothing is decided here that level.hip does not decide: level_first / level_next run on
-// the album's integrated loudness, the gain is level_gain's and the ceiling ceiling_device's,
-// one call a track.  What is new is the measuring pass: r128.hip's album kernels K-weight
+// Nothing is decided here that level.hip does not decide: level_first, level_step and
+// level_record run on the album's integrated loudness and the tracks' ceilings, the kept
+// sources are level_keep's, the gain is level_gain's (on the host level_gain_host's) and the
+// ceiling ceiling_device's, one call a track.  What is new is the measuring pass: r128.hip's album kernels K-weight
 // every track in ONE launch and reduce all hops in one more, with one read-back of the
 // album's hop energies and the look-back's error word, where n calls of r128_hops pay n
 // synchronisations a pass.  The album's figures come from the pooled windows of the tracks
@@ -185,14 +186,6 @@ int album_level_device(mm_ctx *c, void *const *d_pcm, int kind, const int64_t *f
         album_reports(e, pass, frames, &album, tr);
         return MM_OK;
     };
-    auto limited = [&](const std::vector<mm_ceiling> &ce) {  // sums and the minimum over the tracks
-        out.limited_frames = 0;
-        out.min_gain_q16 = LEVEL_ONE;
-        for (const mm_ceiling &m : ce) {
-            out.limited_frames += m.limited_frames;
-            out.min_gain_q16 = std::min(out.min_gain_q16, m.min_gain_q16);
-        }
-    };
     auto done = [&]() {
         c->r128s = tr;
         if (C) c->ceilings = ceil;
@@ -200,34 +193,22 @@ int album_level_device(mm_ctx *c, void *const *d_pcm, int kind, const int64_t *f
         c->album_r128s.assign(1, album);
         return MM_OK;
     };
+    const int nc = C ? n : 0;  // ceilings a pass
     RET(measure());
     out.source_lufs = album.integrated;
     if (!std::isfinite(album.integrated)) {  // no window, or silence: every track only gets its ceiling
-        out.status = MM_LEVEL_UNMEASURABLE;
-        if (C) {
-            for (int t = 0; t < n; ++t) RET(ceiling_device(c, d_pcm[t], kind, frames[t], channels, C, W, &ceil[(size_t)t]));
-            limited(ceil);
-            RET(measure());  // the reports describe what is delivered
-        }
+        for (int t = 0; t < nc; ++t) RET(ceiling_device(c, d_pcm[t], kind, frames[t], channels, C, W, &ceil[(size_t)t]));
+        level_unmeasurable(&out, ceil.data(), nc);
+        if (C) RET(measure());  // the reports describe what is delivered
         return done();
     }
-    // the sources, kept in one buffer, each at its delivered buffer's offset within 16 bytes
-    std::vector<char *> src((size_t)n);
+    std::vector<char *> src;
     std::vector<size_t> bytes((size_t)n);
-    size_t keep_bytes = 0;
-    for (int t = 0; t < n; ++t) {
-        bytes[(size_t)t] = pcm_bytes(kind, frames[t], channels);
-        keep_bytes += ((bytes[(size_t)t] + 15) & ~(size_t)15) + 16;
-    }
-    char *keep;
+    for (int t = 0; t < n; ++t) bytes[(size_t)t] = pcm_bytes(kind, frames[t], channels);
     LevelDev *st;
     std::vector<LevelDev> hs((size_t)n);
-    RET(get_buf(c, "album_src", keep_bytes, &keep));
+    RET(level_keep(c, "album_src", d_pcm, kind, frames, n, channels, src));
     RET(get_buf(c, "album_res", (size_t)n, &st));
-    for (int t = 0; t < n; ++t) {
-        src[(size_t)t] = keep + ((uintptr_t)d_pcm[t] & 15);
-        keep += ((bytes[(size_t)t] + 15) & ~(size_t)15) + 16;
-    }
     auto results = [&]() -> int {  // every slot of the pass, behind the next synchronisation
         HIPCHK(c, hipMemcpyAsync(hs.data(), st, (size_t)n * sizeof(LevelDev), hipMemcpyDeviceToHost, c->stream));
         return MM_OK;
@@ -247,38 +228,24 @@ int album_level_device(mm_ctx *c, void *const *d_pcm, int kind, const int64_t *f
     }
     int32_t g = level_first(&out);
     while (g) {
-        bool capped = false, boost = false;
-        if (!C) {
-            if (g > g_peak) g = g_peak, capped = true;
-        } else if (g > LEVEL_ONE) {  // the limiter before the boost, so that the boost cannot clip first
-            const int32_t g_cap = level_boost_cap(C);
-            if (g > g_cap) g = g_cap, capped = true;
-            boost = true;
-        }
+        const LevelStep s = level_step(C, g, g_peak);
         HIPCHK(c, hipMemsetAsync(st, 0, (size_t)n * sizeof(LevelDev), c->stream));
         for (int t = 0; t < n; ++t) {
             const int64_t ns = frames[t] * channels;
-            if (!boost) {
-                RET(level_gain_queue(c, src[(size_t)t], d_pcm[t], kind, ns, g, st + t));
+            if (!s.boost) {
+                RET(level_gain_queue(c, src[(size_t)t], d_pcm[t], kind, ns, s.g, st + t));
                 continue;
             }
             if (bytes[(size_t)t]) HIPCHK(c, hipMemcpyAsync(d_pcm[t], src[(size_t)t], bytes[(size_t)t], hipMemcpyDeviceToDevice, c->stream));
-            RET(ceiling_device(c, d_pcm[t], kind, frames[t], channels, level_inner_ceiling(C, g), W, &ce_in[(size_t)t]));
-            RET(level_gain_queue(c, d_pcm[t], d_pcm[t], kind, ns, g, st + t));
+            RET(ceiling_device(c, d_pcm[t], kind, frames[t], channels, s.C_inner, W, &ce_in[(size_t)t]));
+            RET(level_gain_queue(c, d_pcm[t], d_pcm[t], kind, ns, s.g, st + t));
         }
         RET(results());
-        if (C) {
-            for (int t = 0; t < n; ++t) RET(ceiling_device(c, d_pcm[t], kind, frames[t], channels, C, W, &ceil[(size_t)t]));
-            if (!boost) ce_in = ceil;
-        }
+        for (int t = 0; t < nc; ++t) RET(ceiling_device(c, d_pcm[t], kind, frames[t], channels, C, W, &ceil[(size_t)t]));
         RET(measure());
-        const int k = out.passes++;
-        out.pass_gain_q16[k] = g;
-        out.pass_lufs[k] = album.integrated;
-        out.clipped = 0;
-        for (const LevelDev &h : hs) out.clipped += (int64_t)h.clipped;
-        if (C) limited(ce_in);
-        g = level_next(&out, capped);
+        int64_t clipped = 0;
+        for (const LevelDev &h : hs) clipped += (int64_t)h.clipped;
+        g = level_record(&out, s, album.integrated, clipped, ceil.data(), ce_in.data(), nc);
     }
     return done();
 }
@@ -297,6 +264,17 @@ int album_upload(mm_ctx *c, const char *name, const void *const *pcm, int kind, 
         if (bytes && pcm) HIPCHK(c, hipMemcpyAsync(base, pcm[t], bytes, hipMemcpyHostToDevice, c->stream));
         base += (bytes + 15) & ~(size_t)15;
     }
+    return MM_OK;
+}
+
+// d[t] back into pcm[t] for the tracks `pick` names (null: all), synchronous
+int batch_download(mm_ctx *c, void *const *pcm, const std::vector<void *> &d, int kind, const int64_t *frames, int n,
+                   int channels, const char *pick) {
+    for (int t = 0; t < n; ++t) {
+        const size_t bytes = pcm_bytes(kind, frames[t], channels);
+        if (bytes && (!pick || pick[t])) HIPCHK(c, hipMemcpyAsync(pcm[t], d[(size_t)t], bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return MM_OK;
 }
 
@@ -346,28 +324,18 @@ int mm_album_level_host(int16_t *const *pcm, const int64_t *frames, int n, int c
         album->channels = channels;
         return MM_OK;
     };
-    auto limited = [&](const std::vector<mm_ceiling> &ce) {
-        out->limited_frames = 0;
-        out->min_gain_q16 = LEVEL_ONE;
-        for (const mm_ceiling &m : ce) {
-            out->limited_frames += m.limited_frames;
-            out->min_gain_q16 = std::min(out->min_gain_q16, m.min_gain_q16);
-        }
-    };
     auto done = [&]() {
         if (C && track_ceil)
             for (int t = 0; t < n; ++t) track_ceil[t] = ceil[(size_t)t];
         return MM_OK;
     };
+    const int nc = C ? n : 0;  // ceilings a pass
     RET(measure());
     out->source_lufs = album->integrated;
     if (!std::isfinite(album->integrated)) {
-        out->status = MM_LEVEL_UNMEASURABLE;
-        if (C) {
-            for (int t = 0; t < n; ++t) RET(mm_ceiling_host(pcm[t], frames[t], channels, C, W, &ceil[(size_t)t]));
-            limited(ceil);
-            RET(measure());
-        }
+        for (int t = 0; t < nc; ++t) RET(mm_ceiling_host(pcm[t], frames[t], channels, C, W, &ceil[(size_t)t]));
+        level_unmeasurable(out, ceil.data(), nc);
+        if (C) RET(measure());
         return done();
     }
     std::vector<std::vector<int16_t>> src((size_t)n);
@@ -377,46 +345,23 @@ int mm_album_level_host(int16_t *const *pcm, const int64_t *frames, int n, int c
         for (int16_t s : src[(size_t)t]) peak = std::max(peak, std::abs((int32_t)s));
     }
     const int32_t g_peak = level_peak_cap(peak);
-    int64_t clipped = 0;
-    auto gain = [&](const int16_t *from, int16_t *to, size_t ns, int32_t g) {  // gain(x, g) as the definition writes it
-        for (size_t i = 0; i < ns; ++i) {
-            const int64_t v = (int64_t)from[i] * g + (1 << 15);
-            const int64_t y = v >= 0 ? v >> 16 : -((-v + 65535) >> 16);  // floor(v / 2^16): the arithmetic shift
-            const int64_t d = std::min<int64_t>(32767, std::max<int64_t>(-32768, y));
-            clipped += d != y;
-            to[i] = (int16_t)d;
-        }
-    };
     int32_t g = level_first(out);
     while (g) {
-        bool capped = false, boost = false;
-        if (!C) {
-            if (g > g_peak) g = g_peak, capped = true;
-        } else if (g > LEVEL_ONE) {
-            const int32_t g_cap = level_boost_cap(C);
-            if (g > g_cap) g = g_cap, capped = true;
-            boost = true;
-        }
-        clipped = 0;
+        const LevelStep s = level_step(C, g, g_peak);
+        int64_t clipped = 0;
         for (int t = 0; t < n; ++t) {
-            const std::vector<int16_t> &s = src[(size_t)t];
-            if (boost) {
-                if (!s.empty()) memcpy(pcm[t], s.data(), s.size() * sizeof(int16_t));
-                RET(mm_ceiling_host(pcm[t], frames[t], channels, level_inner_ceiling(C, g), W, &ce_in[(size_t)t]));
-                gain(pcm[t], pcm[t], s.size(), g);
+            const std::vector<int16_t> &x = src[(size_t)t];
+            if (s.boost) {
+                if (!x.empty()) memcpy(pcm[t], x.data(), x.size() * sizeof(int16_t));
+                RET(mm_ceiling_host(pcm[t], frames[t], channels, s.C_inner, W, &ce_in[(size_t)t]));
+                level_gain_host(pcm[t], pcm[t], x.size(), s.g, clipped);
             } else {
-                gain(s.data(), pcm[t], s.size(), g);
+                level_gain_host(x.data(), pcm[t], x.size(), s.g, clipped);
             }
             if (C) RET(mm_ceiling_host(pcm[t], frames[t], channels, C, W, &ceil[(size_t)t]));
         }
-        if (C && !boost) ce_in = ceil;
         RET(measure());
-        const int k = out->passes++;
-        out->pass_gain_q16[k] = g;
-        out->pass_lufs[k] = album->integrated;
-        out->clipped = clipped;
-        if (C) limited(ce_in);
-        g = level_next(out, capped);
+        g = level_record(out, s, album->integrated, clipped, ceil.data(), ce_in.data(), nc);
     }
     return done();
 }
@@ -473,12 +418,7 @@ int mm_album_level_pcm(mm_ctx *c, void *const *pcm, int kind, const int64_t *fra
     std::vector<void *> d;
     RET(album_upload(c, "album_io", pcm, kind, frames, n, channels, d));
     RET(album_level_device(c, d.data(), kind, frames, n, channels, rate, sos, level_clu, ceiling_q28, window));
-    for (int t = 0; t < n; ++t) {
-        const size_t bytes = pcm_bytes(kind, frames[t], channels);
-        if (bytes) HIPCHK(c, hipMemcpyAsync(pcm[t], d[(size_t)t], bytes, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return MM_OK;
+    return batch_download(c, pcm, d, kind, frames, n, channels, nullptr);
 }
 
 int mm_last_album(mm_ctx *c, mm_level *level, mm_r128 *album) {

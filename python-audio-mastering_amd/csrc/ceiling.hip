@@ -284,6 +284,18 @@ const char *ceiling_bad_args(int64_t frames, int channels, int32_t C, int32_t W)
     return nullptr;
 }
 
+// what the limiter's launches found: TP0 and the statistics of `s`, and the linked true peak
+// after the limiter, which is the delivered one until a trim runs
+void ceiling_results(mm_ceiling *o, const CeilDev &s, int32_t tp_limited) {
+    o->tp_in_q28 = (int32_t)s.tp0;
+    o->tp_limited_q28 = o->tp_out_q28 = tp_limited;
+    o->min_gain_q16 = CEIL_ONE - (int32_t)s.max_red;
+    o->limited_frames = (int64_t)s.limited;
+}
+
+// the static trim of a residue tp_limited > C: provably under C (the file's head)
+int32_t ceiling_trim_gain(int32_t C, int32_t tp_limited) { return (int32_t)(((int64_t)(C - CEIL_GUARD) << 16) / tp_limited); }
+
 }  // namespace
 
 // The ceiling on a device-resident signal, in place (synchronous on return): need, apply
@@ -296,7 +308,7 @@ static int ceiling_device(mm_ctx *c, void *d_pcm, int kind, int64_t frames, int 
     ceiling_clear(out, frames, channels, C, W);
     if (frames == 0) return MM_OK;
     const int Ct = C - CEIL_GUARD;
-    const int64_t spans = (frames + 11 + METER_SPAN - 1) / METER_SPAN, plane_len = spans * METER_SPAN;
+    const int64_t plane_len = tracks_plane_len(frames);
     uint16_t *plane;
     CeilDev *st;
     MeterDev *res;
@@ -304,8 +316,8 @@ static int ceiling_device(mm_ctx *c, void *d_pcm, int kind, int64_t frames, int 
     RET(get_buf(c, "ceil_res", 1, &st));
     RET(get_buf(c, "meter_res", 1, &res));
     HIPCHK(c, hipMemsetAsync(st, 0, sizeof(CeilDev), c->stream));
-    const dim3 gn((unsigned)spans), bn(METER_THREADS);
-    const dim3 ga((unsigned)((frames + CEIL_SPAN - 1) / CEIL_SPAN)), ba(CEIL_THREADS);
+    const dim3 gn((unsigned)tracks_need_spans(frames)), bn(METER_THREADS);
+    const dim3 ga((unsigned)tracks_apply_spans(frames)), ba(CEIL_THREADS);
     const unsigned rcp = (unsigned)(((uint64_t)1 << 32) / (uint64_t)(2 * W + 1));
     RET(dispatch_pcm(kind, channels, [&](auto ch, auto t) {
         using T = decltype(t);
@@ -325,12 +337,9 @@ static int ceiling_device(mm_ctx *c, void *d_pcm, int kind, int64_t frames, int 
         for (int ch = 0; ch < channels; ++ch) tp = std::max(tp, (int32_t)(m.key[ch] >> 32));
         return tp;
     };
-    out->tp_in_q28 = (int32_t)hs.tp0;
-    out->tp_limited_q28 = out->tp_out_q28 = linked(hm);
-    out->min_gain_q16 = CEIL_ONE - (int32_t)hs.max_red;
-    out->limited_frames = (int64_t)hs.limited;
-    if (out->tp_limited_q28 > C) {  // the residue: one static trim, provably under C
-        const int gt = (int)(((int64_t)Ct << 16) / out->tp_limited_q28);
+    ceiling_results(out, hs, linked(hm));
+    if (out->tp_limited_q28 > C) {  // the residue: one static trim
+        const int gt = ceiling_trim_gain(C, out->tp_limited_q28);
         const int64_t n = frames * channels;
         RET(dispatch_pcm(kind, 1, [&](auto, auto t) {  // (pointwise: the samples as one mono line)
             using T = decltype(t);
@@ -466,7 +475,7 @@ int mm_ceiling_host(int16_t *pcm, int64_t frames, int channels, int32_t C, int32
     }
     out->tp_limited_q28 = out->tp_out_q28 = measure();
     if (out->tp_limited_q28 > C) {
-        out->trim_q16 = (int32_t)((Ct << 16) / out->tp_limited_q28);
+        out->trim_q16 = ceiling_trim_gain(C, out->tp_limited_q28);
         for (int64_t n = 0; n < N; ++n) scale(n, out->trim_q16);
         out->tp_out_q28 = measure();
     }

@@ -4,8 +4,12 @@
 // short secant search on the one number a delivery spec names: every pass forms its
 // candidate from the kept source (so rounding never accumulates), limits it with
 // ceiling.hip's ceiling_device and measures it with r128.hip's r128_device, both unchanged;
-// the decisions (level_first / level_next) are plain C++ shared with the host restatement
-// mm_level_host, which composes mm_ceiling_host and mm_r128_host the same way.
+// the rule (level_first, level_step, level_record / level_next, level_unmeasurable) is plain
+// C++ shared with the host restatement mm_level_host, which composes mm_ceiling_host and
+// mm_r128_host the same way, and with the album's and the batch's drivers (album.hip,
+// tracks.hip): a driver keeps only which launches or host calls form a pass.  The gain's
+// launch geometry (level_gain_geom) and the kept-source layout (level_keep) are here for all
+// of them too.
 //
 // One new kernel, level_gain: s' = clip((s * g + 2^15) >> 16) on the samples as one mono
 // line, src -> dst (src == dst allowed).  It is a streaming kernel (2 or 4 bytes in, as
@@ -19,8 +23,8 @@
 // the first 16-byte boundary of dst and what is left after the last whole vector are
 // single samples (lanes of workgroup 0), so any sample count and any sample-aligned view
 // is right; when src does not share dst's offset within 16 bytes, the loads alone fall back
-// to single samples (level_device keeps its source copy at the delivered buffer's offset,
-// so the chain never takes that path).  `clipped` is summed and the peak maximised over a
+// to single samples (level_keep places a source copy at the delivered buffer's offset, so
+// the chain never takes that path).  `clipped` is summed and the peak maximised over a
 // wave by shuffles and folded with at most one integer atomic a wave: no result depends on
 // the launch geometry.
 //
@@ -203,6 +207,64 @@ int32_t level_peak_cap(int32_t peak) {
     return peak > 0 ? (int32_t)std::min<int64_t>(((int64_t)32767 << 16) / peak, LEVEL_GMAX) : LEVEL_GMAX;
 }
 
+// Step 3 for the candidate g of a pass: the gain the pass runs with, whether a cap held it,
+// and for a boost behind the limiter (C != 0 and g > ONE) the inner ceiling of that gain.
+// g_peak: level_peak_cap of the source, which caps a level without a ceiling.
+struct LevelStep {
+    int32_t g, C_inner;
+    bool capped, boost;
+};
+
+LevelStep level_step(int32_t C, int32_t g, int32_t g_peak) {
+    LevelStep s{g, 0, false, C != 0 && g > LEVEL_ONE};
+    if (C && !s.boost) return s;  // a cut under a ceiling: plain gain
+    const int32_t cap = C ? level_boost_cap(C) : g_peak;
+    if (s.g > cap) s.g = cap, s.capped = true;
+    if (s.boost) s.C_inner = level_inner_ceiling(C, s.g);  // the limiter before the boost, so that the boost cannot clip first
+    return s;
+}
+
+// what the limiter did over n ceilings (one a track): the frames summed, the smallest gain
+void level_limited(mm_level *o, const mm_ceiling *ce, int n) {
+    o->limited_frames = 0;
+    o->min_gain_q16 = LEVEL_ONE;
+    for (int t = 0; t < n; ++t) {
+        o->limited_frames += ce[t].limited_frames;
+        o->min_gain_q16 = std::min(o->min_gain_q16, ce[t].min_gain_q16);
+    }
+}
+
+// The record after a pass ran with s and was measured at `lufs`, then steps 4 and 5: returns
+// level_next.  ce [n]: the pass's ceilings at C; ce_in [n]: its inner ceilings, which a boost
+// reports as the limiter's work (else the ceilings at C are the limiter).  n == 0: no ceiling.
+int32_t level_record(mm_level *o, const LevelStep &s, double lufs, int64_t clipped, const mm_ceiling *ce,
+                     const mm_ceiling *ce_in, int n) {
+    const int k = o->passes++;
+    o->pass_gain_q16[k] = s.g;
+    o->pass_lufs[k] = lufs;
+    o->clipped = clipped;
+    if (n) level_limited(o, s.boost ? ce_in : ce, n);
+    return level_next(o, s.capped);
+}
+
+// no gain to find (fewer than 4 hops, or silence): the signal only got its n ceilings
+void level_unmeasurable(mm_level *o, const mm_ceiling *ce, int n) {
+    o->status = MM_LEVEL_UNMEASURABLE;
+    if (n) level_limited(o, ce, n);
+}
+
+// gain(x, g) as the definition writes it, in int64: from -> to (from == to allowed), the
+// products outside the int16 range added to `clipped`
+void level_gain_host(const int16_t *from, int16_t *to, size_t n, int32_t g, int64_t &clipped) {
+    for (size_t i = 0; i < n; ++i) {
+        const int64_t v = (int64_t)from[i] * g + (1 << 15);
+        const int64_t y = v >= 0 ? v >> 16 : -((-v + 65535) >> 16);  // floor(v / 2^16): the arithmetic shift
+        const int64_t d = std::min<int64_t>(32767, std::max<int64_t>(-32768, y));
+        clipped += d != y;
+        to[i] = (int16_t)d;
+    }
+}
+
 // why the arguments are not a levelling job, or null (C == 0: no ceiling, W is then ignored)
 const char *level_bad_args(int64_t frames, int channels, int rate, int32_t clu, int32_t C, int32_t W) {
     if (clu < -4000 || clu > -500) return "level_clu out of range [-4000, -500] (-40 .. -5 LUFS)";
@@ -210,19 +272,49 @@ const char *level_bad_args(int64_t frames, int channels, int rate, int32_t clu, 
     return C ? ceiling_bad_args(frames, channels, C, W) : nullptr;
 }
 
+// The geometry of one gain launch of n samples: the single samples before dst's first 16-byte
+// boundary, whether src shares dst's offset within 16 bytes (whole-vector loads), and the
+// workgroups (one a LEVEL_SPAN of whole vectors, at least one; none for no samples).
+struct LevelGeom {
+    int head, src_vec;
+    int64_t wgs;
+};
+
+LevelGeom level_gain_geom(const void *src, const void *dst, int kind, int64_t n) {
+    const int64_t sb = (int64_t)pcm_sample_bytes(kind);
+    const int head = (int)std::min<int64_t>(n, (int64_t)((16 - ((uintptr_t)dst & 15)) & 15) / sb);
+    const int src_vec = ((((uintptr_t)src) ^ ((uintptr_t)dst)) & 15) == 0;
+    const int64_t nvec = (n - head) / (16 / sb), vpb = LEVEL_SPAN / (16 / sb);
+    return LevelGeom{head, src_vec, n ? std::max<int64_t>(1, (nvec + vpb - 1) / vpb) : 0};
+}
+
+// The kept sources of n tracks in the one context buffer `name`: src[t] lies at its delivered
+// buffer's offset within 16 bytes, so that a pass from it loads whole vectors.
+int level_keep(mm_ctx *c, const char *name, void *const *d_pcm, int kind, const int64_t *frames, int n, int channels,
+               std::vector<char *> &src) {
+    auto room = [&](int t) { return ((pcm_bytes(kind, frames[t], channels) + 15) & ~(size_t)15) + 16; };
+    size_t total = 0;
+    for (int t = 0; t < n; ++t) total += room(t);
+    char *keep;
+    RET(get_buf(c, name, total, &keep));
+    src.resize((size_t)n);
+    for (int t = 0; t < n; ++t) {
+        src[(size_t)t] = keep + ((uintptr_t)d_pcm[t] & 15);
+        keep += room(t);
+    }
+    return MM_OK;
+}
+
 // src -> dst by g, queued; the statistics are folded into *st, which the caller zeroed on the
 // stream (album.hip zeroes one array of them once a pass)
 int level_gain_queue(mm_ctx *c, const void *src, void *dst, int kind, int64_t n, int32_t g, LevelDev *st) {
     if (n == 0) return MM_OK;
-    const size_t sb = pcm_sample_bytes(kind);
-    const int head = (int)std::min<int64_t>(n, (int64_t)(((16 - ((uintptr_t)dst & 15)) & 15) / sb));
-    const int src_vec = ((((uintptr_t)src) ^ ((uintptr_t)dst)) & 15) == 0;
-    const int64_t nvec = (n - head) / (int64_t)(16 / sb), vpb = LEVEL_SPAN / (int64_t)(16 / sb);
-    const dim3 grid((unsigned)std::max<int64_t>(1, (nvec + vpb - 1) / vpb)), block(LEVEL_THREADS);
+    const LevelGeom geo = level_gain_geom(src, dst, kind, n);
+    const dim3 grid((unsigned)geo.wgs), block(LEVEL_THREADS);
     return dispatch_pcm(kind, 1, [&](auto, auto t) {  // (pointwise: the samples as one mono line)
         using T = decltype(t);
         return launch(c, "level_gain", level_gain_kernel<T>, grid, block, 0, static_cast<const T *>(src), static_cast<T *>(dst), n,
-                      head, src_vec, (int)g, st);
+                      geo.head, geo.src_vec, (int)g, st);
     });
 }
 
@@ -248,23 +340,19 @@ static int level_device(mm_ctx *c, void *d_pcm, int kind, int64_t frames, int ch
     mm_r128 r;
     RET(r128_device(c, d_pcm, kind, frames, channels, rate, sos, &r));
     out->source_lufs = r.integrated;
-    if (!std::isfinite(r.integrated)) {  // fewer than 4 hops, or silence: no gain to find
-        out->status = MM_LEVEL_UNMEASURABLE;
-        if (C) {
-            RET(ceiling_device(c, d_pcm, kind, frames, channels, C, W, ce));
-            out->limited_frames = ce->limited_frames;
-            out->min_gain_q16 = ce->min_gain_q16;
-        }
+    const int nc = C ? 1 : 0;  // ceilings a pass
+    if (!std::isfinite(r.integrated)) {
+        if (C) RET(ceiling_device(c, d_pcm, kind, frames, channels, C, W, ce));
+        level_unmeasurable(out, ce, nc);
         return MM_OK;
     }
-    // the source, kept at the delivered buffer's offset within 16 bytes (whole-vector loads)
     const int64_t n = frames * channels;
     const size_t bytes = pcm_bytes(kind, frames, channels);
-    char *keep;
+    std::vector<char *> kept;
     LevelDev *st, hs{};
-    RET(get_buf(c, "level_src", bytes + 16, &keep));
+    RET(level_keep(c, "level_src", &d_pcm, kind, &frames, 1, channels, kept));
     RET(get_buf(c, "level_res", 1, &st));
-    char *src = keep + ((uintptr_t)d_pcm & 15);
+    char *src = kept[0];
     int32_t g_peak = LEVEL_GMAX;
     if (C) {
         HIPCHK(c, hipMemcpyAsync(src, d_pcm, bytes, hipMemcpyDeviceToDevice, c->stream));
@@ -276,35 +364,18 @@ static int level_device(mm_ctx *c, void *d_pcm, int kind, int64_t frames, int ch
     }
     int32_t g = level_first(out);
     while (g) {
-        bool capped = false, boost = false;
-        if (!C) {
-            if (g > g_peak) g = g_peak, capped = true;
-            RET(level_gain_launch(c, src, d_pcm, kind, n, g, st));
-        } else if (g <= LEVEL_ONE) {
-            RET(level_gain_launch(c, src, d_pcm, kind, n, g, st));
-        } else {  // the limiter before the boost, so that the boost cannot clip first
-            const int32_t g_cap = level_boost_cap(C);
-            if (g > g_cap) g = g_cap, capped = true;
-            boost = true;
+        const LevelStep s = level_step(C, g, g_peak);
+        if (s.boost) {
             HIPCHK(c, hipMemcpyAsync(d_pcm, src, bytes, hipMemcpyDeviceToDevice, c->stream));
-            RET(ceiling_device(c, d_pcm, kind, frames, channels, level_inner_ceiling(C, g), W, &ce_in));
-            RET(level_gain_launch(c, d_pcm, d_pcm, kind, n, g, st));
+            RET(ceiling_device(c, d_pcm, kind, frames, channels, s.C_inner, W, &ce_in));
+            RET(level_gain_launch(c, d_pcm, d_pcm, kind, n, s.g, st));
+        } else {
+            RET(level_gain_launch(c, src, d_pcm, kind, n, s.g, st));
         }
         HIPCHK(c, hipMemcpyAsync(&hs, st, sizeof hs, hipMemcpyDeviceToHost, c->stream));  // (behind the next sync)
-        if (C) {
-            RET(ceiling_device(c, d_pcm, kind, frames, channels, C, W, ce));
-            if (!boost) ce_in = *ce;
-        }
+        if (C) RET(ceiling_device(c, d_pcm, kind, frames, channels, C, W, ce));
         RET(r128_device(c, d_pcm, kind, frames, channels, rate, sos, &r));
-        const int k = out->passes++;
-        out->pass_gain_q16[k] = g;
-        out->pass_lufs[k] = r.integrated;
-        out->clipped = (int64_t)hs.clipped;
-        if (C) {
-            out->limited_frames = ce_in.limited_frames;
-            out->min_gain_q16 = ce_in.min_gain_q16;
-        }
-        g = level_next(out, capped);
+        g = level_record(out, s, r.integrated, (int64_t)hs.clipped, ce, &ce_in, nc);
     }
     return MM_OK;
 }
@@ -383,13 +454,10 @@ int mm_level_host(int16_t *pcm, int64_t frames, int channels, int32_t rate, cons
     mm_r128 r;
     RET(mm_r128_host(pcm, frames, channels, rate, sos, nullptr, 0, &r));
     out->source_lufs = r.integrated;
+    const int nc = C ? 1 : 0;  // ceilings a pass
     if (!std::isfinite(r.integrated)) {
-        out->status = MM_LEVEL_UNMEASURABLE;
-        if (C) {
-            RET(mm_ceiling_host(pcm, frames, channels, C, W, ce));
-            out->limited_frames = ce->limited_frames;
-            out->min_gain_q16 = ce->min_gain_q16;
-        }
+        if (C) RET(mm_ceiling_host(pcm, frames, channels, C, W, ce));
+        level_unmeasurable(out, ce, nc);
         return MM_OK;
     }
     const size_t n = (size_t)(frames * channels);
@@ -397,47 +465,20 @@ int mm_level_host(int16_t *pcm, int64_t frames, int channels, int32_t rate, cons
     int32_t peak = 0;
     for (size_t i = 0; i < n; ++i) peak = std::max(peak, std::abs((int32_t)src[i]));
     const int32_t g_peak = level_peak_cap(peak);
-    int64_t clipped = 0;
-    auto gain = [&](const int16_t *from, int32_t g) {  // gain(x, g) as the definition writes it
-        clipped = 0;
-        for (size_t i = 0; i < n; ++i) {
-            const int64_t v = (int64_t)from[i] * g + (1 << 15);
-            const int64_t y = v >= 0 ? v >> 16 : -((-v + 65535) >> 16);  // floor(v / 2^16): the arithmetic shift
-            const int64_t d = std::min<int64_t>(32767, std::max<int64_t>(-32768, y));
-            clipped += d != y;
-            pcm[i] = (int16_t)d;
-        }
-    };
     int32_t g = level_first(out);
     while (g) {
-        bool capped = false, boost = false;
-        if (!C) {
-            if (g > g_peak) g = g_peak, capped = true;
-            gain(src.data(), g);
-        } else if (g <= LEVEL_ONE) {
-            gain(src.data(), g);
-        } else {
-            const int32_t g_cap = level_boost_cap(C);
-            if (g > g_cap) g = g_cap, capped = true;
-            boost = true;
+        const LevelStep s = level_step(C, g, g_peak);
+        int64_t clipped = 0;
+        if (s.boost) {
             memcpy(pcm, src.data(), n * sizeof(int16_t));
-            RET(mm_ceiling_host(pcm, frames, channels, level_inner_ceiling(C, g), W, &ce_in));
-            gain(pcm, g);
+            RET(mm_ceiling_host(pcm, frames, channels, s.C_inner, W, &ce_in));
+            level_gain_host(pcm, pcm, n, s.g, clipped);
+        } else {
+            level_gain_host(src.data(), pcm, n, s.g, clipped);
         }
-        if (C) {
-            RET(mm_ceiling_host(pcm, frames, channels, C, W, ce));
-            if (!boost) ce_in = *ce;
-        }
+        if (C) RET(mm_ceiling_host(pcm, frames, channels, C, W, ce));
         RET(mm_r128_host(pcm, frames, channels, rate, sos, nullptr, 0, &r));
-        const int k = out->passes++;
-        out->pass_gain_q16[k] = g;
-        out->pass_lufs[k] = r.integrated;
-        out->clipped = clipped;
-        if (C) {
-            out->limited_frames = ce_in.limited_frames;
-            out->min_gain_q16 = ce_in.min_gain_q16;
-        }
-        g = level_next(out, capped);
+        g = level_record(out, s, r.integrated, clipped, ce, &ce_in, nc);
     }
     return MM_OK;
 }

@@ -1285,6 +1285,7 @@ int mm_kernel_stats(mm_ctx *c, char *names, int names_cap, double *total_ms, int
 #include "wav.hip"
 #include "comm.hip"
 #include "pcm16.h"
+#include "tracks.h"  // the span counts of every grid over frames, one track or many
 #include "meter.hip"
 #include "r128.hip"
 #include "ceiling.hip"

@@ -253,7 +253,7 @@ bool meter_has_geometry(const mm_job *loud, int64_t frames) {
 // frames in [1, 2^31 - METER_SPAN), kind and channels already checked.
 static int meter_launch(mm_ctx *c, const void *d_pcm, int kind, int64_t frames, int channels, MeterDev *res) {
     HIPCHK(c, hipMemsetAsync(res, 0, sizeof(MeterDev), c->stream));
-    const int64_t spans = (frames + 11 + METER_SPAN - 1) / METER_SPAN;
+    const int64_t spans = tracks_need_spans(frames);
     const dim3 grid((unsigned)std::min<int64_t>(spans, (int64_t)METER_WGS_PER_CU * c->n_cus)), block(METER_THREADS);
     return dispatch_pcm(kind, channels, [&](auto ch, auto t) {
         using T = decltype(t);

@@ -308,7 +308,7 @@ static int resample_device(mm_ctx *c, const void *d_in, int kind, int64_t frames
     a.M = rs->M;
     a.K = rs->K;
     a.sub = resample_sub(rs);
-    const dim3 grid((unsigned)((a.Nout + RS_SPAN - 1) / RS_SPAN)), block(RS_THREADS);
+    const dim3 grid((unsigned)tracks_resample_spans(a.Nout)), block(RS_THREADS);
     RET(dispatch_pcm(kind, channels, [&](auto ch, auto t) {
         using T = decltype(t);
         return launch(c, "resample", resample_kernel<ch, T>, grid, block, 0, static_cast<const T *>(d_in), static_cast<T *>(d_out), a);

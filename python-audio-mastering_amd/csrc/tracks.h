@@ -12,7 +12,8 @@
 // (tracks_resample_spans of ceil(frames * L / M)).  The need grid's prefix sums also place
 // the planes: track t's r - 1 plane holds whole spans at first_need[t] * TRACKS_METER_SPAN of
 // one buffer of first_need[n] * TRACKS_METER_SPAN entries, so planes neither overlap nor
-// leave their spans' 16-byte alignment.
+// leave their spans' 16-byte alignment.  A single-track launch (ceiling.hip, meter.hip,
+// resample.hip) is the case n = 1 and counts its spans and its plane with the same functions.
 #pragma once
 
 #include <stdint.h>

@@ -6,8 +6,9 @@
 // No numerics are defined here.  Per track the ceiling is mm_ceiling and the level mm_level,
 // bit for bit, and the converter mm_resample: the kernels run the single-track bodies
 // (ceiling.hip: ceil_need_span, ceil_apply_span, ceil_scale; level.hip: level_gain_span;
-// resample.hip: resample_span) and the decisions are level.hip's
-// level_first / level_next / level_boost_cap / level_inner_ceiling / level_peak_cap.  What is
+// resample.hip: resample_span), the decisions are level.hip's level_first / level_step /
+// level_record / level_peak_cap, the gain's geometry and the kept sources its level_gain_geom
+// and level_keep, and a ceiling's results ceiling.hip's ceiling_results.  What is
 // new is the launch structure: one launch covers the spans of all tracks (tracks.h: a track
 // owns a run of workgroups, a workgroup finds its track by a search over at most 257 prefix
 // sums, which are uniform reads), so a pass of the batch costs the same launches and
@@ -28,9 +29,8 @@
 // a track that takes no part exits on one uniform read of it.
 //
 // Included at the end of mastering.hip after album.hip (album_pass_prepare, album_pass_hops,
-// album_reports measure the tracks of a pass; album_upload packs host tracks).
-
-#include "tracks.h"
+// album_reports measure the tracks of a pass; album_upload and batch_download move host
+// tracks); tracks.h itself is included before meter.hip, whose grid counts its spans too.
 
 namespace mm {
 
@@ -157,14 +157,6 @@ struct TracksLayout {
     std::vector<GainTrack> gain[2];
 };
 
-int64_t gain_wgs(const void *dst, int kind, int64_t n) {
-    if (n == 0) return 0;
-    const int64_t sb = (int64_t)pcm_sample_bytes(kind);
-    const int64_t head = std::min<int64_t>(n, (int64_t)((16 - ((uintptr_t)dst & 15)) & 15) / sb);
-    const int64_t nvec = (n - head) / (16 / sb), vpb = LEVEL_SPAN / (16 / sb);
-    return std::max<int64_t>(1, (nvec + vpb - 1) / vpb);
-}
-
 int tracks_prepare(mm_ctx *c, void *const *d_pcm, int kind, const int64_t *frames, int n, int channels, TracksLayout &L) {
     L.n = n;
     L.kind = kind;
@@ -175,7 +167,7 @@ int tracks_prepare(mm_ctx *c, void *const *d_pcm, int kind, const int64_t *frame
         L.tr[(size_t)t] = TrackDev{d_pcm[t], frames[t]};
         need[(size_t)t] = tracks_need_spans(frames[t]);
         apply[(size_t)t] = tracks_apply_spans(frames[t]);
-        gain[(size_t)t] = gain_wgs(d_pcm[t], kind, frames[t] * channels);
+        gain[(size_t)t] = level_gain_geom(d_pcm[t], d_pcm[t], kind, frames[t] * channels).wgs;  // (by the destination alone)
     }
     L.first_need.resize((size_t)n + 1);
     L.first_apply.resize((size_t)n + 1);
@@ -256,12 +248,10 @@ int tracks_ceiling(mm_ctx *c, TracksLayout &L, const int32_t *Cs, int32_t W, mm_
         if (!L.par[(size_t)t].active) continue;
         const int32_t C = Cs[t];
         mm_ceiling *o = &out[t];
-        o->tp_in_q28 = (int32_t)hs[(size_t)t].tp0;
-        o->tp_limited_q28 = o->tp_out_q28 = o->tp_in_q28 <= C ? o->tp_in_q28 : (int32_t)hp[(size_t)t];
-        o->min_gain_q16 = CEIL_ONE - (int32_t)hs[(size_t)t].max_red;
-        o->limited_frames = (int64_t)hs[(size_t)t].limited;
-        if (o->tp_limited_q28 > C) {  // the residue: one static trim, provably under C
-            const int gt = (int)(((int64_t)(C - CEIL_GUARD) << 16) / o->tp_limited_q28);
+        const int32_t tp0 = (int32_t)hs[(size_t)t].tp0;
+        ceiling_results(o, hs[(size_t)t], tp0 <= C ? tp0 : (int32_t)hp[(size_t)t]);  // (untouched: ceil_tracks_peak skipped it)
+        if (o->tp_limited_q28 > C) {  // the residue: one static trim
+            const int gt = ceiling_trim_gain(C, o->tp_limited_q28);
             L.par_trim[(size_t)t] = TrackPar{C, C - CEIL_GUARD, gt, 1};
             o->trim_q16 = gt;
             trim = true;
@@ -292,16 +282,14 @@ int tracks_ceiling(mm_ctx *c, TracksLayout &L, const int32_t *Cs, int32_t W, mm_
 int tracks_gain_queue(mm_ctx *c, TracksLayout &L, int slot, const void *const *from, void *const *to, const int32_t *g,
                       LevelDev *st) {
     const int n = L.n;
-    const size_t sb = pcm_sample_bytes(L.kind);
     std::vector<GainTrack> &tab = L.gain[slot];
     tab.assign((size_t)n, GainTrack{});
     bool any = false;
     for (int t = 0; t < n; ++t) {
         const int64_t ns = L.tr[(size_t)t].frames * L.channels;
         if (!g[t] || ns == 0) continue;
-        const int head = (int)std::min<int64_t>(ns, (int64_t)(((16 - ((uintptr_t)to[t] & 15)) & 15) / sb));
-        const int src_vec = ((((uintptr_t)from[t]) ^ ((uintptr_t)to[t])) & 15) == 0;
-        tab[(size_t)t] = GainTrack{from[t], to[t], ns, head, src_vec, (int)g[t], 1};
+        const LevelGeom geo = level_gain_geom(from[t], to[t], L.kind, ns);
+        tab[(size_t)t] = GainTrack{from[t], to[t], ns, geo.head, geo.src_vec, (int)g[t], 1};
         any = true;
     }
     if (!any) return MM_OK;
@@ -383,43 +371,31 @@ int batch_level_device(mm_ctx *c, void *const *d_pcm, int kind, const int64_t *f
     RET(measure(active));
     active.clear();
     std::vector<int32_t> Cs(N, 0);
-    std::vector<int> again;
+    std::vector<int> quiet, again;
     for (int t = 0; t < n; ++t) {
         lv[(size_t)t].source_lufs = rep[(size_t)t].integrated;
         if (std::isfinite(rep[(size_t)t].integrated)) {
             active.push_back(t);
             continue;
         }
-        lv[(size_t)t].status = MM_LEVEL_UNMEASURABLE;  // fewer than 4 hops, or silence: only its ceiling
+        quiet.push_back(t);  // fewer than 4 hops, or silence: only its ceiling
         Cs[(size_t)t] = C[t];
     }
-    if (std::any_of(Cs.begin(), Cs.end(), [](int32_t v) { return v != 0; })) {
-        RET(tracks_ceiling(c, L, Cs.data(), W, ceil.data()));
-        for (int t = 0; t < n; ++t) {
-            if (!Cs[(size_t)t]) continue;
-            lv[(size_t)t].limited_frames = ceil[(size_t)t].limited_frames;
-            lv[(size_t)t].min_gain_q16 = ceil[(size_t)t].min_gain_q16;
-            if (ceil[(size_t)t].tp_in_q28 > Cs[(size_t)t]) again.push_back(t);
-        }
-        if (!again.empty()) RET(measure(again));  // the reports describe what is delivered
+    if (std::any_of(Cs.begin(), Cs.end(), [](int32_t v) { return v != 0; })) RET(tracks_ceiling(c, L, Cs.data(), W, ceil.data()));
+    for (int t : quiet) {
+        level_unmeasurable(&lv[(size_t)t], &ceil[(size_t)t], C[t] ? 1 : 0);
+        if (C[t] && ceil[(size_t)t].tp_in_q28 > C[t]) again.push_back(t);
     }
+    if (!again.empty()) RET(measure(again));  // the reports describe what is delivered
     if (active.empty()) return done();
-    // the sources, kept in one buffer, each at its delivered buffer's offset within 16 bytes
-    std::vector<const void *> src(N, nullptr), from(N, nullptr);
-    std::vector<void *> keep_at(N, nullptr), to(N, nullptr);
-    size_t keep_bytes = 0;
-    for (int t = 0; t < n; ++t) keep_bytes += ((pcm_bytes(kind, frames[t], channels) + 15) & ~(size_t)15) + 16;
-    char *keep;
+    std::vector<char *> kept;
+    RET(level_keep(c, "batch_src", d_pcm, kind, frames, n, channels, kept));
+    std::vector<const void *> src(kept.begin(), kept.end()), from(N, nullptr);
+    std::vector<void *> keep_at(kept.begin(), kept.end()), to(N, nullptr);
     LevelDev *st, *st_copy;
     std::vector<LevelDev> hs(N), hs_copy(N);
-    RET(get_buf(c, "batch_src", keep_bytes, &keep));
     RET(get_buf(c, "batch_res", N, &st));
     RET(get_buf(c, "batch_res_copy", N, &st_copy));
-    for (int t = 0; t < n; ++t) {
-        keep_at[(size_t)t] = keep + ((uintptr_t)d_pcm[t] & 15);
-        src[(size_t)t] = keep_at[(size_t)t];
-        keep += ((pcm_bytes(kind, frames[t], channels) + 15) & ~(size_t)15) + 16;
-    }
     // the copies through the kernel at ONE (the identity), all tracks in one launch: they bring
     // max |s| of every track, which caps the gain of a track without a ceiling
     std::vector<int32_t> g(N, 0), g_copy(N, 0), g_peak(N, LEVEL_GMAX);
@@ -435,26 +411,21 @@ int batch_level_device(mm_ctx *c, void *const *d_pcm, int kind, const int64_t *f
         if (!C[t]) g_peak[(size_t)t] = level_peak_cap((int32_t)hs_copy[(size_t)t].peak);
         g[(size_t)t] = level_first(&lv[(size_t)t]);
     }
-    std::vector<char> capped(N), boost(N);
+    std::vector<LevelStep> step(N);
     while (!active.empty()) {
         bool any_boost = false, any_C = false;
         std::fill(Cs.begin(), Cs.end(), 0);
         std::fill(g_copy.begin(), g_copy.end(), 0);
         for (int t : active) {
             const size_t i = (size_t)t;
-            capped[i] = boost[i] = 0;
-            from[i] = src[i];
+            const LevelStep &s = step[i] = level_step(C[t], g[i], g_peak[i]);
+            g[i] = s.g;
+            from[i] = s.boost ? d_pcm[t] : src[i];
             to[i] = d_pcm[t];
-            if (!C[t]) {
-                if (g[i] > g_peak[i]) g[i] = g_peak[i], capped[i] = 1;
-            } else if (g[i] > LEVEL_ONE) {  // the limiter before the boost, so that the boost cannot clip first
-                const int32_t g_cap = level_boost_cap(C[t]);
-                if (g[i] > g_cap) g[i] = g_cap, capped[i] = 1;
-                boost[i] = 1;
+            if (s.boost) {
                 any_boost = true;
                 g_copy[i] = LEVEL_ONE;
-                Cs[i] = level_inner_ceiling(C[t], g[i]);
-                from[i] = d_pcm[t];
+                Cs[i] = s.C_inner;
             }
             any_C |= C[t] != 0;
         }
@@ -470,39 +441,17 @@ int batch_level_device(mm_ctx *c, void *const *d_pcm, int kind, const int64_t *f
             std::fill(Cs.begin(), Cs.end(), 0);
             for (int t : active) Cs[(size_t)t] = C[t];
             RET(tracks_ceiling(c, L, Cs.data(), W, ceil.data()));
-            for (int t : active)
-                if (C[t] && !boost[(size_t)t]) ce_in[(size_t)t] = ceil[(size_t)t];
         }
         RET(measure(active));
         std::vector<int> next;
         for (int t : active) {
             const size_t i = (size_t)t;
-            mm_level *o = &lv[i];
-            const int k = o->passes++;
-            o->pass_gain_q16[k] = g[i];
-            o->pass_lufs[k] = rep[i].integrated;
-            o->clipped = (int64_t)hs[i].clipped;
-            if (C[t]) {
-                o->limited_frames = ce_in[i].limited_frames;
-                o->min_gain_q16 = ce_in[i].min_gain_q16;
-            }
-            g[i] = level_next(o, capped[i] != 0);
+            g[i] = level_record(&lv[i], step[i], rep[i].integrated, (int64_t)hs[i].clipped, &ceil[i], &ce_in[i], C[t] ? 1 : 0);
             if (g[i]) next.push_back(t);
         }
         active.swap(next);
     }
     return done();
-}
-
-// d[t] back into pcm[t] for the tracks `pick` names (null: all), synchronous
-int batch_download(mm_ctx *c, void *const *pcm, const std::vector<void *> &d, int kind, const int64_t *frames, int n,
-                   int channels, const char *pick) {
-    for (int t = 0; t < n; ++t) {
-        const size_t bytes = pcm_bytes(kind, frames[t], channels);
-        if (bytes && (!pick || pick[t])) HIPCHK(c, hipMemcpyAsync(pcm[t], d[(size_t)t], bytes, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return MM_OK;
 }
 
 int batch_ceiling_device(mm_ctx *c, void *const *d_pcm, int kind, const int64_t *frames, int n, int channels,

@@ -671,6 +671,43 @@ def _batch_convert(ctx: native.Context, jobs, rs: Resampler, d_mids, d_outs, kin
     return (ctypes.c_int64 * n)(*[int(m.frames_out) for m in ms]), [resample_dict(m) for m in ms]
 
 
+def _delivery_jobs(jobs, noun: str, call: str):
+    """Refuses (ValueError) jobs that `call` ("the album call" / "the batch call") cannot master and
+    level as the tracks of `noun` ("an album" / "a batch to deliver"): their count, a plan of their
+    own for what the call does, or more than one rate, channel count or output kind.  Returns the
+    shared (rate, channels, output kind)."""
+    if not 1 <= len(jobs) <= native.ALBUM_TRACKS:
+        raise ValueError(f"{noun} has 1 to {native.ALBUM_TRACKS} tracks, not {len(jobs)}")
+    if any(j.delivery is not None for j in jobs):
+        raise ValueError(f"the jobs of {noun} are planned without a delivery (output_rate, deliver_lufs): "
+                         f"{call} levels them")
+    if any(j.job.ceiling_q28 for j in jobs):
+        raise ValueError(f"the jobs of {noun} are planned without ceiling_dbtp: {call} holds the ceiling")
+    if any(j.job.meter_on for j in jobs):
+        raise ValueError(f"the jobs of {noun} are planned without report or r128: they would describe the tracks "
+                         f"before the level, and {call}'s own per-track reports replace them")
+    if len({j.rate for j in jobs}) != 1:
+        raise ValueError(f"the tracks of {noun} must have one sample rate")
+    if len({j.channels for j in jobs}) != 1:
+        raise ValueError(f"the tracks of {noun} must have one channel count")
+    if len({int(j.job.out_kind) for j in jobs}) != 1:
+        raise ValueError(f"the tracks of {noun} must have one output kind")
+    return jobs[0].rate, jobs[0].channels, int(jobs[0].job.out_kind)
+
+
+def _master_converted(ctx: native.Context, jobs, d_ins, d_outs, output_rate, d_mids, noun: str, kind: int, ch: int):
+    """Master the checked jobs of `noun` as a batch into `d_outs`, or with an `output_rate` other
+    than theirs into `d_mids` and from there, converted, into `d_outs`: (the batch's results, the
+    frames in `d_outs` as a c_int64 array, their rate, [resample_dict ...] or None without a
+    converter).  _batch_resampler's refusals come before any device work."""
+    rs = _batch_resampler(jobs, output_rate, d_mids, noun)
+    res = master_batch(ctx, jobs, d_ins, d_outs if rs is None else d_mids)
+    if rs is None:
+        return res, (ctypes.c_int64 * len(jobs))(*[j.frames_proc for j in jobs]), jobs[0].rate, None
+    frames, converted = _batch_convert(ctx, jobs, rs, d_mids, d_outs, kind, ch)
+    return res, frames, int(output_rate), converted
+
+
 def ceiling_pcm(pcm: np.ndarray, rate: int, ceiling_dbtp: float, window: int | None = None, device: int = 0):
     """Hold an int16 (or float32 = int16 / 32768) array [N] or [N, ch] under a true-peak
     ceiling without mastering it (mm_ceiling_pcm): returns (a new array, ceiling_dict).
@@ -815,31 +852,10 @@ def master_album(ctx: native.Context, jobs, d_ins, d_outs, deliver_lufs: float, 
     with another count of them), or a rate pair design.resample_geometry refuses, is a
     ValueError before any device work."""
     jobs = list(jobs)
-    if not 1 <= len(jobs) <= native.ALBUM_TRACKS:
-        raise ValueError(f"an album has 1 to {native.ALBUM_TRACKS} tracks, not {len(jobs)}")
-    if any(j.delivery is not None for j in jobs):
-        raise ValueError("the jobs of an album are planned without a delivery (output_rate, deliver_lufs): "
-                         "the album call levels them")
-    if any(j.job.ceiling_q28 for j in jobs):
-        raise ValueError("the jobs of an album are planned without ceiling_dbtp: the album call holds the ceiling")
-    if any(j.job.meter_on for j in jobs):
-        raise ValueError("the jobs of an album are planned without report or r128: they would describe the tracks "
-                         "before the level, and the album call's own per-track reports replace them")
-    if len({j.rate for j in jobs}) != 1:
-        raise ValueError("the tracks of an album must have one sample rate")
-    if len({j.channels for j in jobs}) != 1:
-        raise ValueError("the tracks of an album must have one channel count")
-    if len({int(j.job.out_kind) for j in jobs}) != 1:
-        raise ValueError("the tracks of an album must have one output kind")
-    rate, ch, kind = jobs[0].rate, jobs[0].channels, int(jobs[0].job.out_kind)
+    _, ch, kind = _delivery_jobs(jobs, "an album", "the album call")
     clu = design.level_clu(deliver_lufs)
     C = 0 if ceiling_dbtp is None else design.ceiling_q28(ceiling_dbtp)
-    rs = _batch_resampler(jobs, output_rate, d_mids, "an album")
-    res = master_batch(ctx, jobs, d_ins, d_outs if rs is None else d_mids)
-    frames, converted = (ctypes.c_int64 * len(jobs))(*[j.frames_proc for j in jobs]), None
-    if rs is not None:
-        frames, converted = _batch_convert(ctx, jobs, rs, d_mids, d_outs, kind, ch)
-        rate = int(output_rate)
+    res, frames, rate, converted = _master_converted(ctx, jobs, d_ins, d_outs, output_rate, d_mids, "an album", kind, ch)
     ctx.check(ctx.lib.mm_album_level_device(ctx.ptr, _pointers(d_outs), kind, frames, len(jobs), ch, rate,
                                             kweight_sos(rate), clu, C, design.ceiling_window(rate)),
               "mm_album_level_device")
@@ -868,6 +884,66 @@ def _pointers_of(tensors):
     return None if tensors is None else [t.data_ptr() for t in tensors]
 
 
+def _process_files(name: str, noun: str, words, per_file: bool, deliver, input_paths, output_paths, params: dict,
+                   device: int, output_rate):
+    """The files of process_album / process_batch (`name`; their tracks are those of `noun`): the
+    params keys and their refusals (`words`: what the target is, which dict carries the reports,
+    what the files then are, where the two calls' sentences differ), the files read and planned,
+    everything that can be refused before the device is touched, the buffers, `deliver`
+    (master_album's arguments in; the batch's results, the call's result, one dict a file for
+    its info and [resample_dict ...] or None out), the files written.  `per_file`: deliver_lufs
+    and ceiling_dbtp may name one value per file, checked before a file is read.  Returns (one
+    info dict a file, the call's result)."""
+    from . import wavio
+    target, carrier, done = words
+    params = dict(params or {})
+    if params.get("deliver_lufs") is None:
+        raise ValueError(f"{name} needs params['deliver_lufs']: {target}")
+    deliver_lufs = params.pop("deliver_lufs")
+    ceiling = params.pop("ceiling_dbtp", None)
+    if params.pop("output_rate", None) is not None:
+        raise ValueError("delivery at another rate (output_rate) is not available for a batch")
+    fmt = params.pop("output_format", "pcm16")
+    for key in ("report", "r128"):
+        if params.get(key):
+            raise ValueError(f"{name} takes no params['{key}']: the {carrier} carries the R 128 report and "
+                             f"the ceiling of every {done} file (meter one with meter_pcm)")
+        params.pop(key, None)
+    input_paths, output_paths = list(input_paths), list(output_paths)
+    if len(input_paths) != len(output_paths):
+        raise ValueError(f"{name} needs one output path for every input path")
+    if per_file:
+        _batch_targets(len(input_paths), deliver_lufs, ceiling, "deliver_lufs")  # (refused before a file is read)
+    kind = native.MM_OUT_F32 if fmt == "f32" else native.MM_OUT_I16
+    pcms, rates = zip(*[wavio.read_wav(p) for p in input_paths]) if input_paths else ((), ())
+    if len(set(rates)) > 1:
+        raise ValueError(f"the tracks of {noun} must have one sample rate")
+    jobs, xs = [], []
+    for pcm in pcms:
+        job = Job(pcm.shape[0], rates[0], 1 if pcm.ndim == 1 else pcm.shape[1], params, kind)
+        x, job.job.in_kind = _device_input(pcm, wide=True)
+        jobs.append(job)
+        xs.append(x)
+    if len({j.channels for j in jobs}) > 1:
+        raise ValueError(f"the tracks of {noun} must have one channel count")
+    if not 1 <= len(jobs) <= native.ALBUM_TRACKS:
+        raise ValueError(f"{noun} has 1 to {native.ALBUM_TRACKS} tracks, not {len(jobs)}")
+    rs = Resampler(rates[0], int(output_rate)) if output_rate is not None and int(output_rate) != rates[0] else None
+    ctx = native.context(device)
+    d_ins, d_mids, d_outs = _batch_buffers(jobs, xs, kind, device, rs)
+    res, result, extras, converted = deliver(ctx, jobs, _pointers_of(d_ins), _pointers_of(d_outs), deliver_lufs, ceiling,
+                                             None if rs is None else int(output_rate), _pointers_of(d_mids))
+    infos = []
+    for t, (job, r, out, path) in enumerate(zip(jobs, res, d_outs, output_paths)):
+        y = out.cpu().numpy()
+        wavio.write_wav(path, y[:, 0] if job.channels == 1 else y, job.rate if rs is None else int(output_rate))
+        info = dict(_info(job, r), **extras[t], output_path=os.path.abspath(path))
+        if rs is not None:
+            info["frames"], info["rate"], info["resample"] = y.shape[0], int(output_rate), converted[t]
+        infos.append(info)
+    return infos, result
+
+
 def process_album(input_paths, output_paths, params: dict, device: int = 0, output_rate: int | None = None):
     """Master the WAV files of an album with the same `params` and level them as one album
     (master_album): params['deliver_lufs'] (required) is the album's target, params['ceiling_dbtp']
@@ -881,47 +957,12 @@ def process_album(input_paths, output_paths, params: dict, device: int = 0, outp
     the files are written with that rate in their headers and every info dict gains "frames",
     "rate" and "resample" as process's does; None or the files' rate: exactly the call without
     it.  ValueError for a rate pair design.resample_geometry refuses, before any device work."""
-    from . import wavio
-    params = dict(params or {})
-    if params.get("deliver_lufs") is None:
-        raise ValueError("process_album needs params['deliver_lufs']: the album's loudness target")
-    deliver_lufs = params.pop("deliver_lufs")
-    ceiling = params.pop("ceiling_dbtp", None)
-    if params.pop("output_rate", None) is not None:
-        raise ValueError("delivery at another rate (output_rate) is not available for a batch")
-    fmt = params.pop("output_format", "pcm16")
-    for key in ("report", "r128"):
-        if params.get(key):
-            raise ValueError(f"process_album takes no params['{key}']: the album dict carries the R 128 report and "
-                             "the ceiling of every levelled file (meter one with meter_pcm)")
-        params.pop(key, None)
-    input_paths, output_paths = list(input_paths), list(output_paths)
-    if len(input_paths) != len(output_paths):
-        raise ValueError("process_album needs one output path for every input path")
-    kind = native.MM_OUT_F32 if fmt == "f32" else native.MM_OUT_I16
-    pcms, rates = zip(*[wavio.read_wav(p) for p in input_paths]) if input_paths else ((), ())
-    if len(set(rates)) > 1:
-        raise ValueError("the tracks of an album must have one sample rate")
-    jobs, xs = [], []
-    for pcm in pcms:
-        job = Job(pcm.shape[0], rates[0], 1 if pcm.ndim == 1 else pcm.shape[1], params, kind)
-        x, job.job.in_kind = _device_input(pcm, wide=True)
-        jobs.append(job)
-        xs.append(x)
-    rs = Resampler(rates[0], int(output_rate)) if jobs and output_rate is not None and int(output_rate) != rates[0] else None
-    ctx = native.context(device)
-    d_ins, d_mids, d_outs = _batch_buffers(jobs, xs, kind, device, rs)
-    res, album = master_album(ctx, jobs, _pointers_of(d_ins), _pointers_of(d_outs), deliver_lufs, ceiling,
-                              None if rs is None else int(output_rate), _pointers_of(d_mids))
-    infos = []
-    for t, (job, r, out, path) in enumerate(zip(jobs, res, d_outs, output_paths)):
-        y = out.cpu().numpy()
-        wavio.write_wav(path, y[:, 0] if job.channels == 1 else y, job.rate if rs is None else int(output_rate))
-        info = dict(_info(job, r), output_path=os.path.abspath(path))
-        if rs is not None:
-            info["frames"], info["rate"], info["resample"] = y.shape[0], int(output_rate), album["resample"][t]
-        infos.append(info)
-    return infos, album
+    def deliver(*call):
+        res, album = master_album(*call)
+        return res, album, [{}] * len(res), album.get("resample")
+
+    return _process_files("process_album", "an album", ("the album's loudness target", "album dict", "levelled"), False,
+                          deliver, input_paths, output_paths, params, device, output_rate)
 
 
 def deliver_batch(ctx: native.Context, jobs, d_ins, d_outs, deliver_lufs, ceiling_dbtp=None,
@@ -945,30 +986,11 @@ def deliver_batch(ctx: native.Context, jobs, d_ins, d_outs, deliver_lufs, ceilin
     count of them), or a rate pair design.resample_geometry refuses, is a ValueError before any
     device work."""
     jobs = list(jobs)
-    if not 1 <= len(jobs) <= native.ALBUM_TRACKS:
-        raise ValueError(f"a batch to deliver has 1 to {native.ALBUM_TRACKS} tracks, not {len(jobs)}")
-    if any(j.delivery is not None for j in jobs):
-        raise ValueError("the jobs of a batch to deliver are planned without a delivery (output_rate, deliver_lufs): "
-                         "the batch call levels them")
-    if any(j.job.ceiling_q28 for j in jobs):
-        raise ValueError("the jobs of a batch to deliver are planned without ceiling_dbtp: the batch call holds the ceiling")
-    if any(j.job.meter_on for j in jobs):
-        raise ValueError("the jobs of a batch to deliver are planned without report or r128: they would describe the "
-                         "tracks before the level, and the batch call's own per-track reports replace them")
-    if len({j.rate for j in jobs}) != 1:
-        raise ValueError("the tracks of a batch to deliver must have one sample rate")
-    if len({j.channels for j in jobs}) != 1:
-        raise ValueError("the tracks of a batch to deliver must have one channel count")
-    if len({int(j.job.out_kind) for j in jobs}) != 1:
-        raise ValueError("the tracks of a batch to deliver must have one output kind")
-    n, rate, ch, kind = len(jobs), jobs[0].rate, jobs[0].channels, int(jobs[0].job.out_kind)
+    _, ch, kind = _delivery_jobs(jobs, "a batch to deliver", "the batch call")
+    n = len(jobs)
     clu, C = _batch_targets(n, deliver_lufs, ceiling_dbtp, "deliver_lufs")
-    rs = _batch_resampler(jobs, output_rate, d_mids, "a batch to deliver")
-    res = master_batch(ctx, jobs, d_ins, d_outs if rs is None else d_mids)
-    frames, converted = (ctypes.c_int64 * n)(*[j.frames_proc for j in jobs]), None
-    if rs is not None:
-        frames, converted = _batch_convert(ctx, jobs, rs, d_mids, d_outs, kind, ch)
-        rate = int(output_rate)
+    res, frames, rate, converted = _master_converted(ctx, jobs, d_ins, d_outs, output_rate, d_mids, "a batch to deliver",
+                                                     kind, ch)
     ctx.check(ctx.lib.mm_batch_level_device(ctx.ptr, _pointers(d_outs), kind, frames, n, ch, rate, kweight_sos(rate), clu, C,
                                             design.ceiling_window(rate)), "mm_batch_level_device")
     lvs = _batch_dicts(ctx, list(C))
@@ -992,52 +1014,12 @@ def process_batch(input_paths, output_paths, params: dict, device: int = 0, outp
     the files are written with that rate in their headers and every info dict gains "frames",
     "rate" and "resample" as process's does; None or the files' rate: exactly the call without
     it.  ValueError for a rate pair design.resample_geometry refuses, before any device work."""
-    from . import wavio
-    params = dict(params or {})
-    if params.get("deliver_lufs") is None:
-        raise ValueError("process_batch needs params['deliver_lufs']: the loudness target of every file")
-    deliver_lufs = params.pop("deliver_lufs")
-    ceiling = params.pop("ceiling_dbtp", None)
-    if params.pop("output_rate", None) is not None:
-        raise ValueError("delivery at another rate (output_rate) is not available for a batch")
-    fmt = params.pop("output_format", "pcm16")
-    for key in ("report", "r128"):
-        if params.get(key):
-            raise ValueError(f"process_batch takes no params['{key}']: the level dict carries the R 128 report and "
-                             "the ceiling of every delivered file (meter one with meter_pcm)")
-        params.pop(key, None)
-    input_paths, output_paths = list(input_paths), list(output_paths)
-    if len(input_paths) != len(output_paths):
-        raise ValueError("process_batch needs one output path for every input path")
-    _batch_targets(len(input_paths), deliver_lufs, ceiling, "deliver_lufs")  # (refused before a file is read)
-    kind = native.MM_OUT_F32 if fmt == "f32" else native.MM_OUT_I16
-    pcms, rates = zip(*[wavio.read_wav(p) for p in input_paths]) if input_paths else ((), ())
-    if len(set(rates)) > 1:
-        raise ValueError("the tracks of a batch to deliver must have one sample rate")
-    jobs, xs = [], []
-    for pcm in pcms:
-        job = Job(pcm.shape[0], rates[0], 1 if pcm.ndim == 1 else pcm.shape[1], params, kind)
-        x, job.job.in_kind = _device_input(pcm, wide=True)
-        jobs.append(job)
-        xs.append(x)
-    if len({j.channels for j in jobs}) > 1:
-        raise ValueError("the tracks of a batch to deliver must have one channel count")
-    if not 1 <= len(jobs) <= native.ALBUM_TRACKS:
-        raise ValueError(f"a batch to deliver has 1 to {native.ALBUM_TRACKS} tracks, not {len(jobs)}")
-    rs = Resampler(rates[0], int(output_rate)) if output_rate is not None and int(output_rate) != rates[0] else None
-    ctx = native.context(device)
-    d_ins, d_mids, d_outs = _batch_buffers(jobs, xs, kind, device, rs)
-    res, lvs = deliver_batch(ctx, jobs, _pointers_of(d_ins), _pointers_of(d_outs), deliver_lufs, ceiling,
-                             None if rs is None else int(output_rate), _pointers_of(d_mids))
-    infos = []
-    for job, r, lv, out, path in zip(jobs, res, lvs, d_outs, output_paths):
-        y = out.cpu().numpy()
-        wavio.write_wav(path, y[:, 0] if job.channels == 1 else y, job.rate if rs is None else int(output_rate))
-        info = dict(_info(job, r), level=lv, output_path=os.path.abspath(path))
-        if rs is not None:
-            info["frames"], info["rate"], info["resample"] = y.shape[0], int(output_rate), lv["resample"]
-        infos.append(info)
-    return infos
+    def deliver(*call):
+        res, lvs = deliver_batch(*call)
+        return res, lvs, [{"level": lv} for lv in lvs], [lv.get("resample") for lv in lvs]
+
+    return _process_files("process_batch", "a batch to deliver", ("the loudness target of every file", "level dict", "delivered"),
+                          True, deliver, input_paths, output_paths, params, device, output_rate)[0]
 
 
 def process(input_path: str, output_path: str, params: dict, device: int = 0, verbose: bool = False) -> dict:

@@ -423,9 +423,10 @@ def test_python_refusals_need_no_gpu(tmp_path, monkeypatch):
     with pytest.raises(ValueError, match="outside"):
         master_album(None, [job()], [0], [0], -4.0)
     # process_album: the keys and the files
-    a, b = str(tmp_path / "a.wav"), str(tmp_path / "b.wav")
+    a, b, m = str(tmp_path / "a.wav"), str(tmp_path / "b.wav"), str(tmp_path / "m.wav")
     wavio.write_wav(a, np.zeros((44100, 2), np.int16), 44100)
     wavio.write_wav(b, np.zeros((48000, 2), np.int16), 48000)
+    wavio.write_wav(m, np.zeros(44100, np.int16), 44100)
     with pytest.raises(ValueError, match="deliver_lufs"):
         process_album([a], [a + ".out"], {"lufs": -14.0})
     with pytest.raises(ValueError, match=r"delivery at another rate \(output_rate\) is not available for a batch"):
@@ -437,6 +438,8 @@ def test_python_refusals_need_no_gpu(tmp_path, monkeypatch):
         process_album([a, b], [a + ".out"], {"deliver_lufs": -14.0})
     with pytest.raises(ValueError, match="one sample rate"):
         process_album([a, b], [a + ".out", b + ".out"], {"deliver_lufs": -14.0})
+    with pytest.raises(ValueError, match="the tracks of an album must have one channel count"):
+        process_album([a, m], [a + ".out", m + ".out"], {"deliver_lufs": -14.0})
     # master_batch still refuses a job planned with deliver_lufs
     with pytest.raises(ValueError, match="deliver_lufs"):
         engine.master_batch(None, [job(deliver_lufs=-14.0)], [0], [0])
