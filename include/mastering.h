@@ -142,7 +142,8 @@ typedef struct mm_job {
        when the job carries loudness geometry (kweight, blocks, segments), whether or
        not lufs_on is set.  0: the chain queues exactly what it queued before.  Bit 1
        (MM_REPORT_R128; a new value of this field, the struct is unchanged) adds the R 128
-       report of the delivered output (mm_last_r128), which needs kweight.sos and rate. */
+       report of the delivered output (mm_last_r128), which needs kweight.sos and rate.  Bit 2
+       (MM_REPORT_QC; again a new value only) adds its QC report (mm_last_qc), which needs rate. */
     int32_t meter_on;
     /* true-peak ceiling (ABI 5, the former trailing pad): 0 = off, the chain queues exactly
        what it queued before; else the ceiling C as linear * 2^28, 2^24 <= C <= 2^28
@@ -346,11 +347,62 @@ typedef struct mm_r128 {
     double lra_low, lra_high;  /* LUFS: the 10th and 95th percentile levels of step 6  */
 } mm_r128;
 
+/* The delivery QC report of a delivered signal (no reference counterpart): what an ingest
+ * check asks beyond loudness and true peak, as exact integer statements about the int16 grid.
+ * Signal s[c][n] on the int16 grid (MM_OUT_F32 carries the same PCM / 32768 and is converted
+ * back on load, as in the meter), CH = 1 or 2 channels, N frames with 0 <= N < 2^31, rate R.
+ * Parameters: silence_lsb q in 0..32767, min_run r in 1..65535.
+ *   1. Totals (int64, exact: sq <= 2^61): sum[c] = sum s, sq[c] = sum s^2, cross = sum s0 * s1
+ *      (0 for mono); smin[c], smax[c] (0 when N == 0); or_bits[c] = OR of (uint16) s over n.
+ *   2. Silence.  Frame n is silent when |s[c][n]| <= q for every channel.  lead_silence = the
+ *      index of the first non-silent frame (N if none); trail_silence = N - 1 - the last
+ *      non-silent index (N if none); silent_frames = their count; silence_longest /
+ *      silence_longest_at = length and start of the longest maximal run of silent frames
+ *      anywhere, the first among equals (no silent frame: 0, -1).  A dropout is such a run with
+ *      at > 0 and at + len < N.
+ *   3. Clip runs, per channel.  rail = +1 if s == 32767, -1 if s <= -32767, else 0.  A run is a
+ *      maximal stretch of consecutive frames of equal non-zero rail.  clip_samples[c] = frames
+ *      with rail != 0 (== mm_meter.clipped[c]); clip_runs[c] = runs of length >= r;
+ *      clip_longest[c] / clip_longest_at[c] = the longest run and its start (the first of
+ *      equals; none: 0, -1).
+ *   4. Hops, as mm_r128's: B[i] = floor(i * R / 10), H = floor(10 * N / R) complete hops; per
+ *      hop i < H three int64: a[i] = sum s0^2, b[i] = sum s1^2, x[i] = sum s0 * s1 over
+ *      [B[i], B[i+1]) (mono: b = x = 0).  Frames from B[H] on belong to no hop.
+ *   5. Correlation over time (stereo only), in 400 ms windows: a window is 4 hops at j with
+ *      j + 4 <= H; A, Bw, X are its sums of a, b, x and n_w = B[j+4] - B[j].  It is gated in
+ *      when A + Bw >= 2048 * n_w (mean square at least 32^2 a channel, about -60 dBFS: an
+ *      integer comparison).  rho[j] = 0 if A == 0 or Bw == 0, else (double)X / sqrt((double)A *
+ *      (double)Bw), every operation one correctly rounded IEEE operation.  corr_windows = the
+ *      gated windows; corr_negative = those with X < 0 (exact); corr_min = the smallest rho of
+ *      a gated window (NaN if none); corr_min_hop = the smallest j attaining it (-1 if none).
+ *      Mono: 0, 0, NaN, -1.
+ * Everything else a caller reads (DC offset, overall correlation, mono fold-down level, bit use,
+ * dual mono, seconds, the dropout) derives from these integers (engine.qc_dict).  No verdicts:
+ * thresholds are the caller's. */
+typedef struct mm_qc {
+    int64_t frames;
+    int32_t channels;
+    int32_t rate;
+    int64_t hops;                /* H                                                    */
+    int32_t silence_lsb;         /* q                                                    */
+    int32_t min_run;             /* r                                                    */
+    int64_t sum[2], sq[2], cross;
+    int32_t smin[2], smax[2];
+    uint32_t or_bits[2];
+    int64_t lead_silence, trail_silence, silent_frames;
+    int64_t silence_longest, silence_longest_at;
+    int64_t clip_samples[2], clip_runs[2], clip_longest[2], clip_longest_at[2];
+    int64_t corr_windows, corr_negative, corr_min_hop;
+    double corr_min;
+} mm_qc;
+
 /* Bits of mm_job.meter_on and mm_delivery.meter_on: which reports of the delivered output
  * the master call makes (0 and 1 mean what they meant before the second bit). */
 #define MM_REPORT_METER 1 /* mm_meter (mm_last_meters)                                  */
 #define MM_REPORT_R128 2  /* mm_r128 (mm_last_r128), from the kweight.sos and the rate of
                              the job (a delivery: of its `loud` job, which must be set)  */
+#define MM_REPORT_QC 4    /* mm_qc (mm_last_qc) with silence_lsb 1 and min_run 3, at the rate
+                             of the job (a delivery: of its `loud` job, which must be set) */
 
 /* What mm_job cannot carry for a delivery (mm_deliver*): the converter to another rate and,
  * acting on the delivered signal, the loudness target, the ceiling and the report. */
@@ -360,7 +412,8 @@ typedef struct mm_delivery {
     int32_t ceiling_q28;     /* 0 = off; else as mm_job.ceiling_q28                  */
     int32_t window;          /* the ceiling's look-ahead at rate_out (frames)        */
     int32_t meter_on;        /* MM_REPORT_METER: meter the delivered output (mm_last_meters);
-                                MM_REPORT_R128: its R 128 report (mm_last_r128)       */
+                                MM_REPORT_R128: its R 128 report (mm_last_r128);
+                                MM_REPORT_QC: its QC report (mm_last_qc), at loud's rate */
     int32_t level_clu;       /* the former pad: 0 = off (nothing new is queued); else the
                                 loudness target in centi-LU, -4000 .. -500 (design.level_clu):
                                 the delivered signal is levelled to it under the ceiling
@@ -425,7 +478,10 @@ int mm_sync(mm_ctx *ctx);
    mm_op_r128_album_hops, mm_album_level_device, mm_album_level_pcm, mm_last_album); and, again
    as entry points only, the batch (mm_batch_ceiling_device, mm_batch_ceiling_pcm,
    mm_batch_level_device, mm_batch_level_pcm) and its converter (mm_batch_resample_device,
-   mm_batch_resample_pcm).  A caller
+   mm_batch_resample_pcm); and, as a new struct and entry points and a new value of an
+   existing field (bit 2 of mm_job.meter_on and mm_delivery.meter_on): mm_qc and the QC report
+   (mm_qc_from_hops, mm_qc_host, mm_qc_device, mm_qc_pcm, mm_batch_qc_device, mm_batch_qc_pcm,
+   mm_qc_span, mm_last_qc).  A caller
    built against an older header must
    refuse a library whose version differs from its own MM_ABI_VERSION. */
 #define MM_ABI_VERSION 5
@@ -520,6 +576,48 @@ int mm_r128_span(void);
  * for a batch in job order (frames 0 and NaN figures for a job without MM_REPORT_R128);
  * copies min(cap, n) and returns n.  MM_ERR_STATE if no job of that call asked for one. */
 int mm_last_r128(mm_ctx *ctx, int cap, mm_r128 *out);
+
+/* ---- delivery QC report ------------------------------------------------------ */
+/* Step 5 of mm_qc on a stereo signal's hop table hops[H][3] = {a, b, x} in plain C++ (no
+ * context, no GPU): the one tail the host restatement and the GPU path end in.  Sets hops,
+ * rate, corr_windows, corr_negative, corr_min and corr_min_hop of *out and touches no other
+ * field (the table carries no channel count: a mono caller keeps 0, 0, NaN, -1 without
+ * calling).  MM_ERR_ARG for a null pointer, H < 0 or rate < 2000. */
+int mm_qc_from_hops(const int64_t *hops, int64_t H, int32_t rate, mm_qc *out);
+/* The definition restated sequentially on the host (no context, no GPU), interleaved int16.
+ * hops_out (may be NULL) receives the whole table [H][3], H = floor(10 * frames / rate).
+ * MM_ERR_ARG for channels other than 1 or 2, frames outside [0, 2^31), rate < 2000,
+ * silence_lsb outside [0, 32767], min_run outside [1, 65535] or a null pointer. */
+int mm_qc_host(const int16_t *pcm, int64_t frames, int channels, int32_t rate, int32_t silence_lsb, int32_t min_run,
+               mm_qc *out, int64_t *hops_out);
+/* The report of a device-resident signal, interleaved [frames][channels] of `kind` (MM_OUT_I16,
+ * or MM_OUT_F32 = the same PCM / 32768: both give the same mm_qc): one memset, the span launch,
+ * the fold launch and one read-back, then mm_qc_from_hops.  hops_out (may be NULL) as above.
+ * MM_ERR_ARG as mm_qc_host, with words in mm_last_error, and for a bad kind.  The audio is
+ * never altered.  Synchronous on return. */
+int mm_qc_device(mm_ctx *ctx, const void *d_pcm, int kind, int64_t frames, int channels, int32_t rate,
+                 int32_t silence_lsb, int32_t min_run, mm_qc *out, int64_t *hops_out);
+/* The same on a host buffer. */
+int mm_qc_pcm(mm_ctx *ctx, const void *pcm, int kind, int64_t frames, int channels, int32_t rate, int32_t silence_lsb,
+              int32_t min_run, mm_qc *out, int64_t *hops_out);
+/* The reports of n device-resident tracks of one kind, channel count and rate, 1 <= n <=
+ * MM_ALBUM_TRACKS: out[t] is mm_qc_device's of track t alone (a run never joins across two
+ * tracks and no frame of a neighbour is read), with one memset, two launches and one read-back
+ * whatever n.  The results are also left behind mm_last_qc; the levels, ceilings and R 128
+ * reports of the context's last call stay as they are.  MM_ERR_ARG, with words that name the
+ * track and before anything is queued, for a track mm_qc_device refuses or a total of 2^31
+ * frames or more.  Synchronous on return. */
+int mm_batch_qc_device(mm_ctx *ctx, const void *const *d_pcm, int kind, const int64_t *frames, int n, int channels,
+                       int32_t rate, int32_t silence_lsb, int32_t min_run, mm_qc *out);
+/* The same on host buffers. */
+int mm_batch_qc_pcm(mm_ctx *ctx, const void *const *pcm, int kind, const int64_t *frames, int n, int channels,
+                    int32_t rate, int32_t silence_lsb, int32_t min_run, mm_qc *out);
+/* Frames one workgroup of the span kernel covers (where its seams lie). */
+int mm_qc_span(void);
+/* The QC reports of the last master call (as mm_last_meters; frames 0: that job did not ask)
+ * or mm_batch_qc_* call on this context: copies min(cap, n) and returns n.  MM_ERR_STATE if
+ * that call made none. */
+int mm_last_qc(mm_ctx *ctx, int cap, mm_qc *out);
 
 /* ---- true-peak ceiling ----------------------------------------------------- */
 /* Hold a device-resident signal, interleaved [frames][channels] of `kind` (MM_OUT_I16,

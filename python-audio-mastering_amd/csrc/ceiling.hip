@@ -364,7 +364,7 @@ static int level_device(mm_ctx *c, void *d_pcm, int kind, int64_t frames, int ch
 // the ceiling, or with a loudness target (level_clu, a delivery's) the level that contains
 // it, then the reports, which so measure what is delivered: bit 0 of meter_on the
 // meter, bit 1 the R 128 report (r128.hip) with the K-weighting sections and the rate of
-// `loud`, which the level takes too.  A track that did not ask for what another track of the
+// `loud`, which the level takes too, bit 2 the QC report (qc.hip) at that rate.  A track that did not ask for what another track of the
 // call asked for leaves a cleared entry.
 static int finish_delivered(mm_ctx *c, void *d_out, int kind, int64_t frames, int channels, int i, int32_t ceiling_q28,
                             int32_t window, int meter_on, const mm_job *loud, int32_t level_clu) {
@@ -383,6 +383,12 @@ static int finish_delivered(mm_ctx *c, void *d_out, int kind, int64_t frames, in
         RET(r128_device(c, d_out, kind, frames, channels, loud->rate, loud->kweight.sos, &c->r128s[(size_t)i]));
     } else if (!c->r128s.empty()) {
         r128_clear(&c->r128s[(size_t)i], 0, channels, 0);
+    }
+    if (meter_on & MM_REPORT_QC) {
+        if (!loud) return set_err(c, MM_ERR_ARG, "the QC report needs a job with the rate of the delivered signal");
+        RET(qc_device(c, d_out, kind, frames, channels, loud->rate, QC_REPORT_LSB, QC_REPORT_RUN, &c->qcs[(size_t)i], nullptr));
+    } else if (!c->qcs.empty()) {
+        qc_clear(&c->qcs[(size_t)i], 0, channels, 0, QC_REPORT_LSB, QC_REPORT_RUN);
     }
     return MM_OK;
 }

@@ -71,6 +71,8 @@ struct mm_ctx {
     std::vector<mm_meter> meters;
     // R 128 reports of the last master call (mm_last_r128; empty: no job asked for one)
     std::vector<mm_r128> r128s;
+    // QC reports of the last master call or mm_batch_qc_* call (mm_last_qc; empty: none was made)
+    std::vector<mm_qc> qcs;
     // ceilings of the last master call (mm_last_ceilings; empty: no job set one)
     std::vector<mm_ceiling> ceilings;
     // levels of the last master call (mm_last_levels; empty: its delivery set no loudness target)

@@ -21,6 +21,8 @@
 //                      store switched off (a track whose TP0 <= C was not touched: skipped)
 //   ceil_tracks_trim   pointwise, the tracks with a residue only, each by its own g_t
 //   level_tracks_gain  level_gain; head and tail single samples by a track's first workgroup
+//   qc_tracks          the QC report's span kernel (qc.hip: qc_span) over all METER_SPAN spans;
+//                      the fold that follows is qc.hip's own, one workgroup a track
 //   resample_tracks    the converter (resample.hip: resample_span) over all RS_SPAN spans of
 //                      output frames; every position relative to the track's own start, the
 //                      statistics into the track's RsDev (mm_batch_resample_*: one memset,
@@ -137,6 +139,16 @@ __global__ void __launch_bounds__(RS_THREADS) resample_tracks_kernel(const RsTra
     a.st += t;
     resample_span<CH, T>(static_cast<const T *>(k.in), static_cast<T *>(k.out), a,
                          (int64_t)(blockIdx.x - first[t]) * RS_SPAN);
+}
+
+// the QC report's span kernel (qc.hip: qc_span) over the spans of all tracks: a record lands among
+// its track's own, a hop piece in its track's own rows, and every frame index is the track's
+template <int CH, typename T>
+__global__ void __launch_bounds__(QC_THREADS) qc_tracks_kernel(QcLaunch L) {
+    const int t = tracks_find(L.first, L.n, blockIdx.x);
+    const QcTrack tr = L.tr[t];
+    qc_span<CH, T>(static_cast<const T *>(tr.pcm), tr, (int64_t)(blockIdx.x - L.first[t]), L.rate, L.q, L.r,
+                   L.rec + L.first[t], L.hops + 3 * tr.hop0);
 }
 
 }  // namespace mm
@@ -531,9 +543,59 @@ int batch_resample_device(mm_ctx *c, const void *const *d_in, int kind, const in
     return MM_OK;
 }
 
+// Refuses what is not a batch to check (MM_ERR_ARG, the sentence names the track), before
+// anything is queued.
+int batch_qc_check(mm_ctx *c, const void *const *pcm, int kind, const int64_t *frames, int n, int channels, int rate, int q,
+                   int r, const mm_qc *out) {
+    if (n < 1 || n > MM_ALBUM_TRACKS) return set_err(c, MM_ERR_ARG, "batch: %d tracks out of range [1, %d]", n, MM_ALBUM_TRACKS);
+    if (!pcm || !frames || !out) return set_err(c, MM_ERR_ARG, "bad arguments");
+    if (!pcm_kind_ok(kind)) return set_err(c, MM_ERR_ARG, PCM_BAD_KIND, kind);
+    int64_t total = 0;
+    for (int t = 0; t < n; ++t) {
+        if (const char *why = qc_refusal(channels, frames[t], rate, q, r)) return set_err(c, MM_ERR_ARG, "batch: track %d: %s", t, why);
+        if (frames[t] > 0 && !pcm[t]) return set_err(c, MM_ERR_ARG, "batch: track %d: null pointer", t);
+        total += frames[t];
+        if (total >= QC_MAX_FRAMES) return set_err(c, MM_ERR_ARG, "batch: track %d: 2^31 frames or more in all", t);
+    }
+    return MM_OK;
+}
+
+// The QC reports of n checked device-resident tracks (synchronous on return): qc.hip's qc_run
+// with the span launch over all tracks.  Only c->qcs is set: the levels, ceilings and R 128
+// reports of the context's last call stay.
+int batch_qc_device(mm_ctx *c, const void *const *d_pcm, int kind, const int64_t *frames, int n, int channels, int rate, int q,
+                    int r, mm_qc *out) {
+    RET(qc_run(c, d_pcm, frames, n, channels, rate, q, r, out, nullptr, [&](const QcLaunch &L, uint32_t grid) {
+        return dispatch_pcm(kind, channels, [&](auto ch, auto t) {
+            using T = decltype(t);
+            return launch(c, "qc_tracks", qc_tracks_kernel<ch, T>, dim3(grid), dim3(QC_THREADS), 0, L);
+        });
+    }));
+    c->qcs.assign(out, out + n);
+    return MM_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mm_batch_qc_device(mm_ctx *c, const void *const *d_pcm, int kind, const int64_t *frames, int n, int channels,
+                       int32_t rate, int32_t silence_lsb, int32_t min_run, mm_qc *out) {
+    if (!c) return MM_ERR_ARG;
+    RET(batch_qc_check(c, d_pcm, kind, frames, n, channels, rate, silence_lsb, min_run, out));
+    HIPCHK(c, hipSetDevice(c->device));
+    return batch_qc_device(c, d_pcm, kind, frames, n, channels, rate, silence_lsb, min_run, out);
+}
+
+int mm_batch_qc_pcm(mm_ctx *c, const void *const *pcm, int kind, const int64_t *frames, int n, int channels, int32_t rate,
+                    int32_t silence_lsb, int32_t min_run, mm_qc *out) {
+    if (!c) return MM_ERR_ARG;
+    RET(batch_qc_check(c, pcm, kind, frames, n, channels, rate, silence_lsb, min_run, out));
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<void *> d;
+    RET(album_upload(c, "batch_qc_in", pcm, kind, frames, n, channels, d));
+    return batch_qc_device(c, d.data(), kind, frames, n, channels, rate, silence_lsb, min_run, out);
+}
 
 int mm_batch_ceiling_device(mm_ctx *c, void *const *d_pcm, int kind, const int64_t *frames, int n, int channels,
                             const int32_t *ceiling_q28, int32_t window, mm_ceiling *out) {

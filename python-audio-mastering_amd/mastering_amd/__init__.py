@@ -20,6 +20,12 @@ Public surface (mirrors worker/audio_mastering_engine.py):
                                the EBU R 128 report (no reference counterpart): integrated
                                loudness as a BS.1770 meter reads it, maximum momentary and
                                short-term loudness and the loudness range of the delivered output
+  params["qc"], qc_pcm(pcm, rate), qc_batch_pcm(tracks, rate), qcs(ctx), deliver_batch / master_album /
+  process_batch / process_album(..., qc=True)
+                               the delivery QC report (no reference counterpart): phase
+                               correlation overall and in 400 ms windows, DC offset, runs of
+                               full-scale samples, digital silence at the ends and inside, bit
+                               use and dual mono of the delivered output, as exact integers
   params["ceiling_dbtp"], ceiling_pcm(pcm, rate, db), ceilings(ctx)
                                the true-peak ceiling (no reference counterpart): an exact
                                look-ahead limiter on the delivered output
@@ -51,8 +57,8 @@ Public surface (mirrors worker/audio_mastering_engine.py):
 """
 from .engine import (EQ_PRESETS, Job, album_level_pcm, album_r128_pcm, ceiling_batch_pcm, ceiling_pcm, ceilings,  # noqa: F401
                      deliver_batch, level_batch_pcm, level_pcm, levels, master_album, master_batch, master_device,
-                     master_pcm, meter_pcm, meters, process, process_album, process_batch, r128_pcm, r128s, resample_batch_pcm,
-                     resample_pcm)
+                     master_pcm, meter_pcm, meters, process, process_album, process_batch, qc_batch_pcm, qc_dict, qc_pcm, qcs,
+                     r128_pcm, r128s, resample_batch_pcm, resample_pcm)
 from . import legacy  # noqa: F401
 from .gui_compat import batch_process_audio, process_audio  # noqa: F401
 from .ops import (apply_eq_to_samples, apply_multiband_compressor, apply_peak_filter, apply_saturation,  # noqa: F401
@@ -65,4 +71,4 @@ __all__ = ["legacy", "EQ_PRESETS", "Job", "master_pcm", "master_device", "master
            "float_array_to_audio_segment", "integrated_loudness", "true_peak", "meter_pcm", "meters", "ceiling_pcm",
            "ceilings", "resample_pcm", "r128_pcm", "r128s", "level_pcm", "levels", "album_level_pcm", "album_r128_pcm",
            "master_album", "process_album", "ceiling_batch_pcm", "level_batch_pcm", "deliver_batch", "process_batch",
-           "resample_batch_pcm"]
+           "resample_batch_pcm", "qc_pcm", "qc_batch_pcm", "qc_dict", "qcs"]

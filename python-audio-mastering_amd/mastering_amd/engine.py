@@ -69,7 +69,7 @@ class Job:
                  seg_bounds=None, check_length: bool = True, single_chunk: bool = False,
                  crossover=(design.LOW_CROSSOVER, design.HIGH_CROSSOVER), report: bool = False,
                  ceiling_dbtp: float | None = None, output_rate: int | None = None, r128: bool = False,
-                 deliver_lufs: float | None = None):
+                 deliver_lufs: float | None = None, qc: bool = False):
         """`seg_bounds` (time-sharded ranks, distributed.py): this range's loudness
         segment bounds relative to its first frame; the whole-track gating then
         happens on the host after the all-reduce.  `check_length=False` skips
@@ -97,7 +97,9 @@ class Job:
         a delivery, with `output_rate` or without (then without a converter: self.resampler and
         self.output_rate stay None), to which the ceiling and the reports move, and the `loud`
         job with the sections of the delivered rate; not on a time-sharded range or a per-stage
-        operator."""
+        operator.  `qc`: the delivery QC report of the delivered output (bit 2 of meter_on,
+        mm_last_qc; independent of `report` and `r128`); with a delivery the bit moves to it, as
+        `r128` does; not on a time-sharded range, whose rank does not hold the whole track."""
         if deliver_lufs is not None and (seg_bounds is not None or single_chunk):
             raise ValueError("a loudness target (deliver_lufs) needs the whole chain: not available on a "
                              "time-sharded range or a per-stage operator")
@@ -107,6 +109,8 @@ class Job:
             raise ValueError("the true-peak ceiling needs the whole track: not available on a time-sharded range")
         if r128 and seg_bounds is not None:
             raise ValueError("the R 128 report needs the whole track: not available on a time-sharded range")
+        if qc and seg_bounds is not None:
+            raise ValueError("the QC report needs the whole track: not available on a time-sharded range")
         if output_rate is not None and int(output_rate) == int(rate):
             output_rate = None
         if output_rate is not None and (seg_bounds is not None or single_chunk):
@@ -117,6 +121,7 @@ class Job:
         delivers = output_rate is not None or level != 0
         plan_report, report = report, bool(report) and not delivers  # (a delivery's report is planned below)
         plan_r128, r128 = bool(r128), bool(r128) and not delivers
+        plan_qc, qc = bool(qc), bool(qc) and not delivers
         if channels not in (1, 2):
             raise ValueError("only mono and stereo are supported (AME:119,137,152)")
         params = dict(params or {})
@@ -184,7 +189,8 @@ class Job:
         j.comp_warmup = COMP_WARMUP
         j.comp_max_iters = COMP_MAX_ITERS
         j.comp_super = comp_super_frames(self.rate, self.tile)
-        j.meter_on = (native.REPORT_METER if report else 0) | (native.REPORT_R128 if r128 else 0)
+        j.meter_on = ((native.REPORT_METER if report else 0) | (native.REPORT_R128 if r128 else 0)
+                      | (native.REPORT_QC if qc else 0))
         self.ceiling_dbtp = None if ceiling_dbtp is None else float(ceiling_dbtp)
         j.ceiling_q28 = 0 if ceiling_dbtp is None else design.ceiling_q28(ceiling_dbtp)
         # --- loudness (with `report` alone: the geometry only, for the meter; with `r128`
@@ -218,11 +224,12 @@ class Job:
                 out_rate = self.output_rate
             d.ceiling_q28, j.ceiling_q28 = j.ceiling_q28, 0
             d.window = design.ceiling_window(out_rate)
-            d.meter_on = (native.REPORT_METER if plan_report else 0) | (native.REPORT_R128 if plan_r128 else 0)
+            d.meter_on = ((native.REPORT_METER if plan_report else 0) | (native.REPORT_R128 if plan_r128 else 0)
+                          | (native.REPORT_QC if plan_qc else 0))
             d.level_clu = level
             # the output's loudness, as meter_pcm plans it, and the sections of the output's rate for the
-            # R 128 report and the level
-            if (plan_report and self.frames_out >= 0.4 * out_rate) or plan_r128 or level:
+            # R 128 report and the level; the QC report reads its rate alone
+            if (plan_report and self.frames_out >= 0.4 * out_rate) or plan_r128 or level or plan_qc:
                 self._loud = Job(self.frames_out, out_rate, self.channels, {}, single_chunk=True,
                                  report=bool(plan_report), r128=plan_r128 or bool(level))
                 d.loud = ctypes.pointer(self._loud.job)
@@ -360,6 +367,97 @@ def r128_pcm(pcm: np.ndarray, rate: int, device: int = 0) -> dict:
     ctx.check(ctx.lib.mm_r128_pcm(ctx.ptr, x.ctypes.data_as(ctypes.c_void_p), kind, x.shape[0], ch, int(rate),
                                   kweight_sos(rate), ctypes.byref(m)), "mm_r128_pcm")
     return r128_dict(m)
+
+
+def _ratio_db(num: int, den: int) -> float | None:
+    """10 log10(num / den) of two non-negative integers (None for 0 / 0, -inf for 0 / den)."""
+    if den == 0:
+        return None
+    return 10.0 * math.log10(num / den) if num > 0 else -math.inf
+
+
+def qc_dict(m: native.MMQc) -> dict:
+    """An mm_qc as `info["qc"]`: the struct's integers (per-channel figures as lists) and what
+    derives from them.  `dc_offset` (of full scale); `correlation` (overall phase correlation,
+    None for mono or a silent channel) and `corr_min` (the lowest of a gated 400 ms window, None
+    without one) at `corr_min_seconds`; `mono_fold_db`, the level of (L + R) / 2 against the
+    channel mean, and `side_mid_db`, side against mid (None for mono or silence);
+    `dual_mono` (L == R everywhere); `effective_bits` (16 minus the zero low bits all samples
+    share; 0 for digital zero); lead, trail and longest silence in seconds; `dropout` = (at,
+    len) of the longest silent run if it touches neither end, else None.  No verdicts:
+    thresholds are the caller's.  No reference counterpart."""
+    ch, N, rate = int(m.channels), int(m.frames), int(m.rate)
+    d = {f: int(getattr(m, f)) for f in ("frames", "channels", "rate", "hops", "silence_lsb", "min_run", "cross",
+                                         "lead_silence", "trail_silence", "silent_frames", "silence_longest",
+                                         "silence_longest_at", "corr_windows", "corr_negative", "corr_min_hop")}
+    for f in ("sum", "sq", "smin", "smax", "or_bits", "clip_samples", "clip_runs", "clip_longest", "clip_longest_at"):
+        d[f] = [int(getattr(m, f)[c]) for c in range(ch)]
+    d["corr_min"] = None if math.isnan(m.corr_min) else float(m.corr_min)
+    d["corr_min_seconds"] = None if d["corr_min_hop"] < 0 else (d["corr_min_hop"] * rate // 10) / rate
+    d["dc_offset"] = [s / N / 32768.0 if N else 0.0 for s in d["sum"]]
+    d["effective_bits"] = [16 - ((b & -b).bit_length() - 1) if b else 0 for b in d["or_bits"]]
+    d["correlation"] = d["mono_fold_db"] = d["side_mid_db"] = None
+    d["dual_mono"] = False
+    if ch == 2:
+        sq0, sq1, x = d["sq"][0], d["sq"][1], d["cross"]
+        if sq0 and sq1:
+            d["correlation"] = x / math.sqrt(sq0 * sq1)
+        d["mono_fold_db"] = _ratio_db(sq0 + sq1 + 2 * x, 2 * (sq0 + sq1))
+        d["side_mid_db"] = _ratio_db(sq0 + sq1 - 2 * x, sq0 + sq1 + 2 * x)
+        d["dual_mono"] = sq0 + sq1 - 2 * x == 0
+    sec = (lambda n: n / rate) if rate else (lambda n: 0.0)
+    d["lead_silence_seconds"], d["trail_silence_seconds"] = sec(d["lead_silence"]), sec(d["trail_silence"])
+    d["silence_longest_seconds"] = sec(d["silence_longest"])
+    at, ln = d["silence_longest_at"], d["silence_longest"]
+    d["dropout"] = (at, ln) if at > 0 and at + ln < N else None
+    return d
+
+
+def qcs(ctx: native.Context, cap: int = native.BATCH_STREAMS) -> list:
+    """The mm_qc of every track of the context's last master call or QC batch (mm_last_qc), in
+    job order (frames 0: that job did not ask).  RuntimeError if that call made none."""
+    return _last(ctx, "mm_last_qc", native.MMQc, cap)
+
+
+def qc_pcm(pcm: np.ndarray, rate: int, silence_lsb: int = 1, min_run: int = 3, curve: bool = False, device: int = 0):
+    """The delivery QC report (qc_dict) of an int16 (or float32 = int16 / 32768) array [N] or
+    [N, ch] without mastering it (mm_qc_pcm).  A frame is silent when every channel lies within
+    `silence_lsb` of zero; a clip run counts from `min_run` consecutive full-scale samples.
+    `curve=True` returns (qc_dict, the [H, 3] int64 hop table of sum L^2, sum R^2, sum L R a
+    100 ms hop), from which the correlation over time can be plotted."""
+    ch = 1 if pcm.ndim == 1 else pcm.shape[1]
+    x, kind = _out_kind(pcm)
+    ctx = native.context(device)
+    m = native.MMQc()
+    table = np.zeros((10 * x.shape[0] // int(rate) if int(rate) > 0 else 0, 3), np.int64) if curve else None
+    ctx.check(ctx.lib.mm_qc_pcm(ctx.ptr, x.ctypes.data_as(ctypes.c_void_p), kind, x.shape[0], ch, int(rate),
+                                int(silence_lsb), int(min_run), ctypes.byref(m),
+                                table.ctypes.data_as(native.c_int64_p) if curve else None), "mm_qc_pcm")
+    return (qc_dict(m), table) if curve else qc_dict(m)
+
+
+def qc_batch_pcm(tracks, rate: int, silence_lsb: int = 1, min_run: int = 3, device: int = 0) -> list:
+    """The delivery QC reports ([qc_dict ...]) of the tracks of a batch (int16 or float32 = int16
+    / 32768 arrays [N] or [N, ch], one rate, channel count and sample type) without mastering
+    them (mm_batch_qc_pcm: one memset, two launches and one read-back whatever their number).
+    Every track receives what qc_pcm gives on it alone."""
+    xs, kind, ch, frames = _album_tracks(tracks, "a batch")
+    n = len(xs)
+    ctx = native.context(device)
+    out = (native.MMQc * n)()
+    ctx.check(ctx.lib.mm_batch_qc_pcm(ctx.ptr, _pointers([x.ctypes.data for x in xs]), kind, frames, n, ch, int(rate),
+                                      int(silence_lsb), int(min_run), out), "mm_batch_qc_pcm")
+    return [qc_dict(m) for m in out]
+
+
+def _batch_qc(ctx: native.Context, d_outs, kind: int, frames, ch: int, rate: int) -> list:
+    """The QC reports of the delivered buffers of a batch or album call, after its level (one
+    mm_batch_qc_device call at the delivered rate, with a master call's parameters)."""
+    n = len(d_outs)
+    out = (native.MMQc * n)()
+    ctx.check(ctx.lib.mm_batch_qc_device(ctx.ptr, _pointers(d_outs), kind, frames, n, ch, int(rate), 1, 3, out),
+              "mm_batch_qc_device")
+    return [qc_dict(m) for m in out]
 
 
 def ceiling_dict(m: native.MMCeiling) -> dict:
@@ -598,6 +696,8 @@ def _finish_info(info: dict, job: "Job", ctx: native.Context) -> dict:
         info["report"] = report_dict(meters(ctx, 1)[0], job.job.lufs_target if job.job.lufs_on else None)
     if end.meter_on & native.REPORT_R128:
         info["r128"] = r128_dict(r128s(ctx, 1)[0])
+    if end.meter_on & native.REPORT_QC:
+        info["qc"] = qc_dict(qcs(ctx, 1)[0])
     return info
 
 
@@ -753,7 +853,9 @@ def master_pcm(pcm: np.ndarray, rate: int, params: dict, out_kind: int = native.
     'report') adds info['r128'] (r128_dict): the EBU R 128 figures of the delivered output.
     params['deliver_lufs'] (in [-40, -5]) levels the delivered output, at either rate, to
     that R 128 integrated loudness with the ceiling held and adds info['level']
-    (level_dict); absent or None, the call is exactly the call without it."""
+    (level_dict); absent or None, the call is exactly the call without it.  params['qc']
+    (truthy; independent of the other reports) adds info['qc'] (qc_dict): the delivery QC report
+    of the delivered output, with silence_lsb 1 and min_run 3."""
     ch = 1 if pcm.ndim == 1 else pcm.shape[1]
     params = dict(params or {})
     report = bool(params.pop("report", False))
@@ -761,8 +863,9 @@ def master_pcm(pcm: np.ndarray, rate: int, params: dict, out_kind: int = native.
     output_rate = params.pop("output_rate", None)
     r128 = bool(params.pop("r128", False))
     deliver_lufs = params.pop("deliver_lufs", None)
+    qc = bool(params.pop("qc", False))
     job = Job(pcm.shape[0], rate, ch, params, out_kind, report=report, ceiling_dbtp=ceiling, output_rate=output_rate,
-              r128=r128, deliver_lufs=deliver_lufs)
+              r128=r128, deliver_lufs=deliver_lufs, qc=qc)
     x, job.job.in_kind = _device_input(pcm, wide=True)
     shape = (job.frames_out,) if ch == 1 else (job.frames_out, ch)
     out = np.empty(shape, np.int16 if out_kind == native.MM_OUT_I16 else np.float32)
@@ -832,7 +935,7 @@ def master_batch(ctx: native.Context, jobs, d_ins, d_outs, with_results: bool = 
 
 
 def master_album(ctx: native.Context, jobs, d_ins, d_outs, deliver_lufs: float, ceiling_dbtp: float | None = None,
-                 output_rate: int | None = None, d_mids=None):
+                 output_rate: int | None = None, d_mids=None, qc: bool = False):
     """Master the tracks of an album as a batch (master_batch) and level the album in place on
     `d_outs` (mm_album_level_device): one static gain for all tracks to `deliver_lufs` (the
     album's EBU R 128 integrated loudness), every track under `ceiling_dbtp`.  The jobs are
@@ -850,7 +953,9 @@ def master_album(ctx: native.Context, jobs, d_ins, d_outs, deliver_lufs: float, 
     `output_rate` and params['output_rate'] stay refused, here and by master_batch.  None or the
     jobs' rate: the call is exactly the call without it.  An `output_rate` without `d_mids` (or
     with another count of them), or a rate pair design.resample_geometry refuses, is a
-    ValueError before any device work."""
+    ValueError before any device work.  `qc=True`: after the level one mm_batch_qc_device call
+    runs over the delivered buffers at the delivered rate, and every entry of the album dict's
+    "tracks" gains "qc" (qc_dict)."""
     jobs = list(jobs)
     _, ch, kind = _delivery_jobs(jobs, "an album", "the album call")
     clu = design.level_clu(deliver_lufs)
@@ -862,6 +967,9 @@ def master_album(ctx: native.Context, jobs, d_ins, d_outs, deliver_lufs: float, 
     album = _album_dict(ctx, len(jobs), bool(C))
     if converted is not None:
         album["resample"] = converted
+    if qc:
+        for t, q in zip(album["tracks"], _batch_qc(ctx, d_outs, kind, frames, ch, rate)):
+            t["qc"] = q
     return res, album
 
 
@@ -885,7 +993,7 @@ def _pointers_of(tensors):
 
 
 def _process_files(name: str, noun: str, words, per_file: bool, deliver, input_paths, output_paths, params: dict,
-                   device: int, output_rate):
+                   device: int, output_rate, qc: bool = False):
     """The files of process_album / process_batch (`name`; their tracks are those of `noun`): the
     params keys and their refusals (`words`: what the target is, which dict carries the reports,
     what the files then are, where the two calls' sentences differ), the files read and planned,
@@ -909,6 +1017,9 @@ def _process_files(name: str, noun: str, words, per_file: bool, deliver, input_p
             raise ValueError(f"{name} takes no params['{key}']: the {carrier} carries the R 128 report and "
                              f"the ceiling of every {done} file (meter one with meter_pcm)")
         params.pop(key, None)
+    if params.pop("qc", None):
+        raise ValueError(f"{name} takes no params['qc']: the keyword qc=True puts every {done} file's QC report "
+                         f"into the {carrier}")
     input_paths, output_paths = list(input_paths), list(output_paths)
     if len(input_paths) != len(output_paths):
         raise ValueError(f"{name} needs one output path for every input path")
@@ -932,7 +1043,7 @@ def _process_files(name: str, noun: str, words, per_file: bool, deliver, input_p
     ctx = native.context(device)
     d_ins, d_mids, d_outs = _batch_buffers(jobs, xs, kind, device, rs)
     res, result, extras, converted = deliver(ctx, jobs, _pointers_of(d_ins), _pointers_of(d_outs), deliver_lufs, ceiling,
-                                             None if rs is None else int(output_rate), _pointers_of(d_mids))
+                                             None if rs is None else int(output_rate), _pointers_of(d_mids), bool(qc))
     infos = []
     for t, (job, r, out, path) in enumerate(zip(jobs, res, d_outs, output_paths)):
         y = out.cpu().numpy()
@@ -944,7 +1055,8 @@ def _process_files(name: str, noun: str, words, per_file: bool, deliver, input_p
     return infos, result
 
 
-def process_album(input_paths, output_paths, params: dict, device: int = 0, output_rate: int | None = None):
+def process_album(input_paths, output_paths, params: dict, device: int = 0, output_rate: int | None = None,
+                  qc: bool = False):
     """Master the WAV files of an album with the same `params` and level them as one album
     (master_album): params['deliver_lufs'] (required) is the album's target, params['ceiling_dbtp']
     (optional) the true-peak ceiling of every track; params['output_format']='f32' writes
@@ -956,17 +1068,18 @@ def process_album(input_paths, output_paths, params: dict, device: int = 0, outp
     other than the files' rate delivers the album at that rate (master_album's `output_rate`):
     the files are written with that rate in their headers and every info dict gains "frames",
     "rate" and "resample" as process's does; None or the files' rate: exactly the call without
-    it.  ValueError for a rate pair design.resample_geometry refuses, before any device work."""
+    it.  ValueError for a rate pair design.resample_geometry refuses, before any device work.
+    `qc=True`: master_album's keyword; every entry of the album dict's "tracks" gains "qc"."""
     def deliver(*call):
         res, album = master_album(*call)
         return res, album, [{}] * len(res), album.get("resample")
 
     return _process_files("process_album", "an album", ("the album's loudness target", "album dict", "levelled"), False,
-                          deliver, input_paths, output_paths, params, device, output_rate)
+                          deliver, input_paths, output_paths, params, device, output_rate, qc)
 
 
 def deliver_batch(ctx: native.Context, jobs, d_ins, d_outs, deliver_lufs, ceiling_dbtp=None,
-                  output_rate: int | None = None, d_mids=None):
+                  output_rate: int | None = None, d_mids=None, qc: bool = False):
     """Master the tracks of a batch (master_batch) and level every track in place on `d_outs` to
     its own target (mm_batch_level_device): `deliver_lufs` and `ceiling_dbtp` are each a scalar
     or one value per job (a ceiling of None: none for that job).  The jobs are planned without
@@ -984,7 +1097,8 @@ def deliver_batch(ctx: native.Context, jobs, d_ins, d_outs, deliver_lufs, ceilin
     and params['output_rate'] stay refused, here and by master_batch.  None or the jobs' rate:
     the call is exactly the call without it.  An `output_rate` without `d_mids` (or with another
     count of them), or a rate pair design.resample_geometry refuses, is a ValueError before any
-    device work."""
+    device work.  `qc=True`: after the level one mm_batch_qc_device call runs over the delivered
+    buffers at the delivered rate, and every level dict gains "qc" (qc_dict)."""
     jobs = list(jobs)
     _, ch, kind = _delivery_jobs(jobs, "a batch to deliver", "the batch call")
     n = len(jobs)
@@ -997,10 +1111,14 @@ def deliver_batch(ctx: native.Context, jobs, d_ins, d_outs, deliver_lufs, ceilin
     if converted is not None:
         for d, r in zip(lvs, converted):
             d["resample"] = r
+    if qc:
+        for d, q in zip(lvs, _batch_qc(ctx, d_outs, kind, frames, ch, rate)):
+            d["qc"] = q
     return res, lvs
 
 
-def process_batch(input_paths, output_paths, params: dict, device: int = 0, output_rate: int | None = None):
+def process_batch(input_paths, output_paths, params: dict, device: int = 0, output_rate: int | None = None,
+                  qc: bool = False):
     """Master the WAV files of a batch with the same `params` and deliver every file to its own
     loudness target (deliver_batch): params['deliver_lufs'] (required) is a scalar or one value
     per file, params['ceiling_dbtp'] (optional) likewise; params['output_format']='f32' writes
@@ -1013,13 +1131,14 @@ def process_batch(input_paths, output_paths, params: dict, device: int = 0, outp
     other than the files' rate delivers every file at that rate (deliver_batch's `output_rate`):
     the files are written with that rate in their headers and every info dict gains "frames",
     "rate" and "resample" as process's does; None or the files' rate: exactly the call without
-    it.  ValueError for a rate pair design.resample_geometry refuses, before any device work."""
+    it.  ValueError for a rate pair design.resample_geometry refuses, before any device work.
+    `qc=True`: deliver_batch's keyword; every file's level dict gains "qc"."""
     def deliver(*call):
         res, lvs = deliver_batch(*call)
         return res, lvs, [{"level": lv} for lv in lvs], [lv.get("resample") for lv in lvs]
 
     return _process_files("process_batch", "a batch to deliver", ("the loudness target of every file", "level dict", "delivered"),
-                          True, deliver, input_paths, output_paths, params, device, output_rate)[0]
+                          True, deliver, input_paths, output_paths, params, device, output_rate, qc)[0]
 
 
 def process(input_path: str, output_path: str, params: dict, device: int = 0, verbose: bool = False) -> dict:
@@ -1037,6 +1156,7 @@ def process(input_path: str, output_path: str, params: dict, device: int = 0, ve
     params['r128'] (truthy) adds info['r128'] (r128_dict), the EBU R 128 figures of the written samples.
     params['deliver_lufs'] levels the written samples to that R 128 integrated loudness under the
     ceiling (info['level'], level_dict).
+    params['qc'] (truthy) adds info['qc'] (qc_dict), the delivery QC report of the written samples.
     Raises ValueError for unreadable/unsupported input and RuntimeError for device
     failures, like the reference (AME:110-113)."""
     params = dict(params or {})
@@ -1046,12 +1166,13 @@ def process(input_path: str, output_path: str, params: dict, device: int = 0, ve
     output_rate = params.pop("output_rate", None)
     r128 = bool(params.pop("r128", False))
     deliver_lufs = params.pop("deliver_lufs", None)
+    qc = bool(params.pop("qc", False))
     kind = native.MM_OUT_F32 if fmt == "f32" else native.MM_OUT_I16
     wi = wav_info(input_path, device)
     if verbose:
         print(f"Loaded {input_path}: {wi.frames} frames @ {wi.rate} Hz")
     job = Job(wi.frames, wi.rate, wi.channels, params, kind, report=report, ceiling_dbtp=ceiling,
-              output_rate=output_rate, r128=r128, deliver_lufs=deliver_lufs)
+              output_rate=output_rate, r128=r128, deliver_lufs=deliver_lufs, qc=qc)
     ctx = native.context(device)
     res = native.MMResult()
     if job.delivery is not None:

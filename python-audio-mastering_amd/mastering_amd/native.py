@@ -87,7 +87,20 @@ class MMR128(ctypes.Structure):
                 ("lra", ctypes.c_double), ("lra_low", ctypes.c_double), ("lra_high", ctypes.c_double)]
 
 
-REPORT_METER, REPORT_R128 = 1, 2  # bits of mm_job.meter_on / mm_delivery.meter_on
+class MMQc(ctypes.Structure):
+    _fields_ = [("frames", ctypes.c_int64), ("channels", ctypes.c_int32), ("rate", ctypes.c_int32),
+                ("hops", ctypes.c_int64), ("silence_lsb", ctypes.c_int32), ("min_run", ctypes.c_int32),
+                ("sum", ctypes.c_int64 * 2), ("sq", ctypes.c_int64 * 2), ("cross", ctypes.c_int64),
+                ("smin", ctypes.c_int32 * 2), ("smax", ctypes.c_int32 * 2), ("or_bits", ctypes.c_uint32 * 2),
+                ("lead_silence", ctypes.c_int64), ("trail_silence", ctypes.c_int64), ("silent_frames", ctypes.c_int64),
+                ("silence_longest", ctypes.c_int64), ("silence_longest_at", ctypes.c_int64),
+                ("clip_samples", ctypes.c_int64 * 2), ("clip_runs", ctypes.c_int64 * 2),
+                ("clip_longest", ctypes.c_int64 * 2), ("clip_longest_at", ctypes.c_int64 * 2),
+                ("corr_windows", ctypes.c_int64), ("corr_negative", ctypes.c_int64), ("corr_min_hop", ctypes.c_int64),
+                ("corr_min", ctypes.c_double)]
+
+
+REPORT_METER, REPORT_R128, REPORT_QC = 1, 2, 4  # bits of mm_job.meter_on / mm_delivery.meter_on
 c_sos_p = ctypes.POINTER(ctypes.c_double * 5)  # const double sos[2][5]
 
 
@@ -155,6 +168,8 @@ EXPORTS = ("mm_create", "mm_destroy", "mm_last_error", "mm_sync", "mm_version", 
            "mm_meter_span",
            "mm_r128_from_hops", "mm_r128_host", "mm_r128_device", "mm_r128_pcm", "mm_op_r128_hops", "mm_r128_span",
            "mm_last_r128",
+           "mm_qc_from_hops", "mm_qc_host", "mm_qc_device", "mm_qc_pcm", "mm_batch_qc_device", "mm_batch_qc_pcm",
+           "mm_qc_span", "mm_last_qc",
            "mm_ceiling_device", "mm_ceiling_pcm", "mm_ceiling_host", "mm_last_ceilings", "mm_ceiling_span",
            "mm_ceiling_max_window",
            "mm_pcm_decode_device", "mm_op_pcm_decode", "mm_pcm_decode_host", "mm_pcm_decode_span",
@@ -263,6 +278,19 @@ def load():
                                  c_double_p, ctypes.c_int64], ctypes.c_int),
             "mm_r128_span": ([], ctypes.c_int),
             "mm_last_r128": ([vp, ctypes.c_int, P(MMR128)], ctypes.c_int),
+            "mm_qc_from_hops": ([c_int64_p, ctypes.c_int64, ctypes.c_int32, P(MMQc)], ctypes.c_int),
+            "mm_qc_host": ([P(ctypes.c_int16), ctypes.c_int64, ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                            P(MMQc), c_int64_p], ctypes.c_int),
+            "mm_qc_device": ([vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int32, ctypes.c_int32,
+                              ctypes.c_int32, P(MMQc), c_int64_p], ctypes.c_int),
+            "mm_qc_pcm": ([vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int32, ctypes.c_int32,
+                           ctypes.c_int32, P(MMQc), c_int64_p], ctypes.c_int),
+            "mm_batch_qc_device": ([vp, P(vp), ctypes.c_int, c_int64_p, ctypes.c_int, ctypes.c_int, ctypes.c_int32,
+                                    ctypes.c_int32, ctypes.c_int32, P(MMQc)], ctypes.c_int),
+            "mm_batch_qc_pcm": ([vp, P(vp), ctypes.c_int, c_int64_p, ctypes.c_int, ctypes.c_int, ctypes.c_int32,
+                                 ctypes.c_int32, ctypes.c_int32, P(MMQc)], ctypes.c_int),
+            "mm_qc_span": ([], ctypes.c_int),
+            "mm_last_qc": ([vp, ctypes.c_int, P(MMQc)], ctypes.c_int),
             "mm_ceiling_device": ([vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int32, ctypes.c_int32,
                                    P(MMCeiling)], ctypes.c_int),
             "mm_ceiling_pcm": ([vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int32, ctypes.c_int32,
