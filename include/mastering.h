@@ -143,7 +143,9 @@ typedef struct mm_job {
        not lufs_on is set.  0: the chain queues exactly what it queued before.  Bit 1
        (MM_REPORT_R128; a new value of this field, the struct is unchanged) adds the R 128
        report of the delivered output (mm_last_r128), which needs kweight.sos and rate.  Bit 2
-       (MM_REPORT_QC; again a new value only) adds its QC report (mm_last_qc), which needs rate. */
+       (MM_REPORT_QC; again a new value only) adds its QC report (mm_last_qc), which needs rate.
+       Bit 3 (MM_REPORT_SPECTRUM; a new value only) adds its spectrum report (mm_last_spectrum,
+       mm_last_spectrum_bins), which needs rate. */
     int32_t meter_on;
     /* true-peak ceiling (ABI 5, the former trailing pad): 0 = off, the chain queues exactly
        what it queued before; else the ceiling C as linear * 2^28, 2^24 <= C <= 2^28
@@ -396,6 +398,51 @@ typedef struct mm_qc {
     double corr_min;
 } mm_qc;
 
+/* The spectrum report of a delivered signal (no reference counterpart): what it looks like over
+ * frequency.  Welch's long-term average spectrum of each channel and the real part of their
+ * cross-spectrum, and from those the 1/3-octave bands with a phase correlation a band.
+ * Signal x[c][n] = the int16 grid / 32768 (MM_OUT_F32 carries it as it is and is converted back
+ * on load, as in mm_qc), 1 or 2 channels, `frames` frames with 0 <= frames < 2^31, rate >= 2000.
+ *   1. Frames.  Length N = 8192 at every rate, hop H = 4096, the periodic Hann window w[n] =
+ *      0.5 - 0.5 cos(2 pi n / N).  Frame j covers [j H, j H + N); F = 0 if frames < N, else
+ *      (frames - N) / H + 1.  A tail that fills no frame is dropped, as the R 128 gating blocks
+ *      drop theirs.  F == 0 is "unmeasurable": n_frames = 0 and every bin, band and total is NaN.
+ *   2. Bins, k = 0 .. N/2, with X_c,j[k] = sum_n w[n] x_c[j H + n] e^(-2 pi i k n / N):
+ *        S_L[k] = (1/F) sum_j |X_L,j[k]|^2,  S_R[k] likewise,
+ *        C[k]   = (1/F) sum_j Re(X_L,j[k] conj X_R,j[k]).
+ *      The bin table is [N/2 + 1][3] double = {S_L, S_R, C}; mono has S_L and zeros beside it.
+ *   3. Bands (mm_spectrum_bands, mm_spectrum_from_bins).  1/3-octave bands with base-10 centres
+ *      f_m = 1000 * 10^(m / 10) and edges f_m * 10^(-1/20), f_m * 10^(+1/20), from the 20 Hz band
+ *      (m = -17) to the last band whose lower edge is below rate / 2; that band ends at rate / 2.
+ *      Bin k is the rectangle [(k - 1/2) rate / N, (k + 1/2) rate / N) clipped to [0, rate / 2]
+ *      and enters a band with the fraction `frac` of that width that lies inside the band: the
+ *      bands partition the power between their outer edges, no band is empty, and no rule asks
+ *      where a bin's centre falls.  With the bin weight c_k = 1 for k = 0 and N/2 and 2 otherwise,
+ *      a band's row is {ms_L, ms_R, ms_C, bins_in_band}: the mean squares sum frac c_k S[k] /
+ *      (N * 3N/8) of S_L, S_R and C (3N/8 = sum w^2: a full-scale sine gives 1/2), and
+ *      bins_in_band = sum frac c_k / 2, the fractions with the half-width bins 0 and N/2 counting
+ *      as the halves they are, which is the band's width * N / rate: the 20 Hz band at 192 kHz
+ *      rests on a fifth of a bin.
+ *   4. total_ms[c] = sum_k c_k S_c[k] / (N * 3N/8), the mean square of the windowed frames.
+ * Levels in dB, the correlation C_b / sqrt(L_b R_b) of a band, mid and side, the roll-off and the
+ * occupied bandwidth derive from these numbers (engine.spectrum_dict).  Figures, not verdicts.
+ * The FFT is float arithmetic: unlike the integer reports the restatements (numpy in the tests,
+ * mm_spectrum_host in double, the kernels in single with double accumulators) agree to a
+ * tolerance, not bit for bit; the GPU path is bit-identical to itself, a batch to single calls
+ * and a master call's report to mm_spectrum_pcm on what that call delivered. */
+typedef struct mm_spectrum {
+    int64_t frames;
+    int32_t channels;
+    int32_t rate;
+    int32_t n_fft;               /* N = 8192                                             */
+    int32_t hop;                 /* H = 4096                                             */
+    int64_t n_frames;            /* F                                                    */
+    int32_t n_bands;             /* rows of the band table at this rate                  */
+    int32_t _pad;
+    double total_ms[2];          /* step 4 (mono: total_ms[1] = 0; F == 0: NaN)          */
+} mm_spectrum;
+#define MM_SPECTRUM_MAX_BANDS 80 /* bands at any int32 rate (38 at 192 kHz, 31 at 44.1 kHz) */
+
 /* Bits of mm_job.meter_on and mm_delivery.meter_on: which reports of the delivered output
  * the master call makes (0 and 1 mean what they meant before the second bit). */
 #define MM_REPORT_METER 1 /* mm_meter (mm_last_meters)                                  */
@@ -403,6 +450,9 @@ typedef struct mm_qc {
                              the job (a delivery: of its `loud` job, which must be set)  */
 #define MM_REPORT_QC 4    /* mm_qc (mm_last_qc) with silence_lsb 1 and min_run 3, at the rate
                              of the job (a delivery: of its `loud` job, which must be set) */
+#define MM_REPORT_SPECTRUM 8 /* mm_spectrum and its bin table (mm_last_spectrum,
+                             mm_last_spectrum_bins), at the rate of the job (a delivery: of
+                             its `loud` job, which must be set)                          */
 
 /* What mm_job cannot carry for a delivery (mm_deliver*): the converter to another rate and,
  * acting on the delivered signal, the loudness target, the ceiling and the report. */
@@ -413,7 +463,9 @@ typedef struct mm_delivery {
     int32_t window;          /* the ceiling's look-ahead at rate_out (frames)        */
     int32_t meter_on;        /* MM_REPORT_METER: meter the delivered output (mm_last_meters);
                                 MM_REPORT_R128: its R 128 report (mm_last_r128);
-                                MM_REPORT_QC: its QC report (mm_last_qc), at loud's rate */
+                                MM_REPORT_QC: its QC report (mm_last_qc), at loud's rate;
+                                MM_REPORT_SPECTRUM: its spectrum report (mm_last_spectrum), at
+                                loud's rate */
     int32_t level_clu;       /* the former pad: 0 = off (nothing new is queued); else the
                                 loudness target in centi-LU, -4000 .. -500 (design.level_clu):
                                 the delivered signal is levelled to it under the ceiling
@@ -481,7 +533,10 @@ int mm_sync(mm_ctx *ctx);
    mm_batch_resample_pcm); and, as a new struct and entry points and a new value of an
    existing field (bit 2 of mm_job.meter_on and mm_delivery.meter_on): mm_qc and the QC report
    (mm_qc_from_hops, mm_qc_host, mm_qc_device, mm_qc_pcm, mm_batch_qc_device, mm_batch_qc_pcm,
-   mm_qc_span, mm_last_qc).  A caller
+   mm_qc_span, mm_last_qc); and, in the same way (bit 3 of the two meter_on fields): mm_spectrum
+   and the spectrum report (mm_spectrum_bands, mm_spectrum_from_bins, mm_spectrum_host,
+   mm_spectrum_device, mm_spectrum_pcm, mm_batch_spectrum_device, mm_batch_spectrum_pcm,
+   mm_last_spectrum, mm_last_spectrum_bins).  A caller
    built against an older header must
    refuse a library whose version differs from its own MM_ABI_VERSION. */
 #define MM_ABI_VERSION 5
@@ -618,6 +673,55 @@ int mm_qc_span(void);
  * or mm_batch_qc_* call on this context: copies min(cap, n) and returns n.  MM_ERR_STATE if
  * that call made none. */
 int mm_last_qc(mm_ctx *ctx, int cap, mm_qc *out);
+
+/* ---- spectrum report ---------------------------------------------------------- */
+/* The 1/3-octave bands at `rate` (step 3 of mm_spectrum; no context, no GPU): returns their
+ * number n and writes min(cap, n) rows {lower edge, centre, upper edge} in Hz into
+ * edges[cap][3].  MM_ERR_ARG for rate < 2000 or a null pointer with cap > 0. */
+int mm_spectrum_bands(int32_t rate, int cap, double *edges);
+/* Steps 3 and 4 on a bin table bins[N/2 + 1][3] in plain C++ in double (no context, no GPU): the
+ * one tail the host restatement and the GPU path end in.  Sets every field of *out (n_frames
+ * from `frames`) and, if `bands` is not NULL, writes n_bands rows {ms_L, ms_R, ms_C,
+ * bins_in_band} into it (room for MM_SPECTRUM_MAX_BANDS rows always suffices).  NaN bins give
+ * NaN figures.  MM_ERR_ARG as mm_spectrum_host. */
+int mm_spectrum_from_bins(const double *bins, int64_t frames, int channels, int32_t rate, mm_spectrum *out, double *bands);
+/* The definition restated sequentially on the host (no context, no GPU), interleaved int16,
+ * with its own radix-2 FFT in double.  bands (may be NULL) as above; bins_out (may be NULL)
+ * receives the bin table [N/2 + 1][3].  MM_ERR_ARG for channels other than 1 or 2, frames
+ * outside [0, 2^31), rate < 2000 or a null pointer. */
+int mm_spectrum_host(const int16_t *pcm, int64_t frames, int channels, int32_t rate, mm_spectrum *out, double *bands,
+                     double *bins_out);
+/* The report of a device-resident signal, interleaved [frames][channels] of `kind` (MM_OUT_I16,
+ * or MM_OUT_F32 = the same PCM / 32768: both give the same bits): the frames launch, the fold
+ * launch and one read-back, then mm_spectrum_from_bins.  bands and bins_out as above.
+ * MM_ERR_ARG as mm_spectrum_host, with words in mm_last_error, and for a bad kind.  The audio
+ * is never altered.  Synchronous on return. */
+int mm_spectrum_device(mm_ctx *ctx, const void *d_pcm, int kind, int64_t frames, int channels, int32_t rate,
+                       mm_spectrum *out, double *bands, double *bins_out);
+/* The same on a host buffer. */
+int mm_spectrum_pcm(mm_ctx *ctx, const void *pcm, int kind, int64_t frames, int channels, int32_t rate, mm_spectrum *out,
+                    double *bands, double *bins_out);
+/* The reports of n device-resident tracks of one kind, channel count and rate, 1 <= n <=
+ * MM_ALBUM_TRACKS: out[t] and track t's bin table are mm_spectrum_device's of track t alone, bit
+ * for bit (no frame of a neighbour is read; a track may begin at any frame offset of a shared
+ * allocation), with two launches and one read-back whatever n.  The results are left behind
+ * mm_last_spectrum and the tables behind mm_last_spectrum_bins; the other results of the
+ * context's last call stay as they are.  MM_ERR_ARG, with words that name the track and before
+ * anything is queued, for a track mm_spectrum_device refuses or a total of 2^31 frames or more.
+ * Synchronous on return. */
+int mm_batch_spectrum_device(mm_ctx *ctx, const void *const *d_pcm, int kind, const int64_t *frames, int n, int channels,
+                             int32_t rate, mm_spectrum *out);
+/* The same on host buffers. */
+int mm_batch_spectrum_pcm(mm_ctx *ctx, const void *const *pcm, int kind, const int64_t *frames, int n, int channels,
+                          int32_t rate, mm_spectrum *out);
+/* The spectrum reports of the last master call (as mm_last_meters; frames 0 and NaN totals: that
+ * job did not ask) or mm_batch_spectrum_* call on this context: copies min(cap, n) and returns
+ * n.  MM_ERR_STATE if that call made none. */
+int mm_last_spectrum(mm_ctx *ctx, int cap, mm_spectrum *out);
+/* The bin table of track `track` of those reports: copies min(cap, N/2 + 1) rows of 3 doubles
+ * and returns N/2 + 1 (NaN rows for a job that did not ask).  MM_ERR_STATE as mm_last_spectrum;
+ * MM_ERR_ARG for a track outside them. */
+int mm_last_spectrum_bins(mm_ctx *ctx, int track, int cap, double *bins);
 
 /* ---- true-peak ceiling ----------------------------------------------------- */
 /* Hold a device-resident signal, interleaved [frames][channels] of `kind` (MM_OUT_I16,

@@ -364,7 +364,8 @@ static int level_device(mm_ctx *c, void *d_pcm, int kind, int64_t frames, int ch
 // the ceiling, or with a loudness target (level_clu, a delivery's) the level that contains
 // it, then the reports, which so measure what is delivered: bit 0 of meter_on the
 // meter, bit 1 the R 128 report (r128.hip) with the K-weighting sections and the rate of
-// `loud`, which the level takes too, bit 2 the QC report (qc.hip) at that rate.  A track that did not ask for what another track of the
+// `loud`, which the level takes too, bit 2 the QC report (qc.hip) at that rate, bit 3 the
+// spectrum report (spectrum.hip) at that rate.  A track that did not ask for what another track of the
 // call asked for leaves a cleared entry.
 static int finish_delivered(mm_ctx *c, void *d_out, int kind, int64_t frames, int channels, int i, int32_t ceiling_q28,
                             int32_t window, int meter_on, const mm_job *loud, int32_t level_clu) {
@@ -389,6 +390,12 @@ static int finish_delivered(mm_ctx *c, void *d_out, int kind, int64_t frames, in
         RET(qc_device(c, d_out, kind, frames, channels, loud->rate, QC_REPORT_LSB, QC_REPORT_RUN, &c->qcs[(size_t)i], nullptr));
     } else if (!c->qcs.empty()) {
         qc_clear(&c->qcs[(size_t)i], 0, channels, 0, QC_REPORT_LSB, QC_REPORT_RUN);
+    }
+    if (meter_on & MM_REPORT_SPECTRUM) {
+        if (!loud) return set_err(c, MM_ERR_ARG, "the spectrum report needs a job with the rate of the delivered signal");
+        RET(spectrum_device(c, d_out, kind, frames, channels, loud->rate, &c->spectra[(size_t)i], &c->spectrum_bins[(size_t)i]));
+    } else if (!c->spectra.empty()) {
+        spectrum_clear(&c->spectra[(size_t)i], channels);
     }
     return MM_OK;
 }

@@ -73,6 +73,12 @@ struct mm_ctx {
     std::vector<mm_r128> r128s;
     // QC reports of the last master call or mm_batch_qc_* call (mm_last_qc; empty: none was made)
     std::vector<mm_qc> qcs;
+    // spectrum reports of the last master call or mm_batch_spectrum_* call and their bin tables
+    // (mm_last_spectrum, mm_last_spectrum_bins; empty: none was made; a table is empty for a track
+    // that did not ask), and whether the kernels' tables are on the device ("spec_tab")
+    std::vector<mm_spectrum> spectra;
+    std::vector<std::vector<double>> spectrum_bins;
+    bool spec_tab_ok = false;
     // ceilings of the last master call (mm_last_ceilings; empty: no job set one)
     std::vector<mm_ceiling> ceilings;
     // levels of the last master call (mm_last_levels; empty: its delivery set no loudness target)

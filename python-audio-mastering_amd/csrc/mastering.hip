@@ -5,7 +5,7 @@
 // both context.h, followed by decode.hip (24/32-bit PCM input).  ops.hip (the
 // per-stage operators) and loudness.hip (the loudness tail, its operator and the
 // time-sharded entry points) follow the chain, before the units that call
-// line_loudness; wav.hip, comm.hip, then pcm16.h, meter.hip, r128.hip, qc.hip, ceiling.hip, level.hip,
+// line_loudness; wav.hip, comm.hip, then pcm16.h, meter.hip, r128.hip, qc.hip, spectrum.hip, ceiling.hip, level.hip,
 // resample.hip (with mm_master* / mm_deliver*: a master call with or without a delivery) and album.hip
 // come at the end.
 #include <rccl/rccl.h>
@@ -952,13 +952,15 @@ static int unit_complete(mm_ctx *c, const Unit &u, mm_result *res) {
     return MM_OK;
 }
 
-// The per-call results of a master call (mm_last_meters, mm_last_r128, mm_last_qc, mm_last_ceilings,
-// mm_last_levels, mm_last_resample): none at its start; before its end one entry for each of
+// The per-call results of a master call (mm_last_meters, mm_last_r128, mm_last_qc, mm_last_spectrum,
+// mm_last_ceilings, mm_last_levels, mm_last_resample): none at its start; before its end one entry for each of
 // the n delivered buffers of what any of them asked for (meter_on: the reports asked for, bits or-ed).
 static void results_reset(mm_ctx *c, int n = 0, bool ceiling = false, int meter_on = 0, bool level = false) {
     c->meters.assign(meter_on & MM_REPORT_METER ? (size_t)n : 0, mm_meter{});
     c->r128s.assign(meter_on & MM_REPORT_R128 ? (size_t)n : 0, mm_r128{});
     c->qcs.assign(meter_on & MM_REPORT_QC ? (size_t)n : 0, mm_qc{});
+    c->spectra.assign(meter_on & MM_REPORT_SPECTRUM ? (size_t)n : 0, mm_spectrum{});
+    c->spectrum_bins.assign(c->spectra.size(), std::vector<double>());
     c->ceilings.assign(ceiling ? (size_t)n : 0, mm_ceiling{});
     c->levels.assign(level ? (size_t)n : 0, mm_level{});
     c->albums.clear();
@@ -1290,6 +1292,7 @@ int mm_kernel_stats(mm_ctx *c, char *names, int names_cap, double *total_ms, int
 #include "meter.hip"
 #include "r128.hip"
 #include "qc.hip"
+#include "spectrum.hip"
 #include "ceiling.hip"
 #include "level.hip"
 #include "resample.hip"

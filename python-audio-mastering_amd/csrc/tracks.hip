@@ -23,6 +23,8 @@
 //   level_tracks_gain  level_gain; head and tail single samples by a track's first workgroup
 //   qc_tracks          the QC report's span kernel (qc.hip: qc_span) over all METER_SPAN spans;
 //                      the fold that follows is qc.hip's own, one workgroup a track
+//   spec_tracks        the spectrum report's frames kernel (spectrum.hip: spec_frames_group) over
+//                      the groups of frames of all tracks (spectrum.h); the fold is spectrum.hip's
 //   resample_tracks    the converter (resample.hip: resample_span) over all RS_SPAN spans of
 //                      output frames; every position relative to the track's own start, the
 //                      statistics into the track's RsDev (mm_batch_resample_*: one memset,
@@ -149,6 +151,16 @@ __global__ void __launch_bounds__(QC_THREADS) qc_tracks_kernel(QcLaunch L) {
     const QcTrack tr = L.tr[t];
     qc_span<CH, T>(static_cast<const T *>(tr.pcm), tr, (int64_t)(blockIdx.x - L.first[t]), L.rate, L.q, L.r,
                    L.rec + L.first[t], L.hops + 3 * tr.hop0);
+}
+
+// the spectrum report's frames kernel (spectrum.hip: spec_frames_group) over the groups of all
+// tracks: a record lands among its track's own, and every frame index is the track's
+template <int CH, typename T>
+__global__ void __launch_bounds__(SPEC_THREADS) spec_tracks_kernel(SpecLaunch L) {
+    const int t = tracks_find(L.first, L.n, blockIdx.x);
+    const SpecTrack tr = L.tr[t];
+    spec_frames_group<CH, T>(static_cast<const T *>(tr.pcm), tr.F, (int64_t)(blockIdx.x - L.first[t]), L.tab,
+                             L.rec + (size_t)blockIdx.x * SPEC_REC);
 }
 
 }  // namespace mm
@@ -575,6 +587,39 @@ int batch_qc_device(mm_ctx *c, const void *const *d_pcm, int kind, const int64_t
     return MM_OK;
 }
 
+// Refuses what is not a batch to take the spectra of, as batch_qc_check does.
+int batch_spectrum_check(mm_ctx *c, const void *const *pcm, int kind, const int64_t *frames, int n, int channels, int rate,
+                         const mm_spectrum *out) {
+    if (n < 1 || n > MM_ALBUM_TRACKS) return set_err(c, MM_ERR_ARG, "batch: %d tracks out of range [1, %d]", n, MM_ALBUM_TRACKS);
+    if (!pcm || !frames || !out) return set_err(c, MM_ERR_ARG, "bad arguments");
+    if (!pcm_kind_ok(kind)) return set_err(c, MM_ERR_ARG, PCM_BAD_KIND, kind);
+    int64_t total = 0;
+    for (int t = 0; t < n; ++t) {
+        if (const char *why = spectrum_refusal(channels, frames[t], rate)) return set_err(c, MM_ERR_ARG, "batch: track %d: %s", t, why);
+        if (frames[t] > 0 && !pcm[t]) return set_err(c, MM_ERR_ARG, "batch: track %d: null pointer", t);
+        total += frames[t];
+        if (total >= SPEC_MAX_FRAMES) return set_err(c, MM_ERR_ARG, "batch: track %d: 2^31 frames or more in all", t);
+    }
+    return MM_OK;
+}
+
+// The spectrum reports of n checked device-resident tracks (synchronous on return):
+// spectrum.hip's spectrum_run with the frames launch over all tracks.  Only c->spectra and the
+// bin tables are set: the other results of the context's last call stay.
+int batch_spectrum_device(mm_ctx *c, const void *const *d_pcm, int kind, const int64_t *frames, int n, int channels, int rate,
+                          mm_spectrum *out) {
+    std::vector<std::vector<double>> bins;
+    RET(spectrum_run(c, d_pcm, frames, n, channels, rate, out, bins, [&](const SpecLaunch &L, uint32_t grid) {
+        return dispatch_pcm(kind, channels, [&](auto ch, auto t) {
+            using T = decltype(t);
+            return launch(c, "spec_tracks", spec_tracks_kernel<ch, T>, dim3(grid), dim3(SPEC_THREADS), 0, L);
+        });
+    }));
+    c->spectra.assign(out, out + n);
+    c->spectrum_bins.swap(bins);
+    return MM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -595,6 +640,24 @@ int mm_batch_qc_pcm(mm_ctx *c, const void *const *pcm, int kind, const int64_t *
     std::vector<void *> d;
     RET(album_upload(c, "batch_qc_in", pcm, kind, frames, n, channels, d));
     return batch_qc_device(c, d.data(), kind, frames, n, channels, rate, silence_lsb, min_run, out);
+}
+
+int mm_batch_spectrum_device(mm_ctx *c, const void *const *d_pcm, int kind, const int64_t *frames, int n, int channels,
+                             int32_t rate, mm_spectrum *out) {
+    if (!c) return MM_ERR_ARG;
+    RET(batch_spectrum_check(c, d_pcm, kind, frames, n, channels, rate, out));
+    HIPCHK(c, hipSetDevice(c->device));
+    return batch_spectrum_device(c, d_pcm, kind, frames, n, channels, rate, out);
+}
+
+int mm_batch_spectrum_pcm(mm_ctx *c, const void *const *pcm, int kind, const int64_t *frames, int n, int channels,
+                          int32_t rate, mm_spectrum *out) {
+    if (!c) return MM_ERR_ARG;
+    RET(batch_spectrum_check(c, pcm, kind, frames, n, channels, rate, out));
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<void *> d;
+    RET(album_upload(c, "batch_spec_in", pcm, kind, frames, n, channels, d));
+    return batch_spectrum_device(c, d.data(), kind, frames, n, channels, rate, out);
 }
 
 int mm_batch_ceiling_device(mm_ctx *c, void *const *d_pcm, int kind, const int64_t *frames, int n, int channels,

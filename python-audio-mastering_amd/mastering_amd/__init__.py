@@ -26,6 +26,13 @@ Public surface (mirrors worker/audio_mastering_engine.py):
                                correlation overall and in 400 ms windows, DC offset, runs of
                                full-scale samples, digital silence at the ends and inside, bit
                                use and dual mono of the delivered output, as exact integers
+  params["spectrum"], spectrum_pcm(pcm, rate), spectrum_batch_pcm(tracks, rate), spectra(ctx),
+  spectrum_bands(rate), occupied_hz(bins, rate, db), deliver_batch / master_album / process_batch /
+  process_album(..., spectrum=True)
+                               the spectrum report (no reference counterpart): Welch's long-term
+                               spectrum of the delivered output on 8192-sample frames, its 1/3-octave
+                               bands with level, mid / side and phase correlation a band, roll-off
+                               and occupied bandwidth
   params["ceiling_dbtp"], ceiling_pcm(pcm, rate, db), ceilings(ctx)
                                the true-peak ceiling (no reference counterpart): an exact
                                look-ahead limiter on the delivered output
@@ -58,7 +65,8 @@ Public surface (mirrors worker/audio_mastering_engine.py):
 from .engine import (EQ_PRESETS, Job, album_level_pcm, album_r128_pcm, ceiling_batch_pcm, ceiling_pcm, ceilings,  # noqa: F401
                      deliver_batch, level_batch_pcm, level_pcm, levels, master_album, master_batch, master_device,
                      master_pcm, meter_pcm, meters, process, process_album, process_batch, qc_batch_pcm, qc_dict, qc_pcm, qcs,
-                     r128_pcm, r128s, resample_batch_pcm, resample_pcm)
+                     r128_pcm, r128s, resample_batch_pcm, resample_pcm, occupied_hz, spectra, spectrum_bands, spectrum_batch_pcm,
+                     spectrum_dict, spectrum_pcm)
 from . import legacy  # noqa: F401
 from .gui_compat import batch_process_audio, process_audio  # noqa: F401
 from .ops import (apply_eq_to_samples, apply_multiband_compressor, apply_peak_filter, apply_saturation,  # noqa: F401
@@ -71,4 +79,5 @@ __all__ = ["legacy", "EQ_PRESETS", "Job", "master_pcm", "master_device", "master
            "float_array_to_audio_segment", "integrated_loudness", "true_peak", "meter_pcm", "meters", "ceiling_pcm",
            "ceilings", "resample_pcm", "r128_pcm", "r128s", "level_pcm", "levels", "album_level_pcm", "album_r128_pcm",
            "master_album", "process_album", "ceiling_batch_pcm", "level_batch_pcm", "deliver_batch", "process_batch",
-           "resample_batch_pcm", "qc_pcm", "qc_batch_pcm", "qc_dict", "qcs"]
+           "resample_batch_pcm", "qc_pcm", "qc_batch_pcm", "qc_dict", "qcs",
+           "spectrum_pcm", "spectrum_batch_pcm", "spectrum_dict", "spectra", "spectrum_bands", "occupied_hz"]

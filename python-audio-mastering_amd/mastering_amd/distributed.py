@@ -356,6 +356,8 @@ def master_time_sharded(backend, plan: RankPlan, params: dict, d_in, d_out, coll
         raise ValueError("the R 128 report needs the whole track: not available on the time-sharded path")
     if params.get("qc"):
         raise ValueError("the QC report needs the whole track: not available on the time-sharded path")
+    if params.get("spectrum"):
+        raise ValueError("the spectrum report needs the whole track: not available on the time-sharded path")
     if params.get("deliver_lufs") is not None:
         raise ValueError("a loudness target (deliver_lufs) needs the whole track: not available on the time-sharded path")
     # checked before any work or collective: the path depends only on the collective's

@@ -69,7 +69,7 @@ class Job:
                  seg_bounds=None, check_length: bool = True, single_chunk: bool = False,
                  crossover=(design.LOW_CROSSOVER, design.HIGH_CROSSOVER), report: bool = False,
                  ceiling_dbtp: float | None = None, output_rate: int | None = None, r128: bool = False,
-                 deliver_lufs: float | None = None, qc: bool = False):
+                 deliver_lufs: float | None = None, qc: bool = False, spectrum: bool = False):
         """`seg_bounds` (time-sharded ranks, distributed.py): this range's loudness
         segment bounds relative to its first frame; the whole-track gating then
         happens on the host after the all-reduce.  `check_length=False` skips
@@ -99,7 +99,9 @@ class Job:
         job with the sections of the delivered rate; not on a time-sharded range or a per-stage
         operator.  `qc`: the delivery QC report of the delivered output (bit 2 of meter_on,
         mm_last_qc; independent of `report` and `r128`); with a delivery the bit moves to it, as
-        `r128` does; not on a time-sharded range, whose rank does not hold the whole track."""
+        `r128` does; not on a time-sharded range, whose rank does not hold the whole track.
+        `spectrum`: the spectrum report of the delivered output (bit 3 of meter_on, mm_last_spectrum;
+        independent of the other three), placed and refused exactly as `qc`."""
         if deliver_lufs is not None and (seg_bounds is not None or single_chunk):
             raise ValueError("a loudness target (deliver_lufs) needs the whole chain: not available on a "
                              "time-sharded range or a per-stage operator")
@@ -111,6 +113,8 @@ class Job:
             raise ValueError("the R 128 report needs the whole track: not available on a time-sharded range")
         if qc and seg_bounds is not None:
             raise ValueError("the QC report needs the whole track: not available on a time-sharded range")
+        if spectrum and seg_bounds is not None:
+            raise ValueError("the spectrum report needs the whole track: not available on a time-sharded range")
         if output_rate is not None and int(output_rate) == int(rate):
             output_rate = None
         if output_rate is not None and (seg_bounds is not None or single_chunk):
@@ -122,6 +126,7 @@ class Job:
         plan_report, report = report, bool(report) and not delivers  # (a delivery's report is planned below)
         plan_r128, r128 = bool(r128), bool(r128) and not delivers
         plan_qc, qc = bool(qc), bool(qc) and not delivers
+        plan_spectrum, spectrum = bool(spectrum), bool(spectrum) and not delivers
         if channels not in (1, 2):
             raise ValueError("only mono and stereo are supported (AME:119,137,152)")
         params = dict(params or {})
@@ -190,7 +195,7 @@ class Job:
         j.comp_max_iters = COMP_MAX_ITERS
         j.comp_super = comp_super_frames(self.rate, self.tile)
         j.meter_on = ((native.REPORT_METER if report else 0) | (native.REPORT_R128 if r128 else 0)
-                      | (native.REPORT_QC if qc else 0))
+                      | (native.REPORT_QC if qc else 0) | (native.REPORT_SPECTRUM if spectrum else 0))
         self.ceiling_dbtp = None if ceiling_dbtp is None else float(ceiling_dbtp)
         j.ceiling_q28 = 0 if ceiling_dbtp is None else design.ceiling_q28(ceiling_dbtp)
         # --- loudness (with `report` alone: the geometry only, for the meter; with `r128`
@@ -225,11 +230,11 @@ class Job:
             d.ceiling_q28, j.ceiling_q28 = j.ceiling_q28, 0
             d.window = design.ceiling_window(out_rate)
             d.meter_on = ((native.REPORT_METER if plan_report else 0) | (native.REPORT_R128 if plan_r128 else 0)
-                          | (native.REPORT_QC if plan_qc else 0))
+                          | (native.REPORT_QC if plan_qc else 0) | (native.REPORT_SPECTRUM if plan_spectrum else 0))
             d.level_clu = level
             # the output's loudness, as meter_pcm plans it, and the sections of the output's rate for the
-            # R 128 report and the level; the QC report reads its rate alone
-            if (plan_report and self.frames_out >= 0.4 * out_rate) or plan_r128 or level or plan_qc:
+            # R 128 report and the level; the QC and spectrum reports read its rate alone
+            if (plan_report and self.frames_out >= 0.4 * out_rate) or plan_r128 or level or plan_qc or plan_spectrum:
                 self._loud = Job(self.frames_out, out_rate, self.channels, {}, single_chunk=True,
                                  report=bool(plan_report), r128=plan_r128 or bool(level))
                 d.loud = ctypes.pointer(self._loud.job)
@@ -458,6 +463,155 @@ def _batch_qc(ctx: native.Context, d_outs, kind: int, frames, ch: int, rate: int
     ctx.check(ctx.lib.mm_batch_qc_device(ctx.ptr, _pointers(d_outs), kind, frames, n, ch, int(rate), 1, 3, out),
               "mm_batch_qc_device")
     return [qc_dict(m) for m in out]
+
+
+def spectrum_bands(rate: int) -> np.ndarray:
+    """The 1/3-octave bands of the spectrum report at `rate` (mm_spectrum_bands; no GPU): an
+    [n_bands, 3] float64 array of lower edge, centre and upper edge in Hz, from the 20 Hz band to
+    the band that rate / 2 clips."""
+    lib = native.load()
+    edges = np.zeros((native.SPECTRUM_MAX_BANDS, 3), np.float64)
+    n = lib.mm_spectrum_bands(int(rate), native.SPECTRUM_MAX_BANDS, edges.ctypes.data_as(native.c_double_p))
+    if n < 0:
+        raise ValueError(f"mm_spectrum_bands failed ({n}): rate below 2000 Hz")
+    return edges[:n].copy()
+
+
+def occupied_hz(bins: np.ndarray, rate: int, threshold_db: float) -> float | None:
+    """The frequency of the highest bin of a spectrum report's bin table whose level, 10 log10(16 S
+    / N^2) with S summed over the channels (0 dB: a full-scale sine on that bin), reaches
+    `threshold_db`; None if no bin does (or the table is NaN)."""
+    N = native.SPECTRUM_N
+    power = 16.0 * (bins[:, 0] + bins[:, 1]) / (N * N)
+    with np.errstate(invalid="ignore"):
+        hit = np.flatnonzero(power >= 10.0 ** (threshold_db / 10.0))
+    return float(hit[-1]) * rate / N if hit.size else None
+
+
+def spectrum_dict(m: native.MMSpectrum, bands: np.ndarray, bins: np.ndarray) -> dict:
+    """An mm_spectrum, its band table [n_bands, 4] (ms L, ms R, ms C, bins_in_band) and its bin
+    table [N/2 + 1, 3] as `info["spectrum"]`: the struct's integers, `total_dbfs` a channel, and
+    under "bands" one dict a band with `centre_hz`, `lo_hz`, `hi_hz`, `bins_in_band`, `level_dbfs` (a
+    list a channel: 10 log10(2 ms), 0 for a full-scale sine), and for stereo `correlation` (C_b /
+    sqrt(L_b R_b), None where a channel is silent), `mid_dbfs` and `side_dbfs` (of (L + R ± 2 C) /
+    4).  Overall: `rolloff_hz` (keys "95", "99", "99.9": the lowest bin frequency below and at which
+    that share of the power of all channels lies) and `occupied_hz` (keys "-60", "-90":
+    occupied_hz at those thresholds).  An unmeasurable signal (n_frames 0) has None throughout.
+    Figures, not verdicts.  No reference counterpart."""
+    ch, rate = int(m.channels), int(m.rate)
+    d = {f: int(getattr(m, f)) for f in ("frames", "channels", "rate", "n_fft", "hop", "n_frames", "n_bands")}
+    measured = d["n_frames"] > 0
+
+    def db(ms):
+        if not measured or math.isnan(ms):
+            return None
+        return 10.0 * math.log10(2.0 * ms) if ms > 0 else -math.inf
+
+    d["total_ms"] = [float(m.total_ms[c]) if measured else None for c in range(ch)]
+    d["total_dbfs"] = [db(float(m.total_ms[c])) for c in range(ch)]
+    d["bands"] = []
+    for (lo, centre, hi), (L, R, C, width) in zip(spectrum_bands(rate) if rate else (), bands):
+        b = {"centre_hz": float(centre), "lo_hz": float(lo), "hi_hz": float(hi), "bins_in_band": float(width),
+             "ms": [float(v) if measured else None for v in (L, R)[:ch]],
+             "level_dbfs": [db(float(v)) for v in (L, R)[:ch]]}
+        if ch == 2:
+            b["cross_ms"] = float(C) if measured else None
+            b["correlation"] = float(C / math.sqrt(L * R)) if measured and L > 0 and R > 0 else None
+            b["mid_dbfs"] = db(max(0.0, float(L + R + 2 * C) / 4.0))
+            b["side_dbfs"] = db(max(0.0, float(L + R - 2 * C) / 4.0))
+        d["bands"].append(b)
+    d["rolloff_hz"] = {"95": None, "99": None, "99.9": None}
+    d["occupied_hz"] = {"-60": None, "-90": None}
+    if measured:
+        N = native.SPECTRUM_N
+        weight = np.full(native.SPECTRUM_BINS, 2.0)
+        weight[0] = weight[-1] = 1.0
+        cum = np.cumsum(weight * (bins[:, 0] + bins[:, 1]))
+        if cum[-1] > 0:
+            for key in d["rolloff_hz"]:
+                k = int(np.searchsorted(cum, float(key) / 100.0 * cum[-1], side="left"))
+                d["rolloff_hz"][key] = min(k, N // 2) * rate / N
+        for key in d["occupied_hz"]:
+            d["occupied_hz"][key] = occupied_hz(bins, rate, float(key))
+    return d
+
+
+def _spectrum_of(m: native.MMSpectrum, bins: np.ndarray) -> dict:
+    """spectrum_dict of a struct and its bin table, the bands by the tail the library ends in."""
+    bands = np.zeros((native.SPECTRUM_MAX_BANDS, 4), np.float64)
+    if m.rate:  # (a job of a batch that did not ask: a cleared struct)
+        rc = native.load().mm_spectrum_from_bins(bins.ctypes.data_as(native.c_double_p), m.frames, m.channels, m.rate,
+                                                 ctypes.byref(native.MMSpectrum()), bands.ctypes.data_as(native.c_double_p))
+        if rc < 0:
+            raise ValueError(f"mm_spectrum_from_bins failed ({rc})")
+    return spectrum_dict(m, bands[:m.n_bands], bins)
+
+
+def spectra(ctx: native.Context, cap: int = native.BATCH_STREAMS) -> list:
+    """The mm_spectrum of every track of the context's last master call or spectrum batch
+    (mm_last_spectrum), in job order (frames 0: that job did not ask).  RuntimeError if that call
+    made none."""
+    return _last(ctx, "mm_last_spectrum", native.MMSpectrum, cap)
+
+
+def spectrum_bins(ctx: native.Context, track: int = 0) -> np.ndarray:
+    """The bin table [N/2 + 1, 3] float64 (S_L, S_R, C) of track `track` of those reports
+    (mm_last_spectrum_bins)."""
+    bins = np.zeros((native.SPECTRUM_BINS, 3), np.float64)
+    ctx.check(ctx.lib.mm_last_spectrum_bins(ctx.ptr, int(track), native.SPECTRUM_BINS, bins.ctypes.data_as(native.c_double_p)),
+              "mm_last_spectrum_bins")
+    return bins
+
+
+def _last_spectra(ctx: native.Context, n: int, curve: bool = False) -> list:
+    """[spectrum_dict ...] (with `curve`: [(spectrum_dict, bin table) ...]) of the context's last reports."""
+    out = []
+    for t, m in enumerate(spectra(ctx, n)):
+        bins = spectrum_bins(ctx, t)
+        out.append((_spectrum_of(m, bins), bins) if curve else _spectrum_of(m, bins))
+    return out
+
+
+def spectrum_pcm(pcm: np.ndarray, rate: int, curve: bool = False, device: int = 0):
+    """The spectrum report (spectrum_dict) of an int16 (or float32 = int16 / 32768) array [N] or
+    [N, ch] without mastering it (mm_spectrum_pcm).  `curve=True` returns (spectrum_dict, the
+    [N/2 + 1, 3] float64 bin table of S_L, S_R and C)."""
+    ch = 1 if pcm.ndim == 1 else pcm.shape[1]
+    x, kind = _out_kind(pcm)
+    ctx = native.context(device)
+    m = native.MMSpectrum()
+    bins = np.zeros((native.SPECTRUM_BINS, 3), np.float64)
+    bands = np.zeros((native.SPECTRUM_MAX_BANDS, 4), np.float64)
+    ctx.check(ctx.lib.mm_spectrum_pcm(ctx.ptr, x.ctypes.data_as(ctypes.c_void_p), kind, x.shape[0], ch, int(rate),
+                                      ctypes.byref(m), bands.ctypes.data_as(native.c_double_p),
+                                      bins.ctypes.data_as(native.c_double_p)), "mm_spectrum_pcm")
+    d = spectrum_dict(m, bands[:m.n_bands], bins)
+    return (d, bins) if curve else d
+
+
+def spectrum_batch_pcm(tracks, rate: int, curve: bool = False, device: int = 0) -> list:
+    """The spectrum reports ([spectrum_dict ...]; with `curve` [(spectrum_dict, bin table) ...]) of
+    the tracks of a batch (int16 or float32 = int16 / 32768 arrays [N] or [N, ch], one rate, channel
+    count and sample type) without mastering them (mm_batch_spectrum_pcm: two launches and one
+    read-back whatever their number).  Every track receives what spectrum_pcm gives on it alone,
+    bit for bit."""
+    xs, kind, ch, frames = _album_tracks(tracks, "a batch")
+    n = len(xs)
+    ctx = native.context(device)
+    out = (native.MMSpectrum * n)()
+    ctx.check(ctx.lib.mm_batch_spectrum_pcm(ctx.ptr, _pointers([x.ctypes.data for x in xs]), kind, frames, n, ch, int(rate),
+                                            out), "mm_batch_spectrum_pcm")
+    return _last_spectra(ctx, n, curve)
+
+
+def _batch_spectrum(ctx: native.Context, d_outs, kind: int, frames, ch: int, rate: int, curve: bool = False) -> list:
+    """The spectrum reports of the delivered buffers of a batch or album call, after its level (one
+    mm_batch_spectrum_device call at the delivered rate)."""
+    n = len(d_outs)
+    out = (native.MMSpectrum * n)()
+    ctx.check(ctx.lib.mm_batch_spectrum_device(ctx.ptr, _pointers(d_outs), kind, frames, n, ch, int(rate), out),
+              "mm_batch_spectrum_device")
+    return _last_spectra(ctx, n, curve)
 
 
 def ceiling_dict(m: native.MMCeiling) -> dict:
@@ -698,6 +852,8 @@ def _finish_info(info: dict, job: "Job", ctx: native.Context) -> dict:
         info["r128"] = r128_dict(r128s(ctx, 1)[0])
     if end.meter_on & native.REPORT_QC:
         info["qc"] = qc_dict(qcs(ctx, 1)[0])
+    if end.meter_on & native.REPORT_SPECTRUM:
+        info["spectrum"] = _last_spectra(ctx, 1)[0]
     return info
 
 
@@ -855,7 +1011,8 @@ def master_pcm(pcm: np.ndarray, rate: int, params: dict, out_kind: int = native.
     that R 128 integrated loudness with the ceiling held and adds info['level']
     (level_dict); absent or None, the call is exactly the call without it.  params['qc']
     (truthy; independent of the other reports) adds info['qc'] (qc_dict): the delivery QC report
-    of the delivered output, with silence_lsb 1 and min_run 3."""
+    of the delivered output, with silence_lsb 1 and min_run 3.  params['spectrum'] (truthy;
+    independent too) adds info['spectrum'] (spectrum_dict): the spectrum report of the delivered output."""
     ch = 1 if pcm.ndim == 1 else pcm.shape[1]
     params = dict(params or {})
     report = bool(params.pop("report", False))
@@ -864,8 +1021,9 @@ def master_pcm(pcm: np.ndarray, rate: int, params: dict, out_kind: int = native.
     r128 = bool(params.pop("r128", False))
     deliver_lufs = params.pop("deliver_lufs", None)
     qc = bool(params.pop("qc", False))
+    spectrum = bool(params.pop("spectrum", False))
     job = Job(pcm.shape[0], rate, ch, params, out_kind, report=report, ceiling_dbtp=ceiling, output_rate=output_rate,
-              r128=r128, deliver_lufs=deliver_lufs, qc=qc)
+              r128=r128, deliver_lufs=deliver_lufs, qc=qc, spectrum=spectrum)
     x, job.job.in_kind = _device_input(pcm, wide=True)
     shape = (job.frames_out,) if ch == 1 else (job.frames_out, ch)
     out = np.empty(shape, np.int16 if out_kind == native.MM_OUT_I16 else np.float32)
@@ -935,7 +1093,7 @@ def master_batch(ctx: native.Context, jobs, d_ins, d_outs, with_results: bool = 
 
 
 def master_album(ctx: native.Context, jobs, d_ins, d_outs, deliver_lufs: float, ceiling_dbtp: float | None = None,
-                 output_rate: int | None = None, d_mids=None, qc: bool = False):
+                 output_rate: int | None = None, d_mids=None, qc: bool = False, spectrum: bool = False):
     """Master the tracks of an album as a batch (master_batch) and level the album in place on
     `d_outs` (mm_album_level_device): one static gain for all tracks to `deliver_lufs` (the
     album's EBU R 128 integrated loudness), every track under `ceiling_dbtp`.  The jobs are
@@ -955,7 +1113,8 @@ def master_album(ctx: native.Context, jobs, d_ins, d_outs, deliver_lufs: float, 
     with another count of them), or a rate pair design.resample_geometry refuses, is a
     ValueError before any device work.  `qc=True`: after the level one mm_batch_qc_device call
     runs over the delivered buffers at the delivered rate, and every entry of the album dict's
-    "tracks" gains "qc" (qc_dict)."""
+    "tracks" gains "qc" (qc_dict).  `spectrum=True`: likewise one mm_batch_spectrum_device call,
+    and every entry gains "spectrum" (spectrum_dict)."""
     jobs = list(jobs)
     _, ch, kind = _delivery_jobs(jobs, "an album", "the album call")
     clu = design.level_clu(deliver_lufs)
@@ -970,6 +1129,9 @@ def master_album(ctx: native.Context, jobs, d_ins, d_outs, deliver_lufs: float, 
     if qc:
         for t, q in zip(album["tracks"], _batch_qc(ctx, d_outs, kind, frames, ch, rate)):
             t["qc"] = q
+    if spectrum:
+        for t, q in zip(album["tracks"], _batch_spectrum(ctx, d_outs, kind, frames, ch, rate)):
+            t["spectrum"] = q
     return res, album
 
 
@@ -993,7 +1155,7 @@ def _pointers_of(tensors):
 
 
 def _process_files(name: str, noun: str, words, per_file: bool, deliver, input_paths, output_paths, params: dict,
-                   device: int, output_rate, qc: bool = False):
+                   device: int, output_rate, qc: bool = False, spectrum: bool = False):
     """The files of process_album / process_batch (`name`; their tracks are those of `noun`): the
     params keys and their refusals (`words`: what the target is, which dict carries the reports,
     what the files then are, where the two calls' sentences differ), the files read and planned,
@@ -1020,6 +1182,9 @@ def _process_files(name: str, noun: str, words, per_file: bool, deliver, input_p
     if params.pop("qc", None):
         raise ValueError(f"{name} takes no params['qc']: the keyword qc=True puts every {done} file's QC report "
                          f"into the {carrier}")
+    if params.pop("spectrum", None):
+        raise ValueError(f"{name} takes no params['spectrum']: the keyword spectrum=True puts every {done} file's "
+                         f"spectrum report into the {carrier}")
     input_paths, output_paths = list(input_paths), list(output_paths)
     if len(input_paths) != len(output_paths):
         raise ValueError(f"{name} needs one output path for every input path")
@@ -1043,7 +1208,8 @@ def _process_files(name: str, noun: str, words, per_file: bool, deliver, input_p
     ctx = native.context(device)
     d_ins, d_mids, d_outs = _batch_buffers(jobs, xs, kind, device, rs)
     res, result, extras, converted = deliver(ctx, jobs, _pointers_of(d_ins), _pointers_of(d_outs), deliver_lufs, ceiling,
-                                             None if rs is None else int(output_rate), _pointers_of(d_mids), bool(qc))
+                                             None if rs is None else int(output_rate), _pointers_of(d_mids), bool(qc),
+                                             bool(spectrum))
     infos = []
     for t, (job, r, out, path) in enumerate(zip(jobs, res, d_outs, output_paths)):
         y = out.cpu().numpy()
@@ -1056,7 +1222,7 @@ def _process_files(name: str, noun: str, words, per_file: bool, deliver, input_p
 
 
 def process_album(input_paths, output_paths, params: dict, device: int = 0, output_rate: int | None = None,
-                  qc: bool = False):
+                  qc: bool = False, spectrum: bool = False):
     """Master the WAV files of an album with the same `params` and level them as one album
     (master_album): params['deliver_lufs'] (required) is the album's target, params['ceiling_dbtp']
     (optional) the true-peak ceiling of every track; params['output_format']='f32' writes
@@ -1069,17 +1235,18 @@ def process_album(input_paths, output_paths, params: dict, device: int = 0, outp
     the files are written with that rate in their headers and every info dict gains "frames",
     "rate" and "resample" as process's does; None or the files' rate: exactly the call without
     it.  ValueError for a rate pair design.resample_geometry refuses, before any device work.
-    `qc=True`: master_album's keyword; every entry of the album dict's "tracks" gains "qc"."""
+    `qc=True`: master_album's keyword; every entry of the album dict's "tracks" gains "qc";
+    `spectrum=True` likewise ("spectrum")."""
     def deliver(*call):
         res, album = master_album(*call)
         return res, album, [{}] * len(res), album.get("resample")
 
     return _process_files("process_album", "an album", ("the album's loudness target", "album dict", "levelled"), False,
-                          deliver, input_paths, output_paths, params, device, output_rate, qc)
+                          deliver, input_paths, output_paths, params, device, output_rate, qc, spectrum)
 
 
 def deliver_batch(ctx: native.Context, jobs, d_ins, d_outs, deliver_lufs, ceiling_dbtp=None,
-                  output_rate: int | None = None, d_mids=None, qc: bool = False):
+                  output_rate: int | None = None, d_mids=None, qc: bool = False, spectrum: bool = False):
     """Master the tracks of a batch (master_batch) and level every track in place on `d_outs` to
     its own target (mm_batch_level_device): `deliver_lufs` and `ceiling_dbtp` are each a scalar
     or one value per job (a ceiling of None: none for that job).  The jobs are planned without
@@ -1098,7 +1265,8 @@ def deliver_batch(ctx: native.Context, jobs, d_ins, d_outs, deliver_lufs, ceilin
     the call is exactly the call without it.  An `output_rate` without `d_mids` (or with another
     count of them), or a rate pair design.resample_geometry refuses, is a ValueError before any
     device work.  `qc=True`: after the level one mm_batch_qc_device call runs over the delivered
-    buffers at the delivered rate, and every level dict gains "qc" (qc_dict)."""
+    buffers at the delivered rate, and every level dict gains "qc" (qc_dict).  `spectrum=True`:
+    likewise one mm_batch_spectrum_device call, and every level dict gains "spectrum" (spectrum_dict)."""
     jobs = list(jobs)
     _, ch, kind = _delivery_jobs(jobs, "a batch to deliver", "the batch call")
     n = len(jobs)
@@ -1114,11 +1282,14 @@ def deliver_batch(ctx: native.Context, jobs, d_ins, d_outs, deliver_lufs, ceilin
     if qc:
         for d, q in zip(lvs, _batch_qc(ctx, d_outs, kind, frames, ch, rate)):
             d["qc"] = q
+    if spectrum:
+        for d, q in zip(lvs, _batch_spectrum(ctx, d_outs, kind, frames, ch, rate)):
+            d["spectrum"] = q
     return res, lvs
 
 
 def process_batch(input_paths, output_paths, params: dict, device: int = 0, output_rate: int | None = None,
-                  qc: bool = False):
+                  qc: bool = False, spectrum: bool = False):
     """Master the WAV files of a batch with the same `params` and deliver every file to its own
     loudness target (deliver_batch): params['deliver_lufs'] (required) is a scalar or one value
     per file, params['ceiling_dbtp'] (optional) likewise; params['output_format']='f32' writes
@@ -1132,13 +1303,14 @@ def process_batch(input_paths, output_paths, params: dict, device: int = 0, outp
     the files are written with that rate in their headers and every info dict gains "frames",
     "rate" and "resample" as process's does; None or the files' rate: exactly the call without
     it.  ValueError for a rate pair design.resample_geometry refuses, before any device work.
-    `qc=True`: deliver_batch's keyword; every file's level dict gains "qc"."""
+    `qc=True`: deliver_batch's keyword; every file's level dict gains "qc"; `spectrum=True` likewise
+    ("spectrum")."""
     def deliver(*call):
         res, lvs = deliver_batch(*call)
         return res, lvs, [{"level": lv} for lv in lvs], [lv.get("resample") for lv in lvs]
 
     return _process_files("process_batch", "a batch to deliver", ("the loudness target of every file", "level dict", "delivered"),
-                          True, deliver, input_paths, output_paths, params, device, output_rate, qc)[0]
+                          True, deliver, input_paths, output_paths, params, device, output_rate, qc, spectrum)[0]
 
 
 def process(input_path: str, output_path: str, params: dict, device: int = 0, verbose: bool = False) -> dict:
@@ -1157,6 +1329,7 @@ def process(input_path: str, output_path: str, params: dict, device: int = 0, ve
     params['deliver_lufs'] levels the written samples to that R 128 integrated loudness under the
     ceiling (info['level'], level_dict).
     params['qc'] (truthy) adds info['qc'] (qc_dict), the delivery QC report of the written samples.
+    params['spectrum'] (truthy) adds info['spectrum'] (spectrum_dict), their spectrum report.
     Raises ValueError for unreadable/unsupported input and RuntimeError for device
     failures, like the reference (AME:110-113)."""
     params = dict(params or {})
@@ -1167,12 +1340,13 @@ def process(input_path: str, output_path: str, params: dict, device: int = 0, ve
     r128 = bool(params.pop("r128", False))
     deliver_lufs = params.pop("deliver_lufs", None)
     qc = bool(params.pop("qc", False))
+    spectrum = bool(params.pop("spectrum", False))
     kind = native.MM_OUT_F32 if fmt == "f32" else native.MM_OUT_I16
     wi = wav_info(input_path, device)
     if verbose:
         print(f"Loaded {input_path}: {wi.frames} frames @ {wi.rate} Hz")
     job = Job(wi.frames, wi.rate, wi.channels, params, kind, report=report, ceiling_dbtp=ceiling,
-              output_rate=output_rate, r128=r128, deliver_lufs=deliver_lufs, qc=qc)
+              output_rate=output_rate, r128=r128, deliver_lufs=deliver_lufs, qc=qc, spectrum=spectrum)
     ctx = native.context(device)
     res = native.MMResult()
     if job.delivery is not None:

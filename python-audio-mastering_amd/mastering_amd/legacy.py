@@ -195,6 +195,8 @@ def master_pcm(pcm: np.ndarray, rate: int, settings: dict, device: int = 0) -> n
         raise ValueError("the R 128 report belongs to the mastering chain's delivery: not available in the legacy profile")
     if settings.get("qc"):
         raise ValueError("the QC report belongs to the mastering chain's delivery: not available in the legacy profile")
+    if settings.get("spectrum"):
+        raise ValueError("the spectrum report belongs to the mastering chain's delivery: not available in the legacy profile")
     if settings.get("deliver_lufs") is not None:
         raise ValueError("a loudness target (deliver_lufs) belongs to the mastering chain's delivery: not available "
                          "in the legacy profile")

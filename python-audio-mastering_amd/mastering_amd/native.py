@@ -100,7 +100,17 @@ class MMQc(ctypes.Structure):
                 ("corr_min", ctypes.c_double)]
 
 
-REPORT_METER, REPORT_R128, REPORT_QC = 1, 2, 4  # bits of mm_job.meter_on / mm_delivery.meter_on
+class MMSpectrum(ctypes.Structure):
+    _fields_ = [("frames", ctypes.c_int64), ("channels", ctypes.c_int32), ("rate", ctypes.c_int32),
+                ("n_fft", ctypes.c_int32), ("hop", ctypes.c_int32), ("n_frames", ctypes.c_int64),
+                ("n_bands", ctypes.c_int32), ("_pad", ctypes.c_int32), ("total_ms", ctypes.c_double * 2)]
+
+
+SPECTRUM_N, SPECTRUM_HOP = 8192, 4096  # mm_spectrum's frame length and hop
+SPECTRUM_BINS = SPECTRUM_N // 2 + 1    # rows of a bin table
+SPECTRUM_MAX_BANDS = 80                # MM_SPECTRUM_MAX_BANDS
+
+REPORT_METER, REPORT_R128, REPORT_QC, REPORT_SPECTRUM = 1, 2, 4, 8  # bits of mm_job.meter_on / mm_delivery.meter_on
 c_sos_p = ctypes.POINTER(ctypes.c_double * 5)  # const double sos[2][5]
 
 
@@ -170,6 +180,8 @@ EXPORTS = ("mm_create", "mm_destroy", "mm_last_error", "mm_sync", "mm_version", 
            "mm_last_r128",
            "mm_qc_from_hops", "mm_qc_host", "mm_qc_device", "mm_qc_pcm", "mm_batch_qc_device", "mm_batch_qc_pcm",
            "mm_qc_span", "mm_last_qc",
+           "mm_spectrum_bands", "mm_spectrum_from_bins", "mm_spectrum_host", "mm_spectrum_device", "mm_spectrum_pcm",
+           "mm_batch_spectrum_device", "mm_batch_spectrum_pcm", "mm_last_spectrum", "mm_last_spectrum_bins",
            "mm_ceiling_device", "mm_ceiling_pcm", "mm_ceiling_host", "mm_last_ceilings", "mm_ceiling_span",
            "mm_ceiling_max_window",
            "mm_pcm_decode_device", "mm_op_pcm_decode", "mm_pcm_decode_host", "mm_pcm_decode_span",
@@ -291,6 +303,21 @@ def load():
                                  ctypes.c_int32, ctypes.c_int32, P(MMQc)], ctypes.c_int),
             "mm_qc_span": ([], ctypes.c_int),
             "mm_last_qc": ([vp, ctypes.c_int, P(MMQc)], ctypes.c_int),
+            "mm_spectrum_bands": ([ctypes.c_int32, ctypes.c_int, c_double_p], ctypes.c_int),
+            "mm_spectrum_from_bins": ([c_double_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int32, P(MMSpectrum), c_double_p],
+                                      ctypes.c_int),
+            "mm_spectrum_host": ([P(ctypes.c_int16), ctypes.c_int64, ctypes.c_int, ctypes.c_int32, P(MMSpectrum), c_double_p,
+                                  c_double_p], ctypes.c_int),
+            "mm_spectrum_device": ([vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int32, P(MMSpectrum),
+                                    c_double_p, c_double_p], ctypes.c_int),
+            "mm_spectrum_pcm": ([vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int32, P(MMSpectrum),
+                                 c_double_p, c_double_p], ctypes.c_int),
+            "mm_batch_spectrum_device": ([vp, P(vp), ctypes.c_int, c_int64_p, ctypes.c_int, ctypes.c_int, ctypes.c_int32,
+                                          P(MMSpectrum)], ctypes.c_int),
+            "mm_batch_spectrum_pcm": ([vp, P(vp), ctypes.c_int, c_int64_p, ctypes.c_int, ctypes.c_int, ctypes.c_int32,
+                                       P(MMSpectrum)], ctypes.c_int),
+            "mm_last_spectrum": ([vp, ctypes.c_int, P(MMSpectrum)], ctypes.c_int),
+            "mm_last_spectrum_bins": ([vp, ctypes.c_int, ctypes.c_int, c_double_p], ctypes.c_int),
             "mm_ceiling_device": ([vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int32, ctypes.c_int32,
                                    P(MMCeiling)], ctypes.c_int),
             "mm_ceiling_pcm": ([vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int32, ctypes.c_int32,
