@@ -822,8 +822,8 @@ int mm_level_span(void);
  * pointer, n outside [1, MM_ALBUM_TRACKS], a negative hop count or rate < 2000. */
 int mm_r128_album_from_hops(const double *e, const int64_t *track_hops, int n, int32_t rate, mm_r128 *out);
 /* The album level restated in plain C++ on the host (no context, no GPU), in place on n
- * interleaved int16 tracks: mm_ceiling_host, mm_r128_host and the gain composed as
- * mm_level_host composes them.  *album and track_r128[n] (may be NULL) describe what was
+ * interleaved int16 tracks: mm_ceiling_host, mm_r128_host and the gain in the one loop that
+ * mm_level_host runs with n = 1.  *album and track_r128[n] (may be NULL) describe what was
  * delivered; track_ceil[n] (may be NULL) receives, when C != 0, every track's final
  * mm_ceiling call at C.  MM_ERR_ARG as mm_album_level_device. */
 int mm_album_level_host(int16_t *const *pcm, const int64_t *frames, int n, int channels, int32_t rate,
@@ -848,7 +848,9 @@ int mm_op_r128_album_hops(mm_ctx *ctx, const void *const *pcm, int kind, const i
 /* Level n device-resident tracks in place as one album (the album level above) to level_clu
  * under ceiling_q28 (0: none; window as mm_ceiling_device).  The mm_level and the album's
  * mm_r128 are left behind mm_last_album, the per-track reports of the delivered tracks behind
- * mm_last_r128 and, with a ceiling, mm_last_ceilings (n each, in track order).  MM_ERR_ARG,
+ * mm_last_r128 and, with a ceiling, mm_last_ceilings (n each, in track order).  The ceilings,
+ * the gain and the measurement of a pass are each launched once over all tracks, as the batch
+ * level's are, so the launches and synchronisations of a pass do not depend on n.  MM_ERR_ARG,
  * with words in mm_last_error, before anything is queued and with the context still usable,
  * for n outside [1, MM_ALBUM_TRACKS], a track mm_level_device refuses, level_clu outside
  * [-4000, -500] or a total of 2^31 frames or more.  Synchronous on return. */

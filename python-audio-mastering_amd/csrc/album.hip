@@ -3,15 +3,16 @@
 // (the album R 128 figures and the album level in include/mastering.h).  Loudness differences
 // between the tracks are kept.  No reference counterpart.
 //
-// Nothing is decided here that level.hip does not decide: level_first, level_step and
-// level_record run on the album's integrated loudness and the tracks' ceilings, the kept
-// sources are level_keep's, the gain is level_gain's (on the host level_gain_host's) and the
-// ceiling ceiling_device's, one call a track.  What is new is the measuring pass: r128.hip's album kernels K-weight
-// every track in ONE launch and reduce all hops in one more, with one read-back of the
-// album's hop energies and the look-back's error word, where n calls of r128_hops pay n
-// synchronisations a pass.  The album's figures come from the pooled windows of the tracks
-// (no window spans two tracks) through r128_figures, the tail mm_r128_from_hops ends in; the
-// per-track reports come from the same hop energies, so a pass measures once.
+// Two things live here.  The pooled measurement: r128.hip's album kernels K-weight every track
+// in ONE launch and reduce all hops in one more, with one read-back of the hop energies and the
+// look-back's error word, where n calls of r128_hops pay n synchronisations.  Pooled figures
+// come from the windows of the tracks back to back (no window spans two tracks) through
+// r128_figures, the tail mm_r128_from_hops ends in; the per-track reports come from the same hop
+// energies, so a pass measures once.  Every pass of the device's level loop (tracks.hip:
+// level_groups_device) measures this way, whatever it levels.  And the host restatement of the
+// level: level_group_host, the one pass loop in plain C++ over one group of n tracks, behind
+// mm_level_host (n = 1) and mm_album_level_host.  Nothing is decided in it that level.hip does
+// not decide.  The album's device entries are in tracks.hip, behind the driver.
 //
 // Included at the end of mastering.hip after level.hip.
 
@@ -64,27 +65,31 @@ int album_check(mm_ctx *c, const void *const *pcm, int kind, const int64_t *fram
     return MM_OK;
 }
 
-// The segmented measuring pass of one album, laid out once a call: every track on a
-// workgroup boundary, its hops at hop0[t] of the album's.
+// The segmented measuring pass over n tracks, laid out once: every track on a workgroup
+// boundary, its hops at hop0[t] of the pass's.  The host tables live as long as the pass, so
+// their uploads need no synchronisation of their own: album_pass_hops, which every prepared
+// pass with a hop runs, ends in one.
 struct AlbumPass {
     R128AlbumArgs a{};
     unsigned nblk = 0;
     int kind = 0, channels = 0;
     std::vector<int64_t> hops;  // [n] H_t
+    std::vector<R128Track> tracks;
+    std::vector<int> wg_track;
     double *d_e = nullptr;
 };
 
-// Lays the pass out and uploads its tables (synchronous: the host tables are transient).
+// Lays the pass out and queues the uploads of its tables.
 int album_pass_prepare(mm_ctx *c, const void *const *d_pcm, int kind, const int64_t *frames, int n, int channels, int rate,
                        const double sos[2][5], AlbumPass &p) {
-    std::vector<R128Track> tracks((size_t)n);
-    std::vector<int> wg_track;
     int64_t wg = 0, hop = 0;
     p.hops.resize((size_t)n);
+    p.tracks.resize((size_t)n);
+    p.wg_track.clear();
     for (int t = 0; t < n; ++t) {
         const int64_t G = (frames[t] + R128_TILE - 1) / R128_TILE, nwg = (G + LB_THREADS - 1) / LB_THREADS;
-        tracks[(size_t)t] = R128Track{d_pcm[t], frames[t], wg, hop};
-        wg_track.insert(wg_track.end(), (size_t)nwg, t);
+        p.tracks[(size_t)t] = R128Track{d_pcm[t], frames[t], wg, hop};
+        p.wg_track.insert(p.wg_track.end(), (size_t)nwg, t);
         p.hops[(size_t)t] = 10 * frames[t] / rate;
         wg += nwg;
         hop += p.hops[(size_t)t];
@@ -96,7 +101,7 @@ int album_pass_prepare(mm_ctx *c, const void *const *d_pcm, int kind, const int6
     p.a.rate = rate;
     p.a.H = hop;
     memcpy(p.a.sos, sos, sizeof p.a.sos);
-    if (hop == 0) return MM_OK;  // nothing to measure: nothing is launched
+    if (hop == 0) return MM_OK;  // nothing to measure: nothing is queued
     R128Track *d_tracks;
     int *d_wg;
     RET(get_buf(c, "album_tracks", (size_t)n, &d_tracks));
@@ -104,9 +109,8 @@ int album_pass_prepare(mm_ctx *c, const void *const *d_pcm, int kind, const int6
     RET(get_buf(c, "album_part", (size_t)wg * LB_THREADS * 2, &p.a.part));
     RET(get_buf(c, "album_part_hop", (size_t)wg * LB_THREADS, &p.a.part_hop));
     RET(get_buf(c, "album_hops", (size_t)hop, &p.d_e));
-    HIPCHK(c, hipMemcpyAsync(d_tracks, tracks.data(), (size_t)n * sizeof(R128Track), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_wg, wg_track.data(), (size_t)wg * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_tracks, p.tracks.data(), (size_t)n * sizeof(R128Track), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_wg, p.wg_track.data(), (size_t)wg * sizeof(int), hipMemcpyHostToDevice, c->stream));
     p.a.tracks = d_tracks;
     p.a.wg_track = d_wg;
     return MM_OK;
@@ -137,16 +141,15 @@ int album_pass_hops(mm_ctx *c, const AlbumPass &p, std::vector<double> &e) {
     return MM_OK;
 }
 
-// The album's report and every track's from one measurement's hop energies.
-void album_reports(const std::vector<double> &e, const AlbumPass &p, const int64_t *frames, mm_r128 *album,
-                   std::vector<mm_r128> &tracks) {
-    const int n = p.a.n;
-    tracks.resize((size_t)n);
-    album_from_hops(e.data(), p.hops.data(), n, p.a.rate, album, tracks.data());
-    album->channels = p.channels;
+// The pooled report of n tracks and every track's own from their hop energies `e` (track after
+// track, hops[t] of track t): the figures of album_from_hops with the frames and channels filled in.
+void album_reports(const double *e, const int64_t *hops, const int64_t *frames, int n, int rate, int channels, mm_r128 *album,
+                   mm_r128 *tracks) {
+    album_from_hops(e, hops, n, rate, album, tracks);
+    album->channels = channels;
     for (int t = 0; t < n; ++t) {
-        tracks[(size_t)t].frames = frames[t];
-        tracks[(size_t)t].channels = p.channels;
+        tracks[t].frames = frames[t];
+        tracks[t].channels = channels;
         album->frames += frames[t];
     }
 }
@@ -157,97 +160,13 @@ int album_r128_device(mm_ctx *c, const void *const *d_pcm, int kind, const int64
                       const double sos[2][5], mm_r128 *out) {
     AlbumPass pass;
     std::vector<double> e;
-    std::vector<mm_r128> tr;
+    std::vector<mm_r128> tr((size_t)n);
     RET(album_pass_prepare(c, d_pcm, kind, frames, n, channels, rate, sos, pass));
     RET(album_pass_hops(c, pass, e));
-    album_reports(e, pass, frames, out, tr);
+    album_reports(e.data(), pass.hops.data(), frames, n, rate, channels, out, tr.data());
     results_reset(c);
     c->r128s = tr;
     return MM_OK;
-}
-
-// The album level on device-resident tracks, in place (synchronous on return).  Arguments
-// already checked.  The results go behind mm_last_album, mm_last_r128 and mm_last_ceilings.
-int album_level_device(mm_ctx *c, void *const *d_pcm, int kind, const int64_t *frames, int n, int channels, int32_t rate,
-                       const double sos[2][5], int32_t level_clu, int32_t C, int32_t W) {
-    results_reset(c);
-    mm_level out;
-    mm_r128 album;
-    int64_t total = 0;
-    for (int t = 0; t < n; ++t) total += frames[t];
-    level_clear(&out, total, channels, rate, level_clu, C, W);
-    AlbumPass pass;
-    std::vector<double> e;
-    std::vector<mm_r128> tr;
-    std::vector<mm_ceiling> ceil((size_t)n), ce_in((size_t)n);
-    RET(album_pass_prepare(c, d_pcm, kind, frames, n, channels, rate, sos, pass));
-    auto measure = [&]() -> int {
-        RET(album_pass_hops(c, pass, e));
-        album_reports(e, pass, frames, &album, tr);
-        return MM_OK;
-    };
-    auto done = [&]() {
-        c->r128s = tr;
-        if (C) c->ceilings = ceil;
-        c->albums.assign(1, out);
-        c->album_r128s.assign(1, album);
-        return MM_OK;
-    };
-    const int nc = C ? n : 0;  // ceilings a pass
-    RET(measure());
-    out.source_lufs = album.integrated;
-    if (!std::isfinite(album.integrated)) {  // no window, or silence: every track only gets its ceiling
-        for (int t = 0; t < nc; ++t) RET(ceiling_device(c, d_pcm[t], kind, frames[t], channels, C, W, &ceil[(size_t)t]));
-        level_unmeasurable(&out, ceil.data(), nc);
-        if (C) RET(measure());  // the reports describe what is delivered
-        return done();
-    }
-    std::vector<char *> src;
-    std::vector<size_t> bytes((size_t)n);
-    for (int t = 0; t < n; ++t) bytes[(size_t)t] = pcm_bytes(kind, frames[t], channels);
-    LevelDev *st;
-    std::vector<LevelDev> hs((size_t)n);
-    RET(level_keep(c, "album_src", d_pcm, kind, frames, n, channels, src));
-    RET(get_buf(c, "album_res", (size_t)n, &st));
-    auto results = [&]() -> int {  // every slot of the pass, behind the next synchronisation
-        HIPCHK(c, hipMemcpyAsync(hs.data(), st, (size_t)n * sizeof(LevelDev), hipMemcpyDeviceToHost, c->stream));
-        return MM_OK;
-    };
-    int32_t g_peak = LEVEL_GMAX;
-    if (C) {
-        for (int t = 0; t < n; ++t)
-            if (bytes[(size_t)t]) HIPCHK(c, hipMemcpyAsync(src[(size_t)t], d_pcm[t], bytes[(size_t)t], hipMemcpyDeviceToDevice, c->stream));
-    } else {  // the copies through the kernel at ONE (the identity): they bring max_t max |s_t|
-        HIPCHK(c, hipMemsetAsync(st, 0, (size_t)n * sizeof(LevelDev), c->stream));
-        for (int t = 0; t < n; ++t) RET(level_gain_queue(c, d_pcm[t], src[(size_t)t], kind, frames[t] * channels, LEVEL_ONE, st + t));
-        RET(results());
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        unsigned peak = 0;
-        for (const LevelDev &h : hs) peak = std::max(peak, h.peak);
-        g_peak = level_peak_cap((int32_t)peak);
-    }
-    int32_t g = level_first(&out);
-    while (g) {
-        const LevelStep s = level_step(C, g, g_peak);
-        HIPCHK(c, hipMemsetAsync(st, 0, (size_t)n * sizeof(LevelDev), c->stream));
-        for (int t = 0; t < n; ++t) {
-            const int64_t ns = frames[t] * channels;
-            if (!s.boost) {
-                RET(level_gain_queue(c, src[(size_t)t], d_pcm[t], kind, ns, s.g, st + t));
-                continue;
-            }
-            if (bytes[(size_t)t]) HIPCHK(c, hipMemcpyAsync(d_pcm[t], src[(size_t)t], bytes[(size_t)t], hipMemcpyDeviceToDevice, c->stream));
-            RET(ceiling_device(c, d_pcm[t], kind, frames[t], channels, s.C_inner, W, &ce_in[(size_t)t]));
-            RET(level_gain_queue(c, d_pcm[t], d_pcm[t], kind, ns, s.g, st + t));
-        }
-        RET(results());
-        for (int t = 0; t < nc; ++t) RET(ceiling_device(c, d_pcm[t], kind, frames[t], channels, C, W, &ceil[(size_t)t]));
-        RET(measure());
-        int64_t clipped = 0;
-        for (const LevelDev &h : hs) clipped += (int64_t)h.clipped;
-        g = level_record(&out, s, album.integrated, clipped, ceil.data(), ce_in.data(), nc);
-    }
-    return done();
 }
 
 // n host tracks into one context buffer, each on a 16-byte boundary: their device pointers
@@ -278,30 +197,13 @@ int batch_download(mm_ctx *c, void *const *pcm, const std::vector<void *> &d, in
     return MM_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int mm_r128_album_from_hops(const double *e, const int64_t *track_hops, int n, int32_t rate, mm_r128 *out) {
-    if (!out || !track_hops || n < 1 || n > ALBUM_TRACKS || rate < R128_MIN_RATE) return MM_ERR_ARG;
-    int64_t total = 0;
-    for (int t = 0; t < n; ++t) {
-        if (track_hops[t] < 0) return MM_ERR_ARG;
-        total += track_hops[t];
-    }
-    if (total > 0 && !e) return MM_ERR_ARG;
-    album_from_hops(e, track_hops, n, rate, out);
-    return MM_OK;
-}
-
-// The definition restated in plain C++ on the host (no context, no GPU), in place on
-// interleaved int16: mm_ceiling_host, mm_r128_host (for its hops) and the gain, composed as
-// mm_level_host composes them, under the same rule.
-int mm_album_level_host(int16_t *const *pcm, const int64_t *frames, int n, int channels, int32_t rate,
-                        const double sos[2][5], int32_t level_clu, int32_t C, int32_t W, mm_level *out, mm_r128 *album,
-                        mm_r128 *track_r128, mm_ceiling *track_ceil) {
-    if (!out || !album) return MM_ERR_ARG;
-    RET(album_check(nullptr, (const void *const *)pcm, MM_OUT_I16, frames, n, channels, rate, sos, level_clu, C, W, true));
+// The level of one group of n tracks restated in plain C++ on the host (no context, no GPU), in
+// place on interleaved int16: mm_ceiling_host, mm_r128_host (for its hops), album_from_hops and
+// the gain under level.hip's rule, the host's one loop over passes.  Arguments already checked.
+// album: the group's pooled report; track_r128, track_ceil (may be null, [n]): every track's own.
+int level_group_host(int16_t *const *pcm, const int64_t *frames, int n, int channels, int32_t rate, const double sos[2][5],
+                     int32_t level_clu, int32_t C, int32_t W, mm_level *out, mm_r128 *album, mm_r128 *track_r128,
+                     mm_ceiling *track_ceil) {
     int64_t total = 0;
     std::vector<int64_t> hops((size_t)n);
     for (int t = 0; t < n; ++t) {
@@ -366,6 +268,39 @@ int mm_album_level_host(int16_t *const *pcm, const int64_t *frames, int n, int c
     return done();
 }
 
+}  // namespace
+
+extern "C" {
+
+int mm_r128_album_from_hops(const double *e, const int64_t *track_hops, int n, int32_t rate, mm_r128 *out) {
+    if (!out || !track_hops || n < 1 || n > ALBUM_TRACKS || rate < R128_MIN_RATE) return MM_ERR_ARG;
+    int64_t total = 0;
+    for (int t = 0; t < n; ++t) {
+        if (track_hops[t] < 0) return MM_ERR_ARG;
+        total += track_hops[t];
+    }
+    if (total > 0 && !e) return MM_ERR_ARG;
+    album_from_hops(e, track_hops, n, rate, out);
+    return MM_OK;
+}
+
+// The definition restated in plain C++ on the host: a single track is a group of one.
+int mm_level_host(int16_t *pcm, int64_t frames, int channels, int32_t rate, const double sos[2][5], int32_t level_clu,
+                  int32_t C, int32_t W, mm_level *out, mm_ceiling *ceil_out) {
+    if (!out || !sos || (frames > 0 && !pcm) || level_bad_args(frames, channels, rate, level_clu, C, W)) return MM_ERR_ARG;
+    mm_r128 pooled;
+    return level_group_host(&pcm, &frames, 1, channels, rate, sos, level_clu, C, W, out, &pooled, nullptr, ceil_out);
+}
+
+// And an album a group of its n tracks.
+int mm_album_level_host(int16_t *const *pcm, const int64_t *frames, int n, int channels, int32_t rate,
+                        const double sos[2][5], int32_t level_clu, int32_t C, int32_t W, mm_level *out, mm_r128 *album,
+                        mm_r128 *track_r128, mm_ceiling *track_ceil) {
+    if (!out || !album) return MM_ERR_ARG;
+    RET(album_check(nullptr, (const void *const *)pcm, MM_OUT_I16, frames, n, channels, rate, sos, level_clu, C, W, true));
+    return level_group_host(pcm, frames, n, channels, rate, sos, level_clu, C, W, out, album, track_r128, track_ceil);
+}
+
 int mm_album_r128_device(mm_ctx *c, const void *const *d_pcm, int kind, const int64_t *frames, int n, int channels,
                          int32_t rate, const double sos[2][5], mm_r128 *out) {
     if (!c) return MM_ERR_ARG;
@@ -400,25 +335,6 @@ int mm_op_r128_album_hops(mm_ctx *c, const void *const *pcm, int kind, const int
     RET(album_pass_hops(c, pass, e));
     for (size_t i = 0; i < std::min(e.size(), (size_t)cap); ++i) hops_host[i] = e[i];
     return (int)std::min<size_t>(e.size(), (size_t)INT32_MAX);
-}
-
-int mm_album_level_device(mm_ctx *c, void *const *d_pcm, int kind, const int64_t *frames, int n, int channels, int32_t rate,
-                          const double sos[2][5], int32_t level_clu, int32_t ceiling_q28, int32_t window) {
-    if (!c) return MM_ERR_ARG;
-    RET(album_check(c, d_pcm, kind, frames, n, channels, rate, sos, level_clu, ceiling_q28, window, true));
-    HIPCHK(c, hipSetDevice(c->device));
-    return album_level_device(c, d_pcm, kind, frames, n, channels, rate, sos, level_clu, ceiling_q28, window);
-}
-
-int mm_album_level_pcm(mm_ctx *c, void *const *pcm, int kind, const int64_t *frames, int n, int channels, int32_t rate,
-                       const double sos[2][5], int32_t level_clu, int32_t ceiling_q28, int32_t window) {
-    if (!c) return MM_ERR_ARG;
-    RET(album_check(c, pcm, kind, frames, n, channels, rate, sos, level_clu, ceiling_q28, window, true));
-    HIPCHK(c, hipSetDevice(c->device));
-    std::vector<void *> d;
-    RET(album_upload(c, "album_io", pcm, kind, frames, n, channels, d));
-    RET(album_level_device(c, d.data(), kind, frames, n, channels, rate, sos, level_clu, ceiling_q28, window));
-    return batch_download(c, pcm, d, kind, frames, n, channels, nullptr);
 }
 
 int mm_last_album(mm_ctx *c, mm_level *level, mm_r128 *album) {

@@ -18,8 +18,7 @@
 // are integers combined with min / max / add: nothing depends on the launch geometry.
 //
 // Included at the end of mastering.hip after pcm16.h (frames, wave reductions, refusals,
-// dispatch_pcm) and meter.hip (the oversampler, tp_host, meter_launch, meter_device).  The
-// end of a master call, finish_delivered, is here: the ceiling, then the report.
+// dispatch_pcm) and meter.hip (the oversampler, tp_host, meter_launch, meter_device).
 
 namespace mm {
 
@@ -352,51 +351,6 @@ static int ceiling_device(mm_ctx *c, void *d_pcm, int kind, int64_t frames, int 
         out->tp_out_q28 = linked(hm);
     }
     resolve_events(c);
-    return MM_OK;
-}
-
-// level.hip: the level of a delivered signal, which contains its ceiling
-static int level_device(mm_ctx *c, void *d_pcm, int kind, int64_t frames, int channels, int32_t rate,
-                        const double sos[2][5], int32_t level_clu, int32_t C, int32_t W, mm_level *out,
-                        mm_ceiling *ceil_out);
-
-// The end of a master call for delivered buffer i (results_reset sized the call's results):
-// the ceiling, or with a loudness target (level_clu, a delivery's) the level that contains
-// it, then the reports, which so measure what is delivered: bit 0 of meter_on the
-// meter, bit 1 the R 128 report (r128.hip) with the K-weighting sections and the rate of
-// `loud`, which the level takes too, bit 2 the QC report (qc.hip) at that rate, bit 3 the
-// spectrum report (spectrum.hip) at that rate.  A track that did not ask for what another track of the
-// call asked for leaves a cleared entry.
-static int finish_delivered(mm_ctx *c, void *d_out, int kind, int64_t frames, int channels, int i, int32_t ceiling_q28,
-                            int32_t window, int meter_on, const mm_job *loud, int32_t level_clu) {
-    if (level_clu) {
-        if (!loud || loud->kweight.nsec != 2)
-            return set_err(c, MM_ERR_ARG, "a loudness target needs a job with the K-weighting sections (kweight.sos)");
-        RET(level_device(c, d_out, kind, frames, channels, loud->rate, loud->kweight.sos, level_clu, ceiling_q28, window,
-                         &c->levels[(size_t)i], ceiling_q28 ? &c->ceilings[(size_t)i] : nullptr));
-    } else if (ceiling_q28) RET(ceiling_device(c, d_out, kind, frames, channels, ceiling_q28, window, &c->ceilings[(size_t)i]));
-    else if (!c->ceilings.empty()) c->ceilings[(size_t)i].channels = channels;
-    if (meter_on & MM_REPORT_METER) RET(meter_device(c, d_out, kind, frames, channels, loud, &c->meters[(size_t)i]));
-    else if (!c->meters.empty()) meter_clear(&c->meters[(size_t)i], 0, channels);
-    if (meter_on & MM_REPORT_R128) {
-        if (!loud || loud->kweight.nsec != 2)
-            return set_err(c, MM_ERR_ARG, "the R 128 report needs a job with the K-weighting sections (kweight.sos)");
-        RET(r128_device(c, d_out, kind, frames, channels, loud->rate, loud->kweight.sos, &c->r128s[(size_t)i]));
-    } else if (!c->r128s.empty()) {
-        r128_clear(&c->r128s[(size_t)i], 0, channels, 0);
-    }
-    if (meter_on & MM_REPORT_QC) {
-        if (!loud) return set_err(c, MM_ERR_ARG, "the QC report needs a job with the rate of the delivered signal");
-        RET(qc_device(c, d_out, kind, frames, channels, loud->rate, QC_REPORT_LSB, QC_REPORT_RUN, &c->qcs[(size_t)i], nullptr));
-    } else if (!c->qcs.empty()) {
-        qc_clear(&c->qcs[(size_t)i], 0, channels, 0, QC_REPORT_LSB, QC_REPORT_RUN);
-    }
-    if (meter_on & MM_REPORT_SPECTRUM) {
-        if (!loud) return set_err(c, MM_ERR_ARG, "the spectrum report needs a job with the rate of the delivered signal");
-        RET(spectrum_device(c, d_out, kind, frames, channels, loud->rate, &c->spectra[(size_t)i], &c->spectrum_bins[(size_t)i]));
-    } else if (!c->spectra.empty()) {
-        spectrum_clear(&c->spectra[(size_t)i], channels);
-    }
     return MM_OK;
 }
 

@@ -2,17 +2,18 @@
 // gain that makes the DELIVERED signal read the target on a BS.1770-4 meter with the
 // ceiling held (mm_level in include/mastering.h).  No reference counterpart.  The stage is a
 // short secant search on the one number a delivery spec names: every pass forms its
-// candidate from the kept source (so rounding never accumulates), limits it with
-// ceiling.hip's ceiling_device and measures it with r128.hip's r128_device, both unchanged;
-// the rule (level_first, level_step, level_record / level_next, level_unmeasurable) is plain
-// C++ shared with the host restatement mm_level_host, which composes mm_ceiling_host and
-// mm_r128_host the same way, and with the album's and the batch's drivers (album.hip,
-// tracks.hip): a driver keeps only which launches or host calls form a pass.  The gain's
-// launch geometry (level_gain_geom) and the kept-source layout (level_keep) are here for all
-// of them too.
+// candidate from the kept source (so rounding never accumulates), limits it with the ceiling
+// and measures it with the R 128 meter.  This file owns what is decided and the gain's body;
+// it drives nothing.  The rule (level_first, level_step, level_record / level_next,
+// level_unmeasurable, level_peak_cap) is plain C++ with exactly two callers: the device's one
+// pass loop, level_groups_device in tracks.hip, and the host's, level_group_host in album.hip,
+// which composes mm_ceiling_host, mm_r128_host and level_gain_host the same way.  A single
+// track, a batch and an album are groups of tracks to both (tracks.hip: LevelGroup).  The
+// gain's launch geometry (level_gain_geom) and the kept-source layout (level_keep) are here too.
 //
-// One new kernel, level_gain: s' = clip((s * g + 2^15) >> 16) on the samples as one mono
-// line, src -> dst (src == dst allowed).  It is a streaming kernel (2 or 4 bytes in, as
+// The gain, level_gain_span: s' = clip((s * g + 2^15) >> 16) on the samples as one mono
+// line, src -> dst (src == dst allowed).  Its kernel is tracks.hip's level_tracks_gain, which
+// runs it over the spans of n tracks (n = 1 included).  It is a streaming body (2 or 4 bytes in, as
 // many out, a handful of integer operations a sample), so all that matters is the width of
 // its memory instructions: a lane moves 16 bytes a load and a store (8 int16 or 4 f32), a
 // wave one contiguous 1 KiB run, and a workgroup LEVEL_SPAN samples in LEVEL_SPAN / (256
@@ -21,15 +22,15 @@
 // workgroup a span: spans of 16384 samples ran 30 us on the 5-minute track where 8192 ran 35
 // and 4096 more, and a persistent grid-stride form no faster.  The vectors are aligned to the DESTINATION: the up to 15 bytes before
 // the first 16-byte boundary of dst and what is left after the last whole vector are
-// single samples (lanes of workgroup 0), so any sample count and any sample-aligned view
+// single samples (lanes of a signal's workgroup 0), so any sample count and any sample-aligned view
 // is right; when src does not share dst's offset within 16 bytes, the loads alone fall back
 // to single samples (level_keep places a source copy at the delivered buffer's offset, so
-// the chain never takes that path).  `clipped` is summed and the peak maximised over a
+// the level never takes that path).  `clipped` is summed and the peak maximised over a
 // wave by shuffles and folded with at most one integer atomic a wave: no result depends on
 // the launch geometry.
 //
-// Included at the end of mastering.hip after r128.hip and ceiling.hip, whose
-// finish_delivered runs a level in the place of the plain ceiling call (it contains it).
+// Included at the end of mastering.hip after r128.hip and ceiling.hip and before album.hip and
+// tracks.hip.
 
 namespace mm {
 
@@ -71,7 +72,7 @@ struct LevelVec<float> {
 
 // Workgroup b takes the whole vectors [b * VPB, (b + 1) * VPB) of dst + head; workgroup 0
 // also the `head` samples before them (lanes 0 ..) and the tail after the last (lanes 64 ..).
-// (`blk`: the workgroup's index within the signal; tracks.hip runs the same body over n signals.)
+// (`blk`: the workgroup's index within the signal; tracks.hip runs the body over n signals.)
 template <typename T>
 __device__ __forceinline__ void level_gain_span(const T *__restrict__ src, T *__restrict__ dst, int64_t n, int head,
                                                 int src_vec, int g, LevelDev *st, unsigned blk) {
@@ -124,13 +125,6 @@ __device__ __forceinline__ void level_gain_span(const T *__restrict__ src, T *__
         if (clipped) atomicAdd(&st->clipped, (unsigned long long)clipped);
         if ((unsigned)peak > __atomic_load_n(&st->peak, __ATOMIC_RELAXED)) atomicMax(&st->peak, (unsigned)peak);
     }
-}
-
-template <typename T>
-__global__ void __launch_bounds__(LEVEL_THREADS) level_gain_kernel(const T *__restrict__ src, T *__restrict__ dst,
-                                                                    int64_t n, int head, int src_vec, int g,
-                                                                    LevelDev *st) {
-    level_gain_span<T>(src, dst, n, head, src_vec, g, st, blockIdx.x);
 }
 
 }  // namespace mm
@@ -305,106 +299,11 @@ int level_keep(mm_ctx *c, const char *name, void *const *d_pcm, int kind, const 
     return MM_OK;
 }
 
-// src -> dst by g, queued; the statistics are folded into *st, which the caller zeroed on the
-// stream (album.hip zeroes one array of them once a pass)
-int level_gain_queue(mm_ctx *c, const void *src, void *dst, int kind, int64_t n, int32_t g, LevelDev *st) {
-    if (n == 0) return MM_OK;
-    const LevelGeom geo = level_gain_geom(src, dst, kind, n);
-    const dim3 grid((unsigned)geo.wgs), block(LEVEL_THREADS);
-    return dispatch_pcm(kind, 1, [&](auto, auto t) {  // (pointwise: the samples as one mono line)
-        using T = decltype(t);
-        return launch(c, "level_gain", level_gain_kernel<T>, grid, block, 0, static_cast<const T *>(src), static_cast<T *>(dst), n,
-                      geo.head, geo.src_vec, (int)g, st);
-    });
-}
-
-// the same with *st zeroed here
-int level_gain_launch(mm_ctx *c, const void *src, void *dst, int kind, int64_t n, int32_t g, LevelDev *st) {
-    HIPCHK(c, hipMemsetAsync(st, 0, sizeof(LevelDev), c->stream));
-    return level_gain_queue(c, src, dst, kind, n, g, st);
-}
-
 }  // namespace
-
-// The level on a device-resident signal, in place (synchronous on return).  ceil_out (may be
-// null) receives the final mm_ceiling call at C on the delivered pass when C != 0.
-static int level_device(mm_ctx *c, void *d_pcm, int kind, int64_t frames, int channels, int32_t rate,
-                        const double sos[2][5], int32_t level_clu, int32_t C, int32_t W, mm_level *out,
-                        mm_ceiling *ceil_out) {
-    if (!c || !out || !sos || (frames > 0 && !d_pcm)) return set_err(c, MM_ERR_ARG, "bad arguments");
-    if (!pcm_kind_ok(kind)) return set_err(c, MM_ERR_ARG, PCM_BAD_KIND, kind);
-    if (const char *why = level_bad_args(frames, channels, rate, level_clu, C, W)) return set_err(c, MM_ERR_ARG, "level: %s", why);
-    level_clear(out, frames, channels, rate, level_clu, C, W);
-    mm_ceiling ce_own, ce_in;
-    mm_ceiling *ce = ceil_out ? ceil_out : &ce_own;
-    mm_r128 r;
-    RET(r128_device(c, d_pcm, kind, frames, channels, rate, sos, &r));
-    out->source_lufs = r.integrated;
-    const int nc = C ? 1 : 0;  // ceilings a pass
-    if (!std::isfinite(r.integrated)) {
-        if (C) RET(ceiling_device(c, d_pcm, kind, frames, channels, C, W, ce));
-        level_unmeasurable(out, ce, nc);
-        return MM_OK;
-    }
-    const int64_t n = frames * channels;
-    const size_t bytes = pcm_bytes(kind, frames, channels);
-    std::vector<char *> kept;
-    LevelDev *st, hs{};
-    RET(level_keep(c, "level_src", &d_pcm, kind, &frames, 1, channels, kept));
-    RET(get_buf(c, "level_res", 1, &st));
-    char *src = kept[0];
-    int32_t g_peak = LEVEL_GMAX;
-    if (C) {
-        HIPCHK(c, hipMemcpyAsync(src, d_pcm, bytes, hipMemcpyDeviceToDevice, c->stream));
-    } else {  // the copy through the kernel at ONE (the identity): it brings max |s|
-        RET(level_gain_launch(c, d_pcm, src, kind, n, LEVEL_ONE, st));
-        HIPCHK(c, hipMemcpyAsync(&hs, st, sizeof hs, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        g_peak = level_peak_cap((int32_t)hs.peak);
-    }
-    int32_t g = level_first(out);
-    while (g) {
-        const LevelStep s = level_step(C, g, g_peak);
-        if (s.boost) {
-            HIPCHK(c, hipMemcpyAsync(d_pcm, src, bytes, hipMemcpyDeviceToDevice, c->stream));
-            RET(ceiling_device(c, d_pcm, kind, frames, channels, s.C_inner, W, &ce_in));
-            RET(level_gain_launch(c, d_pcm, d_pcm, kind, n, s.g, st));
-        } else {
-            RET(level_gain_launch(c, src, d_pcm, kind, n, s.g, st));
-        }
-        HIPCHK(c, hipMemcpyAsync(&hs, st, sizeof hs, hipMemcpyDeviceToHost, c->stream));  // (behind the next sync)
-        if (C) RET(ceiling_device(c, d_pcm, kind, frames, channels, C, W, ce));
-        RET(r128_device(c, d_pcm, kind, frames, channels, rate, sos, &r));
-        g = level_record(out, s, r.integrated, (int64_t)hs.clipped, ce, &ce_in, nc);
-    }
-    return MM_OK;
-}
 
 extern "C" {
 
 int mm_level_span(void) { return LEVEL_SPAN; }
-
-int mm_level_device(mm_ctx *c, void *d_pcm, int kind, int64_t frames, int channels, int32_t rate, const double sos[2][5],
-                    int32_t level_clu, int32_t ceiling_q28, int32_t window, mm_level *out, mm_ceiling *ceil_out) {
-    if (!c) return MM_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    return level_device(c, d_pcm, kind, frames, channels, rate, sos, level_clu, ceiling_q28, window, out, ceil_out);
-}
-
-int mm_level_pcm(mm_ctx *c, void *pcm, int kind, int64_t frames, int channels, int32_t rate, const double sos[2][5],
-                 int32_t level_clu, int32_t ceiling_q28, int32_t window, mm_level *out, mm_ceiling *ceil_out) {
-    if (!c) return MM_ERR_ARG;
-    if (!out || !sos || (frames > 0 && !pcm)) return set_err(c, MM_ERR_ARG, "bad arguments");
-    if (!pcm_kind_ok(kind)) return set_err(c, MM_ERR_ARG, PCM_BAD_KIND, kind);
-    if (const char *why = level_bad_args(frames, channels, rate, level_clu, ceiling_q28, window))
-        return set_err(c, MM_ERR_ARG, "level: %s", why);
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t bytes = pcm_bytes(kind, frames, channels);
-    char *dio;
-    RET(pcm_upload(c, "level_io", pcm, bytes, &dio));
-    RET(level_device(c, dio, kind, frames, channels, rate, sos, level_clu, ceiling_q28, window, out, ceil_out));
-    return pcm_download(c, pcm, dio, bytes);
-}
 
 int mm_last_levels(mm_ctx *c, int cap, mm_level *out) {
     if (!c || cap < 0 || (cap > 0 && !out)) return set_err(c, MM_ERR_ARG, "bad arguments");
@@ -412,75 +311,6 @@ int mm_last_levels(mm_ctx *c, int cap, mm_level *out) {
     const int n = (int)c->levels.size();
     for (int i = 0; i < std::min(n, cap); ++i) out[i] = c->levels[(size_t)i];
     return n;
-}
-
-// The gain kernel alone on host buffers (a per-stage operator, for parity checks): n samples
-// of `kind` by g, through device views that start src_off and dst_off samples (0 .. 7) past
-// a 16-byte boundary; dst_off < 0: in place (src == dst).
-int mm_op_level_gain(mm_ctx *c, const void *in, int kind, int64_t n, int src_off, int dst_off, int32_t g, void *out_pcm,
-                     int64_t *clipped, int32_t *peak) {
-    if (!c) return MM_ERR_ARG;
-    if (!clipped || !peak || (n > 0 && (!in || !out_pcm)) || n < 0 || n >= (int64_t)1 << 32 || src_off < 0 || src_off > 7 ||
-        dst_off > 7)
-        return set_err(c, MM_ERR_ARG, "bad arguments");
-    if (!pcm_kind_ok(kind)) return set_err(c, MM_ERR_ARG, PCM_BAD_KIND, kind);
-    if (g < LEVEL_GMIN || g > LEVEL_GMAX) return set_err(c, MM_ERR_ARG, "level: gain_q16 out of range [2^8, 2^21]");
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t sb = pcm_sample_bytes(kind), bytes = (size_t)n * sb;
-    char *a, *b;
-    LevelDev *st, hs{};
-    RET(get_buf(c, "level_op_a", bytes + 64, &a));
-    RET(get_buf(c, "level_op_b", bytes + 64, &b));
-    RET(get_buf(c, "level_res", 1, &st));
-    char *src = a + (size_t)src_off * sb, *dst = dst_off < 0 ? src : b + (size_t)dst_off * sb;
-    if (bytes) HIPCHK(c, hipMemcpyAsync(src, in, bytes, hipMemcpyHostToDevice, c->stream));
-    RET(level_gain_launch(c, src, dst, kind, n, g, st));
-    HIPCHK(c, hipMemcpyAsync(&hs, st, sizeof hs, hipMemcpyDeviceToHost, c->stream));
-    RET(pcm_download(c, out_pcm, dst, bytes));
-    resolve_events(c);
-    *clipped = (int64_t)hs.clipped;
-    *peak = (int32_t)hs.peak;
-    return MM_OK;
-}
-
-// The definition restated in plain C++ on the host (no context, no GPU), in place on
-// interleaved int16: mm_ceiling_host, mm_r128_host and the gain, under the same rule.
-int mm_level_host(int16_t *pcm, int64_t frames, int channels, int32_t rate, const double sos[2][5], int32_t level_clu,
-                  int32_t C, int32_t W, mm_level *out, mm_ceiling *ceil_out) {
-    if (!out || !sos || (frames > 0 && !pcm) || level_bad_args(frames, channels, rate, level_clu, C, W)) return MM_ERR_ARG;
-    level_clear(out, frames, channels, rate, level_clu, C, W);
-    mm_ceiling ce_own, ce_in;
-    mm_ceiling *ce = ceil_out ? ceil_out : &ce_own;
-    mm_r128 r;
-    RET(mm_r128_host(pcm, frames, channels, rate, sos, nullptr, 0, &r));
-    out->source_lufs = r.integrated;
-    const int nc = C ? 1 : 0;  // ceilings a pass
-    if (!std::isfinite(r.integrated)) {
-        if (C) RET(mm_ceiling_host(pcm, frames, channels, C, W, ce));
-        level_unmeasurable(out, ce, nc);
-        return MM_OK;
-    }
-    const size_t n = (size_t)(frames * channels);
-    const std::vector<int16_t> src(pcm, pcm + n);
-    int32_t peak = 0;
-    for (size_t i = 0; i < n; ++i) peak = std::max(peak, std::abs((int32_t)src[i]));
-    const int32_t g_peak = level_peak_cap(peak);
-    int32_t g = level_first(out);
-    while (g) {
-        const LevelStep s = level_step(C, g, g_peak);
-        int64_t clipped = 0;
-        if (s.boost) {
-            memcpy(pcm, src.data(), n * sizeof(int16_t));
-            RET(mm_ceiling_host(pcm, frames, channels, s.C_inner, W, &ce_in));
-            level_gain_host(pcm, pcm, n, s.g, clipped);
-        } else {
-            level_gain_host(src.data(), pcm, n, s.g, clipped);
-        }
-        if (C) RET(mm_ceiling_host(pcm, frames, channels, C, W, ce));
-        RET(mm_r128_host(pcm, frames, channels, rate, sos, nullptr, 0, &r));
-        g = level_record(out, s, r.integrated, clipped, ce, &ce_in, nc);
-    }
-    return MM_OK;
 }
 
 }  // extern "C"

@@ -27,7 +27,7 @@
 // The grid is the need grid of tracks.h (tracks_need_spans: it counts m in [0, frames + 11), so
 // a track's last span may hold no frame and then writes an empty record, the operator's
 // identity).  Included at the end of mastering.hip after r128.hip (r128_bound, r128_hop_of: the
-// hops are the R 128 report's) and before ceiling.hip, whose finish_delivered runs the report
+// hops are the R 128 report's) and before tracks.hip, whose finish_delivered runs the report
 // beside the other two; the launch over many tracks (qc_tracks_kernel) is in tracks.hip.
 
 namespace mm {

@@ -26,7 +26,7 @@
 // so the stores are at most two to a bank and a lane's reads of its own frames none.
 //
 // Included at the end of mastering.hip (one translation unit) after meter.hip, before
-// ceiling.hip, whose finish_delivered runs the report next to the meter.
+// tracks.hip, whose finish_delivered runs the report next to the meter.
 
 namespace mm {
 

@@ -29,9 +29,9 @@
 // spec_fold: one thread a (track, bin, column) sums the track's records in group order and
 // divides by F (no frame: NaN); stream order gives it the records.
 //
-// Included at the end of mastering.hip after qc.hip and before ceiling.hip, whose
-// finish_delivered runs the report beside the other three; the launch over many tracks
-// (spec_tracks_kernel) is in tracks.hip.
+// Included at the end of mastering.hip after qc.hip and before tracks.hip, whose
+// finish_delivered runs the report beside the other three and which holds the launch over
+// many tracks (spec_tracks_kernel).
 
 #include "spectrum.h"
 

@@ -150,6 +150,19 @@ def album_h():
     return [stepped_noise(3 * RATE, RATE, 2), pink(2, 2, -9, 1), pink(0.3, 2, -10, 5), pink(1.5, 2, -24, 2)]
 
 
+def album_fates():
+    """(tracks, rate, target, C, W): a stereo album at 8 kHz that boosts, with tracks of different
+    fates in one pass: 2 s that the inner ceiling limits, 2 s that it does not touch, a track
+    three frames longer than one span of the ceiling, 0.3 s (no window of its own) and an empty
+    track.  test_the_fates_album_is_what_its_name_says asserts all of that on the host."""
+    from mastering_amd import native
+    from mastering_amd.synth import pink_noise_pcm16
+    rate, n = 8000, native.load().mm_ceiling_span() + 3
+    tracks = [pink(2, 2, -14, 31, rate), pink(2, 2, -40, 32, rate), pink_noise_pcm16(n, rate, 2, track=33, level_dbfs=-16.0),
+              pink(0.3, 2, -14, 34, rate), np.zeros((0, 2), np.int16)]
+    return tracks, rate, -10.0, q28(-1.0), 40
+
+
 def case_inputs():
     """name -> (tracks, target, C, W, status, passes): the outcomes are those of the rule's numpy
     prototype on these albums (asserted on ref_album_level itself in `refs`)."""
@@ -353,6 +366,28 @@ def test_one_track_is_mm_level_host(cases):
         assert np.array_equal(got[0], want) and bytes(m) == bytes(m1)
         assert (bytes(ce[0]) == bytes(ce1)) if C else True
         assert bytes(alb) == bytes(tr[0])
+
+
+def test_the_fates_album_is_what_its_name_says():
+    """Every pass boosts behind the limiter; the inner ceiling of every pass lies under the true
+    peaks of tracks 0, 2 and 3 and above that of track 1; and no decision of the rule is nearer
+    than 1e-3 LU to its threshold."""
+    from test_meter import ref_meter
+    from mastering_amd import native
+    tracks, rate, T, C, W = album_fates()
+    got, m, alb, tr, ce = host_album_level(tracks, rate, T, C, W)
+    assert (m.status, m.passes) == (STATUS["reached"], 3) and m.limited_frames > 0
+    assert [len(t) for t in tracks] == [2 * rate, 2 * rate, native.load().mm_ceiling_span() + 3, 3 * rate // 10, 0]
+    tp = [max(ref_meter(t)["true_peak_q28"]) for t in tracks[:4]]
+    for k in range(m.passes):
+        g = m.pass_gain_q16[k]
+        inner = ((C - GUARD) << 16) // g
+        assert g > ONE and tp[1] <= inner < min(tp[0], tp[2], tp[3]), k
+        assert abs(abs(T - m.pass_lufs[k]) - TOL) >= 1e-3, k
+        if k:
+            d = [20.0 * math.log10(m.pass_gain_q16[j] / 65536.0) for j in (k - 1, k)]
+            assert abs((m.pass_lufs[k] - m.pass_lufs[k - 1]) / (d[1] - d[0]) - SMIN) >= 0.01, k
+    assert all(c.tp_out_q28 <= C for c in ce) and ce[4].frames == 0 and math.isnan(tr[3].integrated)
 
 
 def test_host_refusals():

@@ -135,6 +135,39 @@ def test_album_level_pcm_is_the_host_restatement(host_results, name):
     assert all(np.array_equal(a, g) for a, g in zip(again, got)) and d2 == d  # a second run: bit for bit
 
 
+@pytest.fixture(scope="module")
+def fates_host():
+    """mm_album_level_host of the album of tests/test_album.py's album_fates (shared, read-only);
+    what the album is made of and its decision margins are asserted there."""
+    from test_album import album_fates
+    tracks, rate, T, C, W = album_fates()
+    return (tracks, rate, T, C, W), host_album_level(tracks, rate, T, C, W)
+
+
+@pytest.mark.parametrize("f32", [False, True], ids=["i16", "f32"])
+def test_tracks_of_different_fates_in_one_pass(fates_host, f32):
+    """Through the segmented ceilings in one launch: a track the inner ceiling limits, one it
+    does not touch (ceil_tracks_peak skips it), one with a span seam three frames before its
+    end, one without a window of its own and an empty one, in every pass of a boosting album."""
+    from mastering_amd import album_level_pcm, engine, native
+    from test_gpu_level import as_kind, to_i16
+    (tracks, rate, T, C, W), (want, hm, halb, htr, hce) = fates_host
+    got, d = album_level_pcm([as_kind(t, f32) for t in tracks], rate, T, ceiling_dbtp=-1.0, window=W)
+    assert all(np.array_equal(to_i16(g), w) for g, w in zip(got, want))
+    hd = engine.level_dict(hm)
+    for k in ("frames", "channels", "rate", "target_clu", "ceiling_q28", "window", "passes", "gain_q16", "min_gain_q16",
+              "clipped", "limited_frames", "status", "pass_gain_q16"):
+        assert d[k] == hd[k], k
+    for a, b in zip(d["pass_lufs"], hd["pass_lufs"]):
+        assert abs(a - b) <= 1e-6
+    assert abs(d["source_lufs"] - hd["source_lufs"]) <= 1e-6 and abs(d["loudness"] - hd["loudness"]) <= 1e-6
+    check_r128(d["r128"], halb)
+    assert len(d["tracks"]) == len(tracks) == 5
+    for t, rep in enumerate(d["tracks"]):
+        check_r128(rep["r128"], htr[t])
+        assert all(rep["ceiling"][f] == getattr(hce[t], f) for f, _ in native.MMCeiling._fields_), t
+
+
 @pytest.mark.parametrize("name,track", [("cut", 0), ("boost-2", 0), ("no-ceiling", 2), ("unmeasurable", 0)])
 def test_one_track_is_level_pcm(host_results, name, track):
     from mastering_amd import album_level_pcm, engine
@@ -162,11 +195,9 @@ def test_the_balance_between_the_tracks_is_kept(host_results):
     assert abs(before[0] - before[1]) > 5.0  # (a loud opener and a quiet interlude)
 
 
-def test_launch_count(host_results):
-    """One segmented measuring launch for the source and one a pass; the per-track reports come
-    from the same hop energies, so the single-track pass is never launched."""
+def album_launches(tracks, T, W):
+    """(album dict, kernel name -> launches) of one warm album_level_pcm under -1 dBTP."""
     from mastering_amd import album_level_pcm, native
-    (tracks, T, C, W), *_ = host_results["boost-3"]
     ctx = native.context(0)
     album_level_pcm(tracks, RATE, T, ceiling_dbtp=-1.0, window=W)  # (buffers and tables in place)
     ctx.timing(True)
@@ -176,11 +207,32 @@ def test_launch_count(host_results):
         after = ctx.kernel_stats()
     finally:
         ctx.timing(False)
-    count = lambda k: after.get(k, (0.0, 0))[1] - before.get(k, (0.0, 0))[1]  # noqa: E731
+    return d, {k: v[1] - before.get(k, (0.0, 0))[1] for k, v in after.items() if v[1] != before.get(k, (0.0, 0))[1]}
+
+
+def test_launch_count(host_results):
+    """One segmented measuring launch for the source and one a pass; the per-track reports come
+    from the same hop energies, so the single-track pass is never launched.  Nor is any other
+    kernel of the single-track path, and no kernel is launched more often for more tracks: the
+    album with every track listed twice launches what the album launches."""
+    (tracks, T, C, W), *_ = host_results["boost-3"]
+    d, count = album_launches(tracks, T, W)
     assert d["passes"] == 3
-    assert count("r128_album_kweight") == d["passes"] + 1 == count("r128_album_reduce")
-    assert count("r128_kweight") == 0  # (at most the per-track reports of the delivered pass: here none)
-    assert count("level_gain") == d["passes"] * len(tracks)
+    assert count["r128_album_kweight"] == d["passes"] + 1 == count["r128_album_reduce"]
+    for k in ("level_gain", "ceil_need", "ceil_apply", "ceil_trim", "meter_i16", "r128_kweight"):
+        assert k not in count, k
+    d2, count2 = album_launches(tracks + tracks, T, W)
+    assert d2["passes"] == d["passes"]  # (twice the album has the album's loudness)
+    print(count)
+    for k in ("r128_album_kweight", "r128_album_reduce", "level_tracks_gain", "ceil_tracks_need", "ceil_tracks_apply",
+              "ceil_tracks_peak"):
+        assert count[k] == count2[k] > 0, k
+    assert count == count2
+    # what a pass queues, whatever n: the keep, then a pass's gain and its ceiling at C, and for a
+    # boost the copy back and the inner ceiling before them
+    boosts = sum(g > 65536 for g in d["pass_gain_q16"])
+    assert boosts == d["passes"] and count["level_tracks_gain"] == 1 + d["passes"] + boosts
+    assert count["ceil_tracks_need"] == count["ceil_tracks_apply"] == d["passes"] + boosts <= count["ceil_tracks_peak"]
 
 
 # ------------------------------------------------------------------ at the end of a batch

@@ -127,7 +127,9 @@ def test_the_mono_batch(inputs, host, W, f32):
 
 
 def test_every_track_is_level_pcm_on_that_track_alone(inputs, stereo_run):
-    """The whole mm_level and level_dict bit for bit, and the R 128 report of the delivered samples."""
+    """A track's result does not depend on its neighbours in the launch: the whole mm_level and
+    level_dict bit for bit, and the R 128 report of the delivered samples, against the same driver
+    run on that track alone.  (The oracle is the host comparison in check_track.)"""
     from mastering_amd import engine, level_batch_pcm
     (got, lv, ce, rs), _ = stereo_run
     dbs = [None if inputs[k][3] == 0 else -1.0 for k in STEREO]

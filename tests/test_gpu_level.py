@@ -245,16 +245,16 @@ def test_without_the_key_nothing_changes(track):
         ctx.kernel_stats()
         a, ia = engine.master_pcm(track, RATE, params)
         names = set(ctx.kernel_stats())
-        assert "ceil_need" in names and "r128_kweight" in names and "level_gain" not in names
+        assert "ceil_need" in names and "r128_kweight" in names and "level_tracks_gain" not in names
         with pytest.raises(RuntimeError, match="no loudness target"):
             engine.levels(ctx)
         b, ib = engine.master_pcm(track, RATE, dict(params, deliver_lufs=None))
         assert np.array_equal(a, b) and ia == ib and "level" not in ia
-        assert "level_gain" not in set(ctx.kernel_stats())
+        assert "level_tracks_gain" not in set(ctx.kernel_stats())
         job = engine.Job(len(track), RATE, 2, P, ceiling_dbtp=-1.0, report=True, r128=True)
         assert job.delivery is None  # the plain entry point, as before
         engine.master_pcm(track, RATE, dict(params, deliver_lufs=-14.0))
-        assert "level_gain" in set(ctx.kernel_stats()) and engine.levels(ctx)[0].status == STATUS["reached"]
+        assert "level_tracks_gain" in set(ctx.kernel_stats()) and engine.levels(ctx)[0].status == STATUS["reached"]
     finally:
         ctx.timing(False)
 

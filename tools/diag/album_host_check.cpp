@@ -12,7 +12,10 @@
 // one, and checks what the definition promises whatever the pass count: every track's true peak
 // under the ceiling, a REACHED album within 0.05 LU of the target, the album's report the pooled
 // figures of the delivered tracks, without a ceiling every track equal to gain(source, gain_q16)
-// computed here, and an album of one track equal to mm_level_host.  Exits non-zero on any failure.
+// computed here, and an album of one track equal to mm_level_host.  Both entries now run the one
+// host loop (csrc/album.hip: level_group_host), so that last check compares the loop with itself
+// and only guards the two wrappers; what the loop must deliver is pinned by
+// tests/golden/level_host_parent.json (tests/test_level_golden.py).  Exits non-zero on any failure.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -154,7 +157,7 @@ static mm_level run(const std::vector<Track> &src, int ch, int clu, int32_t C, i
     return m;
 }
 
-// n = 1 is mm_level_host: the same samples and the same struct
+// n = 1 is mm_level_host: the same samples and the same struct (one loop behind both: the wrappers agree)
 static void one_track(const Track &src, int ch, int clu, int32_t C, int32_t W) {
     double sos[2][5];
     kweight(RATE, sos);

@@ -1,7 +1,7 @@
 // Stand-alone host check of mm_level_host (delivery to an R 128 loudness target restated in
-// plain C++, csrc/level.hip) for a sanitizer build: no context, no GPU, never loaded into
-// Python.  Build the library's translation unit and this file into one program with the
-// host side instrumented, and run it on the CPU:
+// plain C++: csrc/album.hip's level_group_host over one track) for a sanitizer build: no
+// context, no GPU, never loaded into Python.  Build the library's translation unit and this
+// file into one program with the host side instrumented, and run it on the CPU:
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Wno-unused-value -Wno-unused-result \
 //     -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer \
 //     python-audio-mastering_amd/csrc/mastering.hip tools/diag/level_host_check.cpp -lrccl -o level_host_check
