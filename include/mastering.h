@@ -305,6 +305,36 @@ typedef struct mm_resample {
     int32_t peak[2];         /* max |delivered sample|, 0..32768                     */
 } mm_resample;
 
+/* The linear-phase FIR (no reference counterpart), all integers: the stage a reference match
+ * applies its curve with (design.match_taps).  taps is the caller's table c[K], int32
+ * multiples of 2^-22, K odd, H = (K - 1) / 2, symmetric: c[k] == c[K-1-k].  For input s
+ * (int16, 0 outside [0, N)) the output has N frames; frame n of a channel is
+ *   acc = sum_{k<K} c[k] * s[n + H - k]
+ *   y = (acc + 2^21) >> 22 (arithmetic), delivered clipped to [-32768, 32767].
+ * Frame n stays at frame n: no latency, no tail.  Channels are independent.
+ * A table is refused (MM_ERR_ARG) unless K is odd and 3 <= K <= 8191, the taps are symmetric
+ * and sum |c| < 2^24.  Then |acc| < 2^39: the sum is exact in int64 and in f64 FMAs in any
+ * order, with the pairs of equal taps folded or not. */
+typedef struct mm_fir {
+    int32_t rate;            /* of the signal: carried into mm_fir_result, nothing else    */
+    int32_t K;
+    const int32_t *taps;     /* host [K]                                             */
+    uint64_t taps_key;       /* content key of taps (nonzero; the context keeps its
+                                device copy while the key and K stay the same).
+                                0: no key, checked and uploaded on every call          */
+} mm_fir;
+
+typedef struct mm_fir_result {
+    int64_t frames;
+    int32_t channels;
+    int32_t rate;
+    int32_t K;
+    int32_t _pad;
+    int64_t clipped[2];        /* y outside the int16 range                          */
+    int32_t peak[2];           /* max |delivered sample|, 0..32768                   */
+    int32_t peak_unclipped[2]; /* max |y| before the clip (below 2^17)               */
+} mm_fir_result;
+
 /* The EBU R 128 report of a delivered signal (no reference counterpart): what an ITU-R
  * BS.1770-4 meter reads.  mm_meter.loudness is the reference's own measure (pyloudnorm on
  * the channel mean through float32 write-backs), which the chain normalises to; here every
@@ -536,7 +566,9 @@ int mm_sync(mm_ctx *ctx);
    mm_qc_span, mm_last_qc); and, in the same way (bit 3 of the two meter_on fields): mm_spectrum
    and the spectrum report (mm_spectrum_bands, mm_spectrum_from_bins, mm_spectrum_host,
    mm_spectrum_device, mm_spectrum_pcm, mm_batch_spectrum_device, mm_batch_spectrum_pcm,
-   mm_last_spectrum, mm_last_spectrum_bins).  A caller
+   mm_last_spectrum, mm_last_spectrum_bins); and, as new structs and entry points only: mm_fir,
+   mm_fir_result and the linear-phase FIR (mm_fir_device, mm_fir_pcm, mm_fir_host, mm_fir_span,
+   mm_last_fir).  A caller
    built against an older header must
    refuse a library whose version differs from its own MM_ABI_VERSION. */
 #define MM_ABI_VERSION 5
@@ -959,6 +991,28 @@ int mm_deliver_wav(mm_ctx *ctx, const mm_job *job, const mm_delivery *dl, const 
 /* The converter's statistics of the last mm_deliver* call on this context; MM_ERR_STATE
  * if the last master call was not a delivery. */
 int mm_last_resample(mm_ctx *ctx, mm_resample *out);
+
+/* ---- linear-phase FIR --------------------------------------------------------- */
+/* Filter a device-resident signal, interleaved [frames][channels] of `kind` (MM_OUT_I16, or
+ * MM_OUT_F32 = the same PCM / 32768: both give the same integers), into d_out (the same
+ * shape and kind, another buffer: the filter runs out of place, and two ranges that overlap
+ * anywhere are refused) as mm_fir defines.  frames = 0 is valid.  MM_ERR_ARG, with words in
+ * mm_last_error and nothing written, for a table mm_fir refuses (a table whose nonzero taps_key and K are the context's cached ones is not read
+ * again), more than 2 channels, frames outside [0, 2^31) or a bad kind.  Synchronous on return. */
+int mm_fir_device(mm_ctx *ctx, const void *d_in, int kind, int64_t frames, int channels, const mm_fir *fir, void *d_out,
+                  mm_fir_result *out);
+/* The same on host buffers. */
+int mm_fir_pcm(mm_ctx *ctx, const void *in, int kind, int64_t frames, int channels, const mm_fir *fir, void *out_pcm,
+               mm_fir_result *out);
+/* The definition restated in plain C++ with an int64 sum on the host (no context, no GPU),
+ * interleaved int16 in and out: a CPU check of what the kernel computes.  Nothing outside
+ * in[0, frames * channels) is read. */
+int mm_fir_host(const int16_t *in, int64_t frames, int channels, const mm_fir *fir, int16_t *out_pcm, mm_fir_result *out);
+/* Output frames per workgroup of the filter's kernel (where its seams lie). */
+int mm_fir_span(void);
+/* The statistics of the context's last mm_fir_device / mm_fir_pcm pass; MM_ERR_STATE if it
+ * has run none. */
+int mm_last_fir(mm_ctx *ctx, mm_fir_result *out);
 
 /* ---- 24- and 32-bit integer PCM --------------------------------------------- */
 /* Decode n_samples of `kind` (MM_IN_I24: any byte address; MM_IN_I32: 4-byte

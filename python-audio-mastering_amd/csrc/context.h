@@ -93,6 +93,12 @@ struct mm_ctx {
     int rs_L = 0, rs_M = 0, rs_K = 0;
     mm_resample resample{};
     bool resample_valid = false;
+    // the FIR's taps on the device ("fir_taps": content key and length; key 0: none) and the
+    // statistics of the context's last filter pass (mm_last_fir)
+    uint64_t fir_key = 0;
+    int fir_K = 0;
+    mm_fir_result fir{};
+    bool fir_valid = false;
     // rccl
     ncclComm_t comm = nullptr;
     int rank = 0, nranks = 1;

@@ -1296,5 +1296,6 @@ int mm_kernel_stats(mm_ctx *c, char *names, int names_cap, double *total_ms, int
 #include "ceiling.hip"
 #include "level.hip"
 #include "resample.hip"
+#include "fir.hip"
 #include "album.hip"
 #include "tracks.hip"

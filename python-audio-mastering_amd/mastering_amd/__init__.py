@@ -58,13 +58,17 @@ Public surface (mirrors worker/audio_mastering_engine.py):
                                a batch or an album delivered at another rate (no reference
                                counterpart): every track as resample_pcm gives it, all tracks
                                in one converter launch, then levelled at the new rate
+  params["match"], match_pcm(pcm, rate, reference), match_gains(source, reference), fir_pcm(pcm, rate, taps)
+                               the reference match (no reference counterpart): the delivered
+                               output's 1/3-octave balance brought to a reference's by an exact
+                               linear-phase FIR of up to 8191 taps, before the level and the ceiling
   legacy.master_pcm / legacy.process and main.py's helpers
                                the older monolithic engine (root main.py:46-192) as an
                                alternate DSP profile on the same HIP operators
 """
 from .engine import (EQ_PRESETS, Job, album_level_pcm, album_r128_pcm, ceiling_batch_pcm, ceiling_pcm, ceilings,  # noqa: F401
-                     deliver_batch, level_batch_pcm, level_pcm, levels, master_album, master_batch, master_device,
-                     master_pcm, meter_pcm, meters, process, process_album, process_batch, qc_batch_pcm, qc_dict, qc_pcm, qcs,
+                     deliver_batch, fir_pcm, level_batch_pcm, level_pcm, levels, master_album, master_batch, master_device,
+                     master_pcm, match_gains, match_pcm, meter_pcm, meters, process, process_album, process_batch, qc_batch_pcm, qc_dict, qc_pcm, qcs,
                      r128_pcm, r128s, resample_batch_pcm, resample_pcm, occupied_hz, spectra, spectrum_bands, spectrum_batch_pcm,
                      spectrum_dict, spectrum_pcm)
 from . import legacy  # noqa: F401
@@ -80,4 +84,5 @@ __all__ = ["legacy", "EQ_PRESETS", "Job", "master_pcm", "master_device", "master
            "ceilings", "resample_pcm", "r128_pcm", "r128s", "level_pcm", "levels", "album_level_pcm", "album_r128_pcm",
            "master_album", "process_album", "ceiling_batch_pcm", "level_batch_pcm", "deliver_batch", "process_batch",
            "resample_batch_pcm", "qc_pcm", "qc_batch_pcm", "qc_dict", "qcs",
-           "spectrum_pcm", "spectrum_batch_pcm", "spectrum_dict", "spectra", "spectrum_bands", "occupied_hz"]
+           "spectrum_pcm", "spectrum_batch_pcm", "spectrum_dict", "spectra", "spectrum_bands", "occupied_hz",
+           "match_pcm", "match_gains", "fir_pcm"]

@@ -292,6 +292,104 @@ def resample_frames(frames: int, L: int, M: int) -> int:
     return -(-int(frames) * int(L) // int(M))
 
 
+# The reference match's linear-phase FIR (include/mastering.h: mm_fir).  The library convolves
+# integers with the integer taps designed here and never evaluates a window or a response.
+MATCH_MAX_TAPS = 8191       # K (mm_fir's limit)
+MATCH_FFT = 1 << 17         # points of the inverse real FFT the impulse response comes from
+MATCH_BETA = 6.0            # Kaiser window
+MATCH_ONE = 1 << 22         # a tap of 1.0
+MATCH_SUM_LIMIT = 1 << 24   # sum |c| below this
+
+
+def match_length(rate: int) -> int:
+    """Taps of the match filter at `rate`: min(8191, 2 * floor(rate * 1024 / 44100) - 1), about
+    46 ms (2047 at 44.1 kHz, 2227 at 48 kHz, 4457 at 96 kHz, 8191 at 192 kHz)."""
+    return min(MATCH_MAX_TAPS, 2 * (int(rate) * 1024 // 44100) - 1)
+
+
+def _band_centres(rate: int) -> np.ndarray:
+    """Centres in Hz of the spectrum report's 1/3-octave bands at `rate` (mm_spectrum_bands; no GPU)."""
+    from . import native
+    edges = np.zeros((native.SPECTRUM_MAX_BANDS, 3), np.float64)
+    n = native.load().mm_spectrum_bands(int(rate), native.SPECTRUM_MAX_BANDS, edges.ctypes.data_as(native.c_double_p))
+    if n < 0:
+        raise ValueError(f"mm_spectrum_bands failed ({n}): rate below 2000 Hz")
+    return edges[:n, 1].copy()
+
+
+def _match_half(rate: int, gains_db, K: int | None):
+    """(K, the first (K + 1) / 2 taps of the match filter in f64, in units of 2^-22, untrimmed)."""
+    rate = int(rate)
+    K = match_length(rate) if K is None else int(K)
+    if K < 3 or K > MATCH_MAX_TAPS or K % 2 == 0:
+        raise ValueError(f"the match filter has an odd number of taps in [3, {MATCH_MAX_TAPS}], not {K}")
+    centres = _band_centres(rate)
+    g = np.asarray(gains_db, dtype=np.float64)
+    if g.shape != centres.shape:
+        raise ValueError(f"gains_db: {g.size} values for the {centres.size} bands at {rate} Hz")
+    H = (K - 1) // 2
+    f = np.arange(MATCH_FFT // 2 + 1, dtype=np.float64) * (rate / MATCH_FFT)
+    with np.errstate(divide="ignore"):
+        db = np.interp(np.log2(f), np.log2(centres), g)  # (log2 0 = -inf: the first gain)
+    h = np.fft.irfft(10.0 ** (db / 20.0), MATCH_FFT)  # zero phase: h[-n] = h[n]
+    return K, h[:H + 1][::-1] * np.kaiser(K, MATCH_BETA)[:H + 1] * MATCH_ONE  # taps 0..H (tap H: h[0])
+
+
+def match_taps(rate: int, gains_db, K: int | None = None, trim: float = 1.0) -> np.ndarray:
+    """The match filter's taps c[K], int32 multiples of 2^-22, exactly symmetric, for one gain in
+    dB per band of the spectrum report at `rate` (engine.spectrum_bands).  The response in dB is
+    piecewise-linear over log2 f through (centre, gain), constant below the first centre and
+    above the last; its zero-phase impulse response is the inverse real FFT of MATCH_FFT points;
+    the centre K taps (default match_length(rate); odd, 3..8191) are taken under a Kaiser window
+    (beta 6) and multiplied by `trim`; the first (K + 1) / 2 are rounded and mirrored.
+    ValueError for a K mm_fir refuses, a gain count other than the bands', or sum |c| >= 2^24
+    (match_headroom gives the trim under which the table fits)."""
+    K, half = _match_half(rate, gains_db, K)
+    H = (K - 1) // 2
+    c = np.rint(half * float(trim)).astype(np.int64)
+    c = np.concatenate([c, c[:H][::-1]])
+    if int(np.abs(c).sum()) >= MATCH_SUM_LIMIT:
+        raise ValueError("the match filter's taps have sum |c| >= 2^24: design them under match_headroom's trim")
+    return np.ascontiguousarray(c, dtype=np.int32)
+
+
+def match_headroom(rate: int, gains_db, K: int | None = None) -> float:
+    """The largest trim <= 1 under which match_taps' table keeps sum |c| < 2^24, the bound the
+    filter's exactness rests on: 1.0 when the untrimmed table does, else (2^24 - K) / sum |c| of
+    the unrounded taps (rounding moves the sum by at most K / 2).  A curve whose boosts and cuts
+    alternate has a sum far above its largest gain, so curves of a few dB already need it."""
+    K, half = _match_half(rate, gains_db, K)
+    total = 2.0 * float(np.abs(half[:-1]).sum()) + float(abs(half[-1]))
+    return 1.0 if total + K < MATCH_SUM_LIMIT else (MATCH_SUM_LIMIT - K) / total
+
+
+def match_trim(K: int, peak_unclipped: int) -> float:
+    """The factor by which the trim of the taps is lowered after a pass whose largest |y| before
+    the clip was `peak_unclipped` > 32767: (32767 - K / 128 - 1) / peak_unclipped, under which the
+    second pass cannot clip."""
+    return (32767.0 - K / 128.0 - 1.0) / float(peak_unclipped)
+
+
+def fir_response_db(taps, rate: int, freqs) -> np.ndarray:
+    """20 log10 |C(f)| of integer symmetric taps (c / 2^22) at `freqs` Hz: the response the
+    library's filter realises, evaluated directly (c[H] + 2 sum_d c[H + d] cos(2 pi f d / rate))."""
+    c = np.asarray(taps, dtype=np.float64)
+    H = (c.size - 1) // 2
+    w = 2.0 * np.pi * np.asarray(freqs, dtype=np.float64) / float(rate)
+    d = np.arange(1, H + 1, dtype=np.float64)
+    amp = (c[H] + 2.0 * (np.cos(np.outer(w, d)) @ c[H + 1:])) / MATCH_ONE
+    with np.errstate(divide="ignore"):
+        return 20.0 * np.log10(np.abs(amp))
+
+
+def match_key(taps) -> int:
+    """Content key (nonzero 64-bit) of a table of taps: the context caches its device copy by
+    this key (mm_fir.taps_key)."""
+    c = np.ascontiguousarray(taps, dtype=np.int32)
+    head = np.array([c.size], np.int64).tobytes()
+    return int.from_bytes(hashlib.blake2b(head + c.tobytes(), digest_size=8).digest(), "little") or 1
+
+
 def crossover_sections(rate, low_hz=LOW_CROSSOVER, high_hz=HIGH_CROSSOVER):
     """AME:197-198: butter(4) LP and HP as 2 SOS sections each."""
     lp = scipy.signal.butter(4, low_hz, btype="lowpass", fs=rate, output="sos")

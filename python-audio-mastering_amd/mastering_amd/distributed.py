@@ -360,6 +360,8 @@ def master_time_sharded(backend, plan: RankPlan, params: dict, d_in, d_out, coll
         raise ValueError("the spectrum report needs the whole track: not available on the time-sharded path")
     if params.get("deliver_lufs") is not None:
         raise ValueError("a loudness target (deliver_lufs) needs the whole track: not available on the time-sharded path")
+    if params.get("match") is not None:
+        raise ValueError("the reference match (params['match']) needs the whole track: not available on the time-sharded path")
     # checked before any work or collective: the path depends only on the collective's
     # kind and the plan, the same on every rank (raises since round 5)
     if isinstance(coll, LibraryCollectives) and (coll.ctx is not getattr(backend, "ctx", None)

@@ -62,6 +62,11 @@ class Resampler:
         return design.resample_frames(frames, self.L, self.M)
 
 
+# (master_pcm and process take the key off before they plan)
+MATCH_REFUSAL = ("the reference match (params['match']) works on one whole delivered track, in master_pcm and process: "
+                 "not available for a batch, an album, a time-sharded range or a staged job")
+
+
 class Job:
     """A planned mastering job: the mm_job POD plus the host arrays it points to."""
 
@@ -130,6 +135,8 @@ class Job:
         if channels not in (1, 2):
             raise ValueError("only mono and stereo are supported (AME:119,137,152)")
         params = dict(params or {})
+        if params.get("match") is not None:
+            raise ValueError(MATCH_REFUSAL)
         self.params = params
         self.rate, self.channels, self.frames_in = int(rate), int(channels), int(frames_in)
         multiband = bool(params.get("multiband"))
@@ -900,6 +907,229 @@ def resample_batch_pcm(tracks, rate_in: int, rate_out: int, device: int = 0):
     return outs, [resample_dict(m) for m in ms]
 
 
+class Fir:
+    """The mm_fir POD of a table of taps plus the array it points to.  `key`: the content key the
+    context caches the device copy under (default design.match_key(taps); 0: no key, the table
+    is checked and uploaded on every call)."""
+
+    def __init__(self, taps, rate: int, key: int | None = None):
+        self.taps = np.ascontiguousarray(taps, dtype=np.int32)
+        f = native.MMFir()
+        f.rate, f.K = int(rate), int(self.taps.size)
+        f.taps = self.taps.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        f.taps_key = design.match_key(self.taps) if key is None else int(key)
+        self.fir = f
+
+
+def fir_dict(m: native.MMFirResult) -> dict:
+    """An mm_fir_result as a dict: the struct's integers (clipped, peak and peak_unclipped as
+    per-channel lists) and the largest delivered sample in dBFS.  No reference counterpart."""
+    ch = int(m.channels)
+    d = {f: int(getattr(m, f)) for f in ("frames", "channels", "rate", "K")}
+    for f in ("clipped", "peak", "peak_unclipped"):
+        d[f] = [int(getattr(m, f)[c]) for c in range(ch)]
+    d["peak_dbfs"] = _db(max(d["peak"], default=0) / 32768.0)
+    return d
+
+
+def fir_pcm(pcm: np.ndarray, rate: int, taps, key: int | None = None, device: int = 0):
+    """Filter an int16 (or float32 = int16 / 32768) array [N] or [N, ch] with the symmetric int32
+    `taps` (multiples of 2^-22, as design.match_taps makes them) without mastering it
+    (mm_fir_pcm): returns (a new array of the same shape, fir_dict).  Frame n stays at frame n.
+    `key`: as Fir's.  ValueError for a table mm_fir refuses."""
+    ch = 1 if pcm.ndim == 1 else pcm.shape[1]
+    x, kind = _out_kind(pcm)
+    f = Fir(taps, rate, key)
+    out = np.empty_like(x)
+    ctx = native.context(device)
+    m = native.MMFirResult()
+    ctx.check(ctx.lib.mm_fir_pcm(ctx.ptr, x.ctypes.data_as(ctypes.c_void_p), kind, x.shape[0], ch, ctypes.byref(f.fir),
+                                 out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(m)), "mm_fir_pcm")
+    return out, fir_dict(m)
+
+
+def fir_host(pcm: np.ndarray, rate: int, taps):
+    """fir_pcm's definition restated in plain C++ on the host (mm_fir_host; int16 only, no GPU):
+    (a new array, fir_dict).  ValueError for what the library refuses."""
+    x = np.ascontiguousarray(pcm, dtype=np.int16)
+    ch = 1 if x.ndim == 1 else x.shape[1]
+    f = Fir(taps, rate, 0)
+    out = np.zeros_like(x)
+    m = native.MMFirResult()
+    p16 = ctypes.POINTER(ctypes.c_int16)
+    rc = native.load().mm_fir_host(x.ctypes.data_as(p16), x.shape[0], ch, ctypes.byref(f.fir), out.ctypes.data_as(p16),
+                                   ctypes.byref(m))
+    if rc < 0:
+        raise ValueError(f"mm_fir_host failed ({rc}): a table or a signal mm_fir refuses")
+    return out, fir_dict(m)
+
+
+MATCH_FLOOR_DB = -90.0  # a band at or below this level is not compared
+MATCH_MIN_BANDS = 3     # comparable bands a match needs
+
+
+def _band_level(band: dict) -> float | None:
+    """10 log10 of the mean over the channels of a band's `ms` (None: not measured; -inf: silent)."""
+    ms = band["ms"]
+    if any(v is None or math.isnan(v) for v in ms):
+        return None
+    mean = sum(ms) / len(ms)
+    return 10.0 * math.log10(mean) if mean > 0 else -math.inf
+
+
+def match_gains(source_spectrum: dict, reference_spectrum: dict, amount: float = 1.0, max_db: float = 12.0) -> dict:
+    """The match rule on two spectrum_dicts (their rates may differ): one gain in dB per band of
+    the source's table, for design.match_taps at the source's rate.  A band's level is 10 log10
+    of the mean over the channels of its `ms` (one curve serves both channels).  A band is
+    comparable when the reference has a band of the same `lo_hz` / `hi_hz` (the band Nyquist clips
+    usually has none), both have `bins_in_band` >= 1 and both levels lie above -90 dB.  On those
+    the gain is reference - source, less the unweighted mean of these differences (the loudness
+    is deliver_lufs's business), clipped to +-`max_db` and multiplied by `amount` in [0, 1]; every
+    other band takes the gain of the nearest comparable band, the lower one on a tie.  Fewer than
+    three comparable bands, or a spectrum without a frame (n_frames 0): status "unmeasurable" and
+    all gains 0.  Returns {"status" ("matched" | "unmeasurable"), "amount", "max_db", "comparable"
+    (their count), "gains_db" (a list), "bands": one dict a band with `centre_hz`, `source_dbfs`,
+    `reference_dbfs` (None: no such band, or not measured), `comparable`, `gain_db`}."""
+    amount, max_db = float(amount), float(max_db)
+    if not 0.0 <= amount <= 1.0:
+        raise ValueError(f"match: amount must lie in [0, 1], not {amount}")
+    if not max_db >= 0.0:
+        raise ValueError(f"match: max_db must not be negative, not {max_db}")
+    ref = {(b["lo_hz"], b["hi_hz"]): b for b in reference_spectrum["bands"]}
+    measured = source_spectrum["n_frames"] > 0 and reference_spectrum["n_frames"] > 0
+    bands, diff = [], {}
+    for i, b in enumerate(source_spectrum["bands"]):
+        r = ref.get((b["lo_hz"], b["hi_hz"]))
+        src = _band_level(b) if measured else None
+        rf = _band_level(r) if measured and r is not None else None
+        ok = (src is not None and rf is not None and b["bins_in_band"] >= 1 and r["bins_in_band"] >= 1
+              and src > MATCH_FLOOR_DB and rf > MATCH_FLOOR_DB)
+        if ok:
+            diff[i] = rf - src
+        bands.append({"centre_hz": b["centre_hz"], "source_dbfs": src, "reference_dbfs": rf, "comparable": ok,
+                      "gain_db": 0.0})
+    out = {"status": "unmeasurable", "amount": amount, "max_db": max_db, "comparable": len(diff), "bands": bands}
+    if len(diff) >= MATCH_MIN_BANDS:
+        out["status"] = "matched"
+        mean = sum(diff.values()) / len(diff)
+        idx = sorted(diff)
+        for i, b in enumerate(bands):
+            near = min(idx, key=lambda k: (abs(k - i), k))  # (the lower one on a tie)
+            b["gain_db"] = amount * min(max_db, max(-max_db, diff[near] - mean))
+    out["gains_db"] = [b["gain_db"] for b in bands]
+    return out
+
+
+def _spectrum_device(ctx: native.Context, d_pcm: int, kind: int, frames: int, ch: int, rate: int) -> dict:
+    """The spectrum report (spectrum_dict) of a device-resident signal (mm_spectrum_device)."""
+    m = native.MMSpectrum()
+    bins = np.zeros((native.SPECTRUM_BINS, 3), np.float64)
+    bands = np.zeros((native.SPECTRUM_MAX_BANDS, 4), np.float64)
+    ctx.check(ctx.lib.mm_spectrum_device(ctx.ptr, ctypes.c_void_p(d_pcm), kind, frames, ch, int(rate), ctypes.byref(m),
+                                         bands.ctypes.data_as(native.c_double_p), bins.ctypes.data_as(native.c_double_p)),
+              "mm_spectrum_device")
+    return spectrum_dict(m, bands[:m.n_bands], bins)
+
+
+def _match_reference(reference, device: int = 0) -> dict:
+    """A match's reference as a spectrum_dict: a spectrum_dict itself, a (pcm, rate) pair measured
+    with spectrum_pcm, or the path of a 16-bit PCM WAV read and measured (ValueError for another
+    sample format: references wider than 16 bit are not taken)."""
+    if isinstance(reference, dict):
+        return reference
+    if isinstance(reference, (str, os.PathLike)):
+        from . import wavio
+        pcm, rate = wavio.read_wav(os.fspath(reference))
+        if pcm.dtype != np.int16:
+            raise ValueError(f"params['match']: the reference {os.fspath(reference)!r} is not a 16-bit PCM WAV")
+        return spectrum_pcm(pcm, rate, device=device)
+    pcm, rate = reference
+    return spectrum_pcm(np.asarray(pcm), int(rate), device=device)
+
+
+def match_apply(first_pass, gains: dict, rate: int, K: int | None = None):
+    """The match after its rule: the taps of `gains` (match_gains) at `rate`, under
+    design.match_headroom's trim where their sum |c| would reach 2^24, one pass of
+    `first_pass(taps)` -> fir_dict, and, if that pass clipped, the taps redesigned with the trim
+    lowered by design.match_trim and applied once more from the untouched source, which cannot
+    clip.  `first_pass` is called once or twice and each call filters the source anew.  Returns the
+    match_dict of match_pcm; nothing runs for an unmeasurable match.  The composition is the same
+    whatever applies the taps: fir_pcm, mm_fir_device on device buffers, or a host restatement."""
+    K = design.match_length(rate) if K is None else int(K)
+    d = {"status": gains["status"], "K": K, "rate": int(rate), "amount": gains["amount"], "max_db": gains["max_db"],
+         "trim_db": 0.0, "passes": 0, "fir": None, "bands": [dict(b, realised_db=0.0) for b in gains["bands"]]}
+    if gains["status"] != "matched":
+        return d
+    fit = design.match_headroom(rate, gains["gains_db"], K)  # (1.0 unless sum |c| would reach 2^24)
+    taps = design.match_taps(rate, gains["gains_db"], K, fit)
+    realised = design.fir_response_db(taps, rate, [b["centre_hz"] for b in d["bands"]])
+    for b, r in zip(d["bands"], realised):
+        b["realised_db"] = float(r) - 20.0 * math.log10(fit)
+    fir = first_pass(taps)
+    d["passes"], trim = 1, fit
+    if any(fir["clipped"]):
+        trim = fit * design.match_trim(K, max(fir["peak_unclipped"]))
+        fir = first_pass(design.match_taps(rate, gains["gains_db"], K, trim))
+        d["passes"] = 2
+        assert not any(fir["clipped"]), "the trimmed match clipped"
+    d["trim_db"] = 20.0 * math.log10(trim)
+    d["fir"] = fir
+    return d
+
+
+def _match_device(ctx: native.Context, d_in: int, d_out: int, kind: int, frames: int, ch: int, rate: int,
+                  reference: dict, amount: float, max_db: float, K: int | None = None) -> dict:
+    """The match on device buffers: the spectrum of the signal at `d_in` (mm_spectrum_device), the
+    gains against the `reference` spectrum_dict, the taps, and mm_fir_device from `d_in` into `d_out`
+    (twice when the first pass clips).  Returns the match_dict; `d_out` holds the matched signal when
+    its `passes` > 0, else nothing was written and `d_in` is what is delivered."""
+    gains = match_gains(_spectrum_device(ctx, d_in, kind, frames, ch, rate), reference, amount, max_db)
+
+    def run(taps):
+        f = Fir(taps, rate)
+        m = native.MMFirResult()
+        ctx.check(ctx.lib.mm_fir_device(ctx.ptr, ctypes.c_void_p(d_in), kind, frames, ch, ctypes.byref(f.fir),
+                                        ctypes.c_void_p(d_out), ctypes.byref(m)), "mm_fir_device")
+        return fir_dict(m)
+
+    return match_apply(run, gains, rate, K)
+
+
+def _device_pair(x: np.ndarray, device: int):
+    """A host signal on the device and a second buffer of its shape (torch: plumbing only)."""
+    import torch
+    dev = torch.device("cuda", device)
+    d_in = torch.from_numpy(x).to(dev)
+    d_out = torch.empty_like(d_in)
+    torch.cuda.synchronize(dev)
+    return d_in, d_out
+
+
+def match_pcm(pcm: np.ndarray, rate: int, reference, amount: float = 1.0, max_db: float = 12.0, taps: int | None = None,
+              device: int = 0):
+    """Match the tonal balance of an int16 (or float32 = int16 / 32768) array [N] or [N, ch] to a
+    reference without mastering it: returns (a new array, match_dict).  `reference`: a
+    spectrum_dict, or a (pcm, rate) pair measured with spectrum_pcm; its rate may differ.  On the
+    device: the signal's spectrum (mm_spectrum_device), match_gains, design.match_taps (`taps`:
+    their number, default design.match_length(rate)), and one mm_fir_device pass into a second
+    buffer; if that pass clips, the taps are redesigned with design.match_trim and applied once
+    more from the untouched source, and that pass cannot clip.  The curve is tonal (its mean over
+    the comparable bands is 0 dB) and linked (one curve for both channels).
+    match_dict: `status` ("matched", or "unmeasurable": the signal is returned unchanged), `K`,
+    `rate`, `amount`, `max_db`, `trim_db` (<= 0; 0 when the table fit and one pass sufficed), `passes`, per band
+    `centre_hz`, `source_dbfs`, `reference_dbfs`, `comparable`, `gain_db` (asked) and `realised_db`
+    (the integer taps' response at the centre, trim excluded: the lowest bands are
+    resolution-limited), and `fir`, the last pass's fir_dict.  Figures, not verdicts."""
+    ch = 1 if pcm.ndim == 1 else pcm.shape[1]
+    x, kind = _out_kind(pcm)
+    amount, max_db = float(amount), float(max_db)
+    ref = _match_reference(reference, device)
+    ctx = native.context(device)
+    d_in, d_out = _device_pair(x, device)
+    d = _match_device(ctx, d_in.data_ptr(), d_out.data_ptr(), kind, x.shape[0], ch, rate, ref, amount, max_db, taps)
+    return (d_out if d["passes"] else d_in).cpu().numpy(), d
+
+
 def _batch_resampler(jobs, output_rate, d_mids, what: str):
     """The converter of a batch or album call (`what`) whose jobs share one rate: None when
     `output_rate` is None or that rate (the call is then exactly the call without it, and
@@ -1012,7 +1242,12 @@ def master_pcm(pcm: np.ndarray, rate: int, params: dict, out_kind: int = native.
     (level_dict); absent or None, the call is exactly the call without it.  params['qc']
     (truthy; independent of the other reports) adds info['qc'] (qc_dict): the delivery QC report
     of the delivered output, with silence_lsb 1 and min_run 3.  params['spectrum'] (truthy;
-    independent too) adds info['spectrum'] (spectrum_dict): the spectrum report of the delivered output."""
+    independent too) adds info['spectrum'] (spectrum_dict): the spectrum report of the delivered output.
+    params['match'] = {"reference": a spectrum_dict, a (pcm, rate) pair or the path of a 16-bit PCM
+    WAV, "amount": 1.0, "max_db": 12.0} brings the output's tonal balance to the reference's
+    (match_pcm) after the chain and the converter, at the delivered rate, and before the level, the
+    ceiling and the reports, and adds info['match'] (match_dict); deliver_lufs makes up what its
+    trim took.  Absent or None, the call is exactly the call without it."""
     ch = 1 if pcm.ndim == 1 else pcm.shape[1]
     params = dict(params or {})
     report = bool(params.pop("report", False))
@@ -1022,6 +1257,11 @@ def master_pcm(pcm: np.ndarray, rate: int, params: dict, out_kind: int = native.
     deliver_lufs = params.pop("deliver_lufs", None)
     qc = bool(params.pop("qc", False))
     spectrum = bool(params.pop("spectrum", False))
+    match = params.pop("match", None)
+    if match is not None:
+        return _master_matched(pcm, rate, ch, params, out_kind, device, _match_params(match, device),
+                               dict(report=report, ceiling_dbtp=ceiling, output_rate=output_rate, r128=r128,
+                                    deliver_lufs=deliver_lufs, qc=qc, spectrum=spectrum))
     job = Job(pcm.shape[0], rate, ch, params, out_kind, report=report, ceiling_dbtp=ceiling, output_rate=output_rate,
               r128=r128, deliver_lufs=deliver_lufs, qc=qc, spectrum=spectrum)
     x, job.job.in_kind = _device_input(pcm, wide=True)
@@ -1037,6 +1277,88 @@ def master_pcm(pcm: np.ndarray, rate: int, params: dict, out_kind: int = native.
         ctx.check(ctx.lib.mm_master(ctx.ptr, ctypes.byref(job.job), x.ctypes.data_as(ctypes.c_void_p),
                                     out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(res)), "mm_master")
     return out, _finish_info(_info(job, res), job, ctx)
+
+
+def _match_params(match, device: int = 0) -> dict:
+    """params['match'] checked, before any device work on the track: {"reference": a spectrum_dict
+    (a (pcm, rate) pair or the path of a 16-bit PCM WAV is measured here), "amount", "max_db"}."""
+    if not isinstance(match, dict) or match.get("reference") is None:
+        raise ValueError("params['match'] is a dict with a 'reference': a spectrum_dict, a (pcm, rate) pair or the path "
+                         "of a 16-bit PCM WAV")
+    extra = set(match) - {"reference", "amount", "max_db"}
+    if extra:
+        raise ValueError(f"params['match'] has no key {sorted(extra)[0]!r} (reference, amount, max_db)")
+    amount, max_db = float(match.get("amount", 1.0)), float(match.get("max_db", 12.0))
+    if not 0.0 <= amount <= 1.0 or not max_db >= 0.0:
+        raise ValueError(f"params['match']: amount in [0, 1] and max_db >= 0, not {amount} and {max_db}")
+    return {"reference": _match_reference(match["reference"], device), "amount": amount, "max_db": max_db}
+
+
+def _deliver_end(ctx: native.Context, job: "Job", d: int, kind: int, frames: int, ch: int, rate: int, info: dict) -> dict:
+    """The end of a master call, as `job` plans it, on a delivered device buffer, by the device
+    entries of the stages: the level or the ceiling in place (mm_level_device / mm_ceiling_device),
+    then the reports (mm_meter_device, mm_r128_device, mm_qc_device, mm_spectrum_device), into
+    `info` under _finish_info's keys."""
+    end = job.job if job.delivery is None else job.delivery  # who carries ceiling_q28 and meter_on
+    level = 0 if job.delivery is None else int(job.delivery.level_clu)
+    C, on, w = int(end.ceiling_q28), int(end.meter_on), design.ceiling_window(rate)
+    p = ctypes.c_void_p(d)
+    ce = native.MMCeiling()
+    if level:
+        lv = native.MMLevel()
+        ctx.check(ctx.lib.mm_level_device(ctx.ptr, p, kind, frames, ch, rate, kweight_sos(rate), level, C, w, ctypes.byref(lv),
+                                          ctypes.byref(ce) if C else None), "mm_level_device")
+        info["level"] = level_dict(lv)
+    elif C:
+        ctx.check(ctx.lib.mm_ceiling_device(ctx.ptr, p, kind, frames, ch, C, w, ctypes.byref(ce)), "mm_ceiling_device")
+    if C:
+        info["ceiling"] = ceiling_dict(ce)
+    if on & native.REPORT_METER:
+        m = native.MMMeter()
+        loud = ctypes.byref(job.job) if job.delivery is None else job.delivery.loud
+        ctx.check(ctx.lib.mm_meter_device(ctx.ptr, p, kind, frames, ch, loud, ctypes.byref(m)), "mm_meter_device")
+        info["report"] = report_dict(m, job.job.lufs_target if job.job.lufs_on else None)
+    if on & native.REPORT_R128:
+        m = native.MMR128()
+        ctx.check(ctx.lib.mm_r128_device(ctx.ptr, p, kind, frames, ch, rate, kweight_sos(rate), ctypes.byref(m)),
+                  "mm_r128_device")
+        info["r128"] = r128_dict(m)
+    if on & native.REPORT_QC:
+        m = native.MMQc()
+        ctx.check(ctx.lib.mm_qc_device(ctx.ptr, p, kind, frames, ch, rate, 1, 3, ctypes.byref(m), None), "mm_qc_device")
+        info["qc"] = qc_dict(m)
+    if on & native.REPORT_SPECTRUM:
+        info["spectrum"] = _spectrum_device(ctx, d, kind, frames, ch, rate)
+    return info
+
+
+def _master_matched(pcm: np.ndarray, rate: int, ch: int, params: dict, out_kind: int, device: int, match: dict, end: dict):
+    """master_pcm with params['match'], composed over device buffers as deliver_batch composes: the
+    master or deliver call without its end (the chain and, with `output_rate`, the converter), the
+    match at the delivered rate (_match_device), then the end the call asked for (_deliver_end):
+    the level, the ceiling and the reports, which so stay statements about the delivered samples.
+    `end`: Job's keywords of the call.  Nothing is queued before both plans stand."""
+    import torch
+    full = Job(pcm.shape[0], rate, ch, params, out_kind, **end)  # what the call asks for: its refusals, its end
+    head = Job(pcm.shape[0], rate, ch, params, out_kind, output_rate=end["output_rate"])
+    x, head.job.in_kind = _device_input(pcm, wide=True)
+    ctx = native.context(device)
+    dev = torch.device("cuda", device)
+    d_in = torch.from_numpy(x).to(dev)
+    dtype = torch.int16 if out_kind == native.MM_OUT_I16 else torch.float32
+    d_mid = torch.empty((head.frames_out, ch), dtype=dtype, device=dev)
+    d_out = torch.empty_like(d_mid)
+    torch.cuda.synchronize(dev)
+    res = native.MMResult()
+    master_device(ctx, head, d_in.data_ptr(), d_mid.data_ptr(), res)
+    info = _finish_info(_info(head, res), head, ctx)
+    out_rate = head.rate if head.output_rate is None else head.output_rate
+    info["match"] = _match_device(ctx, d_mid.data_ptr(), d_out.data_ptr(), out_kind, head.frames_out, ch, out_rate,
+                                  match["reference"], match["amount"], match["max_db"])
+    d = d_out if info["match"]["passes"] else d_mid
+    _deliver_end(ctx, full, d.data_ptr(), out_kind, head.frames_out, ch, out_rate, info)
+    out = d.cpu().numpy()
+    return (out[:, 0] if pcm.ndim == 1 else out), info
 
 
 def wav_info(path: str, device: int = 0) -> native.MMWavInfo:
@@ -1185,6 +1507,8 @@ def _process_files(name: str, noun: str, words, per_file: bool, deliver, input_p
     if params.pop("spectrum", None):
         raise ValueError(f"{name} takes no params['spectrum']: the keyword spectrum=True puts every {done} file's "
                          f"spectrum report into the {carrier}")
+    if params.get("match") is not None:
+        raise ValueError(f"{name} takes no params['match']: {MATCH_REFUSAL}")
     input_paths, output_paths = list(input_paths), list(output_paths)
     if len(input_paths) != len(output_paths):
         raise ValueError(f"{name} needs one output path for every input path")
@@ -1330,6 +1654,9 @@ def process(input_path: str, output_path: str, params: dict, device: int = 0, ve
     ceiling (info['level'], level_dict).
     params['qc'] (truthy) adds info['qc'] (qc_dict), the delivery QC report of the written samples.
     params['spectrum'] (truthy) adds info['spectrum'] (spectrum_dict), their spectrum report.
+    params['match'] (master_pcm's) matches the written samples' tonal balance to a reference
+    (info['match']); the file is then read whole (wavio.read_wav), mastered as master_pcm masters
+    it and written with wavio.write_wav.
     Raises ValueError for unreadable/unsupported input and RuntimeError for device
     failures, like the reference (AME:110-113)."""
     params = dict(params or {})
@@ -1342,6 +1669,19 @@ def process(input_path: str, output_path: str, params: dict, device: int = 0, ve
     qc = bool(params.pop("qc", False))
     spectrum = bool(params.pop("spectrum", False))
     kind = native.MM_OUT_F32 if fmt == "f32" else native.MM_OUT_I16
+    if params.get("match") is not None:  # the file is read whole and mastered as master_pcm masters it
+        from . import wavio
+        match = _match_params(params.pop("match"), device)
+        pcm, rate = wavio.read_wav(input_path)
+        if verbose:
+            print(f"Loaded {input_path}: {pcm.shape[0]} frames @ {rate} Hz")
+        out, info = _master_matched(pcm, rate, 1 if pcm.ndim == 1 else pcm.shape[1], params, kind, device, match,
+                                    dict(report=report, ceiling_dbtp=ceiling, output_rate=output_rate, r128=r128,
+                                         deliver_lufs=deliver_lufs, qc=qc, spectrum=spectrum))
+        wavio.write_wav(output_path, out, info.get("rate", rate))
+        info["output_path"] = os.path.abspath(output_path)
+        return info
+    params.pop("match", None)
     wi = wav_info(input_path, device)
     if verbose:
         print(f"Loaded {input_path}: {wi.frames} frames @ {wi.rate} Hz")

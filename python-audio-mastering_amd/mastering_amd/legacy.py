@@ -197,6 +197,9 @@ def master_pcm(pcm: np.ndarray, rate: int, settings: dict, device: int = 0) -> n
         raise ValueError("the QC report belongs to the mastering chain's delivery: not available in the legacy profile")
     if settings.get("spectrum"):
         raise ValueError("the spectrum report belongs to the mastering chain's delivery: not available in the legacy profile")
+    if settings.get("match") is not None:
+        raise ValueError("the reference match (settings['match']) belongs to the mastering chain's delivery: not available "
+                         "in the legacy profile")
     if settings.get("deliver_lufs") is not None:
         raise ValueError("a loudness target (deliver_lufs) belongs to the mastering chain's delivery: not available "
                          "in the legacy profile")
@@ -231,6 +234,9 @@ def process(input_path: str, output_path: str, settings: dict, device: int = 0) 
     """main.py:46-72 with local files: decode a 16-bit WAV, master, export WAV."""
     if (settings or {}).get("deliver_lufs") is not None:  # (before the file is read)
         raise ValueError("a loudness target (deliver_lufs) belongs to the mastering chain's delivery: not available "
+                         "in the legacy profile")
+    if (settings or {}).get("match") is not None:
+        raise ValueError("the reference match (settings['match']) belongs to the mastering chain's delivery: not available "
                          "in the legacy profile")
     pcm, rate = wavio.read_wav(input_path)
     if pcm.dtype != np.int16:

@@ -134,6 +134,17 @@ class MMResample(ctypes.Structure):
                 ("peak", ctypes.c_int32 * 2)]
 
 
+class MMFir(ctypes.Structure):
+    _fields_ = [("rate", ctypes.c_int32), ("K", ctypes.c_int32), ("taps", ctypes.POINTER(ctypes.c_int32)),
+                ("taps_key", ctypes.c_uint64)]
+
+
+class MMFirResult(ctypes.Structure):
+    _fields_ = [("frames", ctypes.c_int64), ("channels", ctypes.c_int32), ("rate", ctypes.c_int32),
+                ("K", ctypes.c_int32), ("_pad", ctypes.c_int32), ("clipped", ctypes.c_int64 * 2),
+                ("peak", ctypes.c_int32 * 2), ("peak_unclipped", ctypes.c_int32 * 2)]
+
+
 class MMDelivery(ctypes.Structure):
     _fields_ = [("rs", ctypes.POINTER(MMResampler)), ("ceiling_q28", ctypes.c_int32), ("window", ctypes.c_int32),
                 ("meter_on", ctypes.c_int32), ("level_clu", ctypes.c_int32), ("loud", ctypes.POINTER(MMJob))]
@@ -191,7 +202,8 @@ EXPORTS = ("mm_create", "mm_destroy", "mm_last_error", "mm_sync", "mm_version", 
            "mm_r128_album_from_hops", "mm_album_level_host", "mm_album_r128_device", "mm_album_r128_pcm",
            "mm_op_r128_album_hops", "mm_album_level_device", "mm_album_level_pcm", "mm_last_album",
            "mm_batch_ceiling_device", "mm_batch_ceiling_pcm", "mm_batch_level_device", "mm_batch_level_pcm",
-           "mm_batch_resample_device", "mm_batch_resample_pcm")
+           "mm_batch_resample_device", "mm_batch_resample_pcm",
+           "mm_fir_device", "mm_fir_pcm", "mm_fir_host", "mm_fir_span", "mm_last_fir")
 
 _lib = None
 _lock = threading.Lock()
@@ -381,6 +393,14 @@ def load():
                                           P(vp), P(MMResample)], ctypes.c_int),
             "mm_batch_resample_pcm": ([vp, P(vp), ctypes.c_int, c_int64_p, ctypes.c_int, ctypes.c_int, P(MMResampler),
                                        P(vp), P(MMResample)], ctypes.c_int),
+            "mm_fir_device": ([vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, P(MMFir), vp, P(MMFirResult)],
+                              ctypes.c_int),
+            "mm_fir_pcm": ([vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, P(MMFir), vp, P(MMFirResult)],
+                           ctypes.c_int),
+            "mm_fir_host": ([P(ctypes.c_int16), ctypes.c_int64, ctypes.c_int, P(MMFir), P(ctypes.c_int16),
+                             P(MMFirResult)], ctypes.c_int),
+            "mm_fir_span": ([], ctypes.c_int),
+            "mm_last_fir": ([vp, P(MMFirResult)], ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             fn = getattr(lib, name)

@@ -12,6 +12,8 @@ file goes to ``<output>.report.json`` before the marker, and with
 ``settings["ceiling_dbtp"]`` what the true-peak ceiling did goes to
 ``<output>.ceiling.json`` the same way, and with ``settings["deliver_lufs"]`` what the
 levelling stage did (status, passes, achieved loudness) to ``<output>.level.json``.
+A ``settings["match"]`` whose reference is a string names an object of the tree
+(``gs://<bucket>/<blob>``), resolved as the input is; no message can name another file.
 
 ``wsgi_app`` is the handler as a plain WSGI callable (what gunicorn serves the
 reference's Flask app as), so no web framework is needed; ``handle_push`` is the
@@ -66,12 +68,23 @@ def _json_safe(v):
     return v
 
 
+def _resolve_match(settings, root):
+    """settings["match"] with its reference resolved inside the object tree: a reference named by
+    a string is an object URI (``gs://<bucket>/<blob>``, object_path's rules and its ValueError for
+    anything else), never a path of the worker's own file system; a spectrum dict passes as it is."""
+    match = settings.get("match") if isinstance(settings, dict) else None
+    if isinstance(match, dict) and isinstance(match.get("reference"), str):
+        return dict(settings, match=dict(match, reference=object_path(match["reference"], root)[0]))
+    return settings
+
+
 def process_audio_from_gcs(gcs_uri: str, settings: dict, root: str | None = None, device: int = 0) -> dict:
     """AME:24-113 on the local object tree: master the object, write
     ``processed/mastered_<basename>`` and its ``.complete`` marker; re-raise any
     error after printing it, as the reference does."""
     try:
         src, bucket_dir, blob = object_path(gcs_uri, root)
+        settings = _resolve_match(settings, root)
         print(f"Downloading file from {gcs_uri}...")
         out_name = f"processed/mastered_{os.path.basename(blob)}"
         dst = os.path.join(bucket_dir, out_name)
