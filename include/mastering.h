@@ -908,7 +908,7 @@ int mm_last_album(mm_ctx *ctx, mm_level *level, mm_r128 *album);
  *
  * The tracks share one kind, channel count, rate and window.  Only the launch structure
  * differs from n calls: the need, apply, peak, trim, gain and K-weighting launches each cover
- * all tracks (csrc/tracks.hip), the tracks of a level advance one pass at a time, and the
+ * all tracks (csrc/ceiling.hip, tracks.hip, r128.hip), the tracks of a level advance one pass at a time, and the
  * launches and synchronisations of a pass do not depend on n. */
 
 /* Hold n device-resident tracks, interleaved [frames[t]][channels] of `kind`, under their

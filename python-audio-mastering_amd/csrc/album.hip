@@ -3,9 +3,8 @@
 // (the album R 128 figures and the album level in include/mastering.h).  Loudness differences
 // between the tracks are kept.  No reference counterpart.
 //
-// Two things live here.  The pooled measurement: r128.hip's album kernels K-weight every track
-// in ONE launch and reduce all hops in one more, with one read-back of the hop energies and the
-// look-back's error word, where n calls of r128_hops pay n synchronisations.  Pooled figures
+// Two things live here.  The pooled figures: r128.hip's measuring pass (AlbumPass) gives the
+// hop energies of every track of a call from two launches and one read-back; pooled figures
 // come from the windows of the tracks back to back (no window spans two tracks) through
 // r128_figures, the tail mm_r128_from_hops ends in; the per-track reports come from the same hop
 // energies, so a pass measures once.  Every pass of the device's level loop (tracks.hip:
@@ -65,82 +64,6 @@ int album_check(mm_ctx *c, const void *const *pcm, int kind, const int64_t *fram
     return MM_OK;
 }
 
-// The segmented measuring pass over n tracks, laid out once: every track on a workgroup
-// boundary, its hops at hop0[t] of the pass's.  The host tables live as long as the pass, so
-// their uploads need no synchronisation of their own: album_pass_hops, which every prepared
-// pass with a hop runs, ends in one.
-struct AlbumPass {
-    R128AlbumArgs a{};
-    unsigned nblk = 0;
-    int kind = 0, channels = 0;
-    std::vector<int64_t> hops;  // [n] H_t
-    std::vector<R128Track> tracks;
-    std::vector<int> wg_track;
-    double *d_e = nullptr;
-};
-
-// Lays the pass out and queues the uploads of its tables.
-int album_pass_prepare(mm_ctx *c, const void *const *d_pcm, int kind, const int64_t *frames, int n, int channels, int rate,
-                       const double sos[2][5], AlbumPass &p) {
-    int64_t wg = 0, hop = 0;
-    p.hops.resize((size_t)n);
-    p.tracks.resize((size_t)n);
-    p.wg_track.clear();
-    for (int t = 0; t < n; ++t) {
-        const int64_t G = (frames[t] + R128_TILE - 1) / R128_TILE, nwg = (G + LB_THREADS - 1) / LB_THREADS;
-        p.tracks[(size_t)t] = R128Track{d_pcm[t], frames[t], wg, hop};
-        p.wg_track.insert(p.wg_track.end(), (size_t)nwg, t);
-        p.hops[(size_t)t] = 10 * frames[t] / rate;
-        wg += nwg;
-        hop += p.hops[(size_t)t];
-    }
-    p.nblk = (unsigned)wg;
-    p.kind = kind;
-    p.channels = channels;
-    p.a.n = n;
-    p.a.rate = rate;
-    p.a.H = hop;
-    memcpy(p.a.sos, sos, sizeof p.a.sos);
-    if (hop == 0) return MM_OK;  // nothing to measure: nothing is queued
-    R128Track *d_tracks;
-    int *d_wg;
-    RET(get_buf(c, "album_tracks", (size_t)n, &d_tracks));
-    RET(get_buf(c, "album_wg", (size_t)wg, &d_wg));
-    RET(get_buf(c, "album_part", (size_t)wg * LB_THREADS * 2, &p.a.part));
-    RET(get_buf(c, "album_part_hop", (size_t)wg * LB_THREADS, &p.a.part_hop));
-    RET(get_buf(c, "album_hops", (size_t)hop, &p.d_e));
-    HIPCHK(c, hipMemcpyAsync(d_tracks, p.tracks.data(), (size_t)n * sizeof(R128Track), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_wg, p.wg_track.data(), (size_t)wg * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    p.a.tracks = d_tracks;
-    p.a.wg_track = d_wg;
-    return MM_OK;
-}
-
-// One measurement: the album's hop energies into `e`, track after track.  Two launches, one
-// read-back.  Synchronous on return.
-int album_pass_hops(mm_ctx *c, const AlbumPass &p, std::vector<double> &e) {
-    e.assign((size_t)p.a.H, 0.0);
-    if (p.a.H == 0) return MM_OK;
-    LbArgs lb{};
-    RET(r128_upload_tables(c, p.a.sos, p.channels, lb));
-    RET(lb_prepare(c, p.nblk, 1, lb));
-    RET(get_buf(c, "r128_lb_error", 4, &lb.error));
-    HIPCHK(c, hipMemsetAsync(lb.error, 0, 4, c->stream));
-    const size_t lds = (size_t)lb_lds_bytes<8, 1>() + (size_t)R128_CHUNK * R128_ROW * sizeof(uint32_t);
-    RET(dispatch_pcm(p.kind, p.channels, [&](auto ch, auto t) {
-        using T = decltype(t);
-        return launch(c, "r128_album_kweight", r128_album_kweight_kernel<ch, T>, dim3(p.nblk), dim3(LB_THREADS), lds, p.a, lb);
-    }));
-    RET(launch(c, "r128_album_reduce", r128_album_reduce_kernel, dim3(blocks_for(p.a.H, 4)), dim3(256), 0, p.a, p.d_e));
-    unsigned err = 0;
-    HIPCHK(c, hipMemcpyAsync(e.data(), p.d_e, (size_t)p.a.H * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(&err, lb.error, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    resolve_events(c);
-    if (err) return set_err(c, MM_ERR_STATE, "IIR look-back timed out");
-    return MM_OK;
-}
-
 // The pooled report of n tracks and every track's own from their hop energies `e` (track after
 // track, hops[t] of track t): the figures of album_from_hops with the frames and channels filled in.
 void album_reports(const double *e, const int64_t *hops, const int64_t *frames, int n, int rate, int channels, mm_r128 *album,
@@ -166,34 +89,6 @@ int album_r128_device(mm_ctx *c, const void *const *d_pcm, int kind, const int64
     album_reports(e.data(), pass.hops.data(), frames, n, rate, channels, out, tr.data());
     results_reset(c);
     c->r128s = tr;
-    return MM_OK;
-}
-
-// n host tracks into one context buffer, each on a 16-byte boundary: their device pointers
-int album_upload(mm_ctx *c, const char *name, const void *const *pcm, int kind, const int64_t *frames, int n, int channels,
-                 std::vector<void *> &d) {
-    size_t total = 0;
-    for (int t = 0; t < n; ++t) total += (pcm_bytes(kind, frames[t], channels) + 15) & ~(size_t)15;
-    char *base;
-    RET(get_buf(c, name, std::max<size_t>(total, 1), &base));
-    d.resize((size_t)n);
-    for (int t = 0; t < n; ++t) {
-        const size_t bytes = pcm_bytes(kind, frames[t], channels);
-        d[(size_t)t] = base;
-        if (bytes && pcm) HIPCHK(c, hipMemcpyAsync(base, pcm[t], bytes, hipMemcpyHostToDevice, c->stream));
-        base += (bytes + 15) & ~(size_t)15;
-    }
-    return MM_OK;
-}
-
-// d[t] back into pcm[t] for the tracks `pick` names (null: all), synchronous
-int batch_download(mm_ctx *c, void *const *pcm, const std::vector<void *> &d, int kind, const int64_t *frames, int n,
-                   int channels, const char *pick) {
-    for (int t = 0; t < n; ++t) {
-        const size_t bytes = pcm_bytes(kind, frames[t], channels);
-        if (bytes && (!pick || pick[t])) HIPCHK(c, hipMemcpyAsync(pcm[t], d[(size_t)t], bytes, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
     return MM_OK;
 }
 

@@ -10,15 +10,29 @@
 // g_t = floor(C_t * 2^16 / TP1): requantising moves |Y| by at most 8285.5 < 8286, so
 // the trimmed peak is at most C_t + 8285.5 < C.
 //
-// Three kernels.  ceil_need runs the meter's own oversampler (meter.hip: tp_stage,
-// tp_window, tp_frame) and writes r - 1 as uint16 to a plane; ceil_apply
+// Three span bodies.  ceil_need_span runs the meter's own oversampler (meter.hip: tp_stage,
+// tp_window, tp_frame) and writes r - 1 as uint16 to a plane; ceil_apply_span
 // stages the plane with its halo in LDS, forms both window minima by log-step doubling
-// and the box sums from one LDS scan, and rewrites the samples in place; ceil_trim is
-// pointwise.  The true peak after the limiter is the meter's own kernel.  All results
-// are integers combined with min / max / add: nothing depends on the launch geometry.
+// and the box sums from one LDS scan, and rewrites the samples in place; ceil_scale is
+// pointwise.  The true peak after the limiter is the need body with its store switched off.
+// All results are integers combined with min / max / add: nothing depends on the launch
+// geometry.
+//
+// One launch structure, over n >= 1 tracks each with its own parameters (tracks.h: a track
+// owns a run of workgroups, a workgroup finds its track by a search over at most 257 prefix
+// sums, which are uniform reads, and at n = 1 reads none), so a pass costs the same launches
+// and synchronisations for 1 track as for 256.  A single signal is the case n = 1.
+//   ceil_tracks_need   ceil_need_span over all METER_SPAN spans; track t's r - 1 plane at a
+//                      multiple of METER_SPAN of one plane buffer, TP0 into its CeilDev
+//   ceil_tracks_apply  ceil_apply_span over all CEIL_SPAN spans; the early exit, the plane mask
+//                      and the R mask are the track's own
+//   ceil_tracks_peak   the linked true peak of every track (a track whose TP0 <= C was not
+//                      touched: skipped)
+//   ceil_tracks_trim   pointwise, the tracks with a residue only, each by its own g_t
+// A workgroup of a track that takes no part exits on one uniform read of its parameters.
 //
 // Included at the end of mastering.hip after pcm16.h (frames, wave reductions, refusals,
-// dispatch_pcm) and meter.hip (the oversampler, tp_host, meter_launch, meter_device).
+// dispatch_pcm, the batch plumbing), tracks.h and meter.hip (the oversampler, tp_host).
 
 namespace mm {
 
@@ -55,7 +69,7 @@ __device__ __forceinline__ int ceil_ratio(int Ct, int P) {
 // one 16-byte store at span[thread * METER_FPT] (`span`: the plane at `base`, a 16-byte
 // boundary): the plane holds whole spans, so every entry up to the plane's end is written
 // (2^16 - 1 beyond N + 11, where P = 0).  The span's max P is folded into *tp with one atomic
-// per workgroup.  Without STORE it is the linked true peak alone (tracks.hip: ceil_tracks_peak).
+// per workgroup.  Without STORE it is the linked true peak alone (ceil_tracks_peak).
 template <int CH, typename T, bool STORE>
 __device__ __forceinline__ void ceil_need_span(const T *__restrict__ in, int64_t N, int64_t base, int Ct,
                                                uint16_t *__restrict__ span, unsigned *tp) {
@@ -99,14 +113,6 @@ __device__ __forceinline__ void ceil_need_span(const T *__restrict__ in, int64_t
         for (int w = 1; w < METER_THREADS / 64; ++w) best = max(best, red[w]);
         if (best) atomicMax(tp, (unsigned)best);
     }
-}
-
-// One workgroup per span: TP0 is folded into st->tp0.
-template <int CH, typename T>
-__global__ void __launch_bounds__(METER_THREADS) ceil_need_kernel(const T *__restrict__ in, int64_t N, int Ct,
-                                                                  uint16_t *__restrict__ plane, CeilDev *st) {
-    const int64_t base = (int64_t)blockIdx.x * METER_SPAN;
-    ceil_need_span<CH, T, true>(in, N, base, Ct, plane + base, &st->tp0);
 }
 
 typedef unsigned short ceil_u16x2 __attribute__((ext_vector_type(2)));
@@ -246,18 +252,73 @@ __device__ __forceinline__ void ceil_apply_span(T *__restrict__ pcm, int64_t N, 
     }
 }
 
+static_assert(TRACKS_METER_SPAN == METER_SPAN && TRACKS_CEIL_SPAN == CEIL_SPAN && TRACKS_MAX == MM_ALBUM_TRACKS,
+              "tracks.h restates the spans");
+
+struct TrackDev {  // one a track, uploaded once a call
+    void *pcm;
+    int64_t frames;
+};
+
+struct TrackPar {  // one a track, uploaded once a launch sequence
+    int C, Ct;     // the ceiling and C - CEIL_GUARD
+    int g;         // the trim
+    int active;    // 0: the track's workgroups exit at once
+};
+
+struct TracksArgs {
+    const TrackDev *tr;
+    const uint32_t *first_need, *first_apply;  // [n + 1] prefix sums of the two grids
+    const TrackPar *par;
+    uint16_t *plane;
+    CeilDev *st;     // [n]
+    unsigned *peak;  // [n] the linked true peak after the limiter / the trim
+    int n, W;
+    unsigned rcp;
+};
+
 template <int CH, typename T>
-__global__ void __launch_bounds__(CEIL_THREADS) ceil_apply_kernel(T *__restrict__ pcm, int64_t N, int64_t plane_len,
-                                                                  const uint16_t *__restrict__ plane, int C, int W,
-                                                                  unsigned rcp, CeilDev *st) {
-    ceil_apply_span<CH, T>(pcm, N, plane_len, plane, C, W, rcp, st, (int64_t)blockIdx.x * CEIL_SPAN);
+__global__ void __launch_bounds__(METER_THREADS) ceil_tracks_need_kernel(TracksArgs a) {
+    const int t = tracks_find(a.first_need, a.n, blockIdx.x);
+    const TrackPar p = a.par[t];
+    if (!p.active) return;
+    const TrackDev tr = a.tr[t];
+    const int64_t base = (int64_t)(blockIdx.x - a.first_need[t]) * METER_SPAN;
+    ceil_need_span<CH, T, true>(static_cast<const T *>(tr.pcm), tr.frames, base, p.Ct,
+                                a.plane + tracks_plane_off(a.first_need, t) + base, &a.st[t].tp0);
 }
 
-// The static trim: every sample by g (pointwise, in place).
+template <int CH, typename T>
+__global__ void __launch_bounds__(METER_THREADS) ceil_tracks_peak_kernel(TracksArgs a) {
+    const int t = tracks_find(a.first_need, a.n, blockIdx.x);
+    const TrackPar p = a.par[t];
+    if (!p.active || a.st[t].tp0 <= (unsigned)p.C) return;
+    const TrackDev tr = a.tr[t];
+    const int64_t base = (int64_t)(blockIdx.x - a.first_need[t]) * METER_SPAN;
+    ceil_need_span<CH, T, false>(static_cast<const T *>(tr.pcm), tr.frames, base, 0, nullptr, &a.peak[t]);
+}
+
+template <int CH, typename T>
+__global__ void __launch_bounds__(CEIL_THREADS) ceil_tracks_apply_kernel(TracksArgs a) {
+    const int t = tracks_find(a.first_apply, a.n, blockIdx.x);
+    const TrackPar p = a.par[t];
+    if (!p.active) return;
+    const TrackDev tr = a.tr[t];
+    const int64_t base = (int64_t)(blockIdx.x - a.first_apply[t]) * CEIL_SPAN;
+    ceil_apply_span<CH, T>(static_cast<T *>(tr.pcm), tr.frames, tracks_plane_len(tr.frames),
+                           a.plane + tracks_plane_off(a.first_need, t), p.C, a.W, a.rcp, &a.st[t], base);
+}
+
+// The static trim: the samples of the span's frames as one mono line
 template <typename T>
-__global__ void __launch_bounds__(256) ceil_trim_kernel(T *__restrict__ pcm, int64_t n, int g) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) ceil_scale<1, T>(pcm, i, g);
+__global__ void __launch_bounds__(CEIL_THREADS) ceil_tracks_trim_kernel(TracksArgs a, int channels) {
+    const int t = tracks_find(a.first_apply, a.n, blockIdx.x);
+    const TrackPar p = a.par[t];
+    if (!p.active) return;
+    const TrackDev tr = a.tr[t];
+    const int64_t base = (int64_t)(blockIdx.x - a.first_apply[t]) * CEIL_SPAN;
+    const int64_t s1 = (tr.frames < base + CEIL_SPAN ? tr.frames : base + CEIL_SPAN) * channels;
+    for (int64_t i = base * channels + threadIdx.x; i < s1; i += CEIL_THREADS) ceil_scale<1, T>(static_cast<T *>(tr.pcm), i, p.g);
 }
 
 }  // namespace mm
@@ -295,63 +356,144 @@ void ceiling_results(mm_ceiling *o, const CeilDev &s, int32_t tp_limited) {
 // the static trim of a residue tp_limited > C: provably under C (the file's head)
 int32_t ceiling_trim_gain(int32_t C, int32_t tp_limited) { return (int32_t)(((int64_t)(C - CEIL_GUARD) << 16) / tp_limited); }
 
+// The tracks of one call and the two grids over them: host tables, laid out once and uploaded
+// with the parameters of every ceiling that runs on them.
+struct CeilLayout {
+    int n = 0, kind = 0, channels = 0;
+    std::vector<TrackDev> tr;
+    std::vector<uint32_t> first_need, first_apply;
+};
+
+void ceiling_layout(void *const *d_pcm, int kind, const int64_t *frames, int n, int channels, CeilLayout &L) {
+    L.n = n;
+    L.kind = kind;
+    L.channels = channels;
+    L.tr.resize((size_t)n);
+    std::vector<int64_t> need((size_t)n), apply((size_t)n);
+    for (int t = 0; t < n; ++t) {
+        L.tr[(size_t)t] = TrackDev{d_pcm[t], frames[t]};
+        need[(size_t)t] = tracks_need_spans(frames[t]);
+        apply[(size_t)t] = tracks_apply_spans(frames[t]);
+    }
+    L.first_need.resize((size_t)n + 1);
+    L.first_apply.resize((size_t)n + 1);
+    tracks_prefix(need.data(), n, L.first_need.data());
+    tracks_prefix(apply.data(), n, L.first_apply.data());
+}
+
+// The ceiling over the tracks of a layout, in place: every track t with Cs[t] != 0 held under
+// Cs[t] and out[t] filled; the other tracks and their out[t] are not touched.  One upload (the
+// tracks, their parameters, the grids) and one memset (the result blocks, the peaks), then
+// need, apply and the peak behind one synchronisation; the trims and their peak behind one
+// more, when a track is left with a residue.  Nothing to do (no track with a ceiling and
+// frames): nothing is queued.  Arguments already checked.  Synchronous on return.
+int tracks_ceiling(mm_ctx *c, const CeilLayout &L, const int32_t *Cs, int32_t W, mm_ceiling *out) {
+    const int n = L.n;
+    const size_t N = (size_t)n, fb = (N + 1) * sizeof(uint32_t);
+    const size_t o_par = N * sizeof(TrackDev), o_need = o_par + N * sizeof(TrackPar), o_apply = o_need + fb;
+    std::vector<char> tab(o_apply + fb);  // (lives until the synchronisation behind its upload)
+    TrackPar *par = reinterpret_cast<TrackPar *>(tab.data() + o_par);
+    bool any = false;
+    for (int t = 0; t < n; ++t) {
+        par[t] = TrackPar{};
+        if (!Cs[t]) continue;
+        ceiling_clear(&out[t], L.tr[(size_t)t].frames, L.channels, Cs[t], W);
+        if (L.tr[(size_t)t].frames == 0) continue;
+        par[t] = TrackPar{Cs[t], Cs[t] - CEIL_GUARD, 0, 1};
+        any = true;
+    }
+    if (!any) return MM_OK;
+    memcpy(tab.data(), L.tr.data(), o_par);
+    memcpy(tab.data() + o_need, L.first_need.data(), fb);
+    memcpy(tab.data() + o_apply, L.first_apply.data(), fb);
+    char *d_tab, *d_res;
+    const size_t o_peak = N * sizeof(CeilDev), res_bytes = o_peak + N * sizeof(unsigned);
+    TracksArgs a{};
+    RET(get_buf(c, "ceil_tab", tab.size(), &d_tab));
+    RET(get_buf(c, "ceil_res", res_bytes, &d_res));
+    RET(get_buf(c, "ceil_r", (size_t)tracks_plane_total(L.first_need.data(), n), &a.plane));
+    HIPCHK(c, hipMemcpyAsync(d_tab, tab.data(), tab.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_res, 0, res_bytes, c->stream));
+    a.tr = reinterpret_cast<const TrackDev *>(d_tab);
+    a.par = reinterpret_cast<const TrackPar *>(d_tab + o_par);
+    a.first_need = reinterpret_cast<const uint32_t *>(d_tab + o_need);
+    a.first_apply = reinterpret_cast<const uint32_t *>(d_tab + o_apply);
+    a.st = reinterpret_cast<CeilDev *>(d_res);
+    a.peak = reinterpret_cast<unsigned *>(d_res + o_peak);
+    a.n = n;
+    a.W = W;
+    a.rcp = (unsigned)(((uint64_t)1 << 32) / (uint64_t)(2 * W + 1));
+    const dim3 gn(L.first_need[N]), bn(METER_THREADS), ga(L.first_apply[N]), ba(CEIL_THREADS);
+    auto peak = [&]() {
+        return dispatch_pcm(L.kind, L.channels, [&](auto ch, auto t) {
+            using T = decltype(t);
+            return launch(c, "ceil_tracks_peak", ceil_tracks_peak_kernel<ch, T>, gn, bn, 0, a);
+        });
+    };
+    RET(dispatch_pcm(L.kind, L.channels, [&](auto ch, auto t) {
+        using T = decltype(t);
+        RET(launch(c, "ceil_tracks_need", ceil_tracks_need_kernel<ch, T>, gn, bn, 0, a));
+        return launch(c, "ceil_tracks_apply", ceil_tracks_apply_kernel<ch, T>, ga, ba, 0, a);
+    }));
+    RET(peak());
+    std::vector<char> hr(res_bytes);
+    const CeilDev *hs = reinterpret_cast<const CeilDev *>(hr.data());
+    const unsigned *hp = reinterpret_cast<const unsigned *>(hr.data() + o_peak);
+    HIPCHK(c, hipMemcpyAsync(hr.data(), d_res, res_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    bool trim = false;
+    for (int t = 0; t < n; ++t) {  // (everything queued has run: the parameters become the trim's)
+        if (!par[t].active) continue;
+        const int32_t C = Cs[t];
+        mm_ceiling *o = &out[t];
+        const int32_t tp0 = (int32_t)hs[t].tp0;
+        ceiling_results(o, hs[t], tp0 <= C ? tp0 : (int32_t)hp[t]);  // (untouched: ceil_tracks_peak skipped it)
+        par[t].active = o->tp_limited_q28 > C;
+        if (par[t].active) {  // the residue: one static trim
+            par[t].g = o->trim_q16 = ceiling_trim_gain(C, o->tp_limited_q28);
+            trim = true;
+        }
+    }
+    if (trim) {
+        HIPCHK(c, hipMemcpyAsync(d_tab + o_par, par, N * sizeof(TrackPar), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemsetAsync(a.peak, 0, N * sizeof(unsigned), c->stream));
+        RET(dispatch_pcm(L.kind, 1, [&](auto, auto t) {
+            using T = decltype(t);
+            return launch(c, "ceil_tracks_trim", ceil_tracks_trim_kernel<T>, ga, ba, 0, a, L.channels);
+        }));
+        RET(peak());
+        HIPCHK(c, hipMemcpyAsync(hr.data() + o_peak, a.peak, N * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (int t = 0; t < n; ++t)
+            if (par[t].active) out[t].tp_out_q28 = (int32_t)hp[t];
+    }
+    resolve_events(c);
+    return MM_OK;
+}
+
+// Refuses what is not a batch to hold under ceilings, before anything is queued.
+int batch_ceiling_check(mm_ctx *c, const void *const *pcm, int kind, const int64_t *frames, int n, int channels, const int32_t *C,
+                        int32_t W) {
+    return batch_check(c, pcm, kind, frames, n, channels, C != nullptr,
+                       [&](int t) { return ceiling_bad_args(frames[t], channels, C[t], W); });
+}
+
+int batch_ceiling_device(mm_ctx *c, void *const *d_pcm, int kind, const int64_t *frames, int n, int channels,
+                         const int32_t *C, int32_t W, mm_ceiling *out) {
+    CeilLayout L;
+    ceiling_layout(d_pcm, kind, frames, n, channels, L);
+    return tracks_ceiling(c, L, C, W, out);
+}
+
 }  // namespace
 
-// The ceiling on a device-resident signal, in place (synchronous on return): need, apply
-// and the meter pass behind one sync; the trim and its meter pass behind one more.
+// The ceiling on a device-resident signal, in place (synchronous on return): a batch of one.
 static int ceiling_device(mm_ctx *c, void *d_pcm, int kind, int64_t frames, int channels, int32_t C, int32_t W,
                           mm_ceiling *out) {
     if (!c || !out || (frames > 0 && !d_pcm)) return set_err(c, MM_ERR_ARG, "bad arguments");
     if (!pcm_kind_ok(kind)) return set_err(c, MM_ERR_ARG, PCM_BAD_KIND, kind);
     if (const char *why = ceiling_bad_args(frames, channels, C, W)) return set_err(c, MM_ERR_ARG, "%s", why);
-    ceiling_clear(out, frames, channels, C, W);
-    if (frames == 0) return MM_OK;
-    const int Ct = C - CEIL_GUARD;
-    const int64_t plane_len = tracks_plane_len(frames);
-    uint16_t *plane;
-    CeilDev *st;
-    MeterDev *res;
-    RET(get_buf(c, "ceil_r", (size_t)plane_len, &plane));
-    RET(get_buf(c, "ceil_res", 1, &st));
-    RET(get_buf(c, "meter_res", 1, &res));
-    HIPCHK(c, hipMemsetAsync(st, 0, sizeof(CeilDev), c->stream));
-    const dim3 gn((unsigned)tracks_need_spans(frames)), bn(METER_THREADS);
-    const dim3 ga((unsigned)tracks_apply_spans(frames)), ba(CEIL_THREADS);
-    const unsigned rcp = (unsigned)(((uint64_t)1 << 32) / (uint64_t)(2 * W + 1));
-    RET(dispatch_pcm(kind, channels, [&](auto ch, auto t) {
-        using T = decltype(t);
-        T *p = static_cast<T *>(d_pcm);
-        RET(launch(c, "ceil_need", ceil_need_kernel<ch, T>, gn, bn, 0, (const T *)p, frames, Ct, plane, st));
-        return launch(c, "ceil_apply", ceil_apply_kernel<ch, T>, ga, ba, 0, p, frames, plane_len, (const uint16_t *)plane,
-                      (int)C, (int)W, rcp, st);
-    }));
-    RET(meter_launch(c, d_pcm, kind, frames, channels, res));
-    CeilDev hs;
-    MeterDev hm;
-    HIPCHK(c, hipMemcpyAsync(&hs, st, sizeof hs, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(&hm, res, sizeof hm, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    auto linked = [&](const MeterDev &m) {
-        int32_t tp = 0;
-        for (int ch = 0; ch < channels; ++ch) tp = std::max(tp, (int32_t)(m.key[ch] >> 32));
-        return tp;
-    };
-    ceiling_results(out, hs, linked(hm));
-    if (out->tp_limited_q28 > C) {  // the residue: one static trim
-        const int gt = ceiling_trim_gain(C, out->tp_limited_q28);
-        const int64_t n = frames * channels;
-        RET(dispatch_pcm(kind, 1, [&](auto, auto t) {  // (pointwise: the samples as one mono line)
-            using T = decltype(t);
-            return launch(c, "ceil_trim", ceil_trim_kernel<T>, dim3(pw_blocks(n)), dim3(256), 0, static_cast<T *>(d_pcm), n, gt);
-        }));
-        RET(meter_launch(c, d_pcm, kind, frames, channels, res));
-        HIPCHK(c, hipMemcpyAsync(&hm, res, sizeof hm, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        out->trim_q16 = gt;
-        out->tp_out_q28 = linked(hm);
-    }
-    resolve_events(c);
-    return MM_OK;
+    return batch_ceiling_device(c, &d_pcm, kind, &frames, 1, channels, &C, W, out);
 }
 
 extern "C" {
@@ -381,6 +523,29 @@ int mm_ceiling_pcm(mm_ctx *c, void *pcm, int kind, int64_t frames, int channels,
     return pcm_download(c, pcm, dio, bytes);
 }
 
+int mm_batch_ceiling_device(mm_ctx *c, void *const *d_pcm, int kind, const int64_t *frames, int n, int channels,
+                            const int32_t *ceiling_q28, int32_t window, mm_ceiling *out) {
+    if (!c) return MM_ERR_ARG;
+    if (!out) return set_err(c, MM_ERR_ARG, "bad arguments");
+    RET(batch_ceiling_check(c, d_pcm, kind, frames, n, channels, ceiling_q28, window));
+    HIPCHK(c, hipSetDevice(c->device));
+    return batch_ceiling_device(c, d_pcm, kind, frames, n, channels, ceiling_q28, window, out);
+}
+
+int mm_batch_ceiling_pcm(mm_ctx *c, void *const *pcm, int kind, const int64_t *frames, int n, int channels,
+                         const int32_t *ceiling_q28, int32_t window, mm_ceiling *out) {
+    if (!c) return MM_ERR_ARG;
+    if (!out) return set_err(c, MM_ERR_ARG, "bad arguments");
+    RET(batch_ceiling_check(c, pcm, kind, frames, n, channels, ceiling_q28, window));
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<void *> d;
+    RET(album_upload(c, "batch_io", pcm, kind, frames, n, channels, d));
+    RET(batch_ceiling_device(c, d.data(), kind, frames, n, channels, ceiling_q28, window, out));
+    std::vector<char> pick((size_t)n);  // (an untouched track is not copied back)
+    for (int t = 0; t < n; ++t) pick[(size_t)t] = out[t].tp_in_q28 > ceiling_q28[t];
+    return batch_download(c, pcm, d, kind, frames, n, channels, pick.data());
+}
+
 int mm_last_ceilings(mm_ctx *c, int cap, mm_ceiling *out) {
     if (!c || cap < 0 || (cap > 0 && !out)) return set_err(c, MM_ERR_ARG, "bad arguments");
     if (c->ceilings.empty()) return set_err(c, MM_ERR_STATE, "the last master call set no ceiling");
@@ -390,7 +555,7 @@ int mm_last_ceilings(mm_ctx *c, int cap, mm_ceiling *out) {
 }
 
 // The definition restated in plain C++ on the host (no context, no GPU), in place on
-// interleaved int16: what the three kernels must reproduce, samples and statistics.
+// interleaved int16: what the kernels must reproduce, samples and statistics.
 int mm_ceiling_host(int16_t *pcm, int64_t frames, int channels, int32_t C, int32_t W, mm_ceiling *out) {
     if (!out || (frames > 0 && !pcm) || ceiling_bad_args(frames, channels, C, W)) return MM_ERR_ARG;
     ceiling_clear(out, frames, channels, C, W);

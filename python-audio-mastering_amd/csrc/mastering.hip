@@ -6,8 +6,8 @@
 // per-stage operators) and loudness.hip (the loudness tail, its operator and the
 // time-sharded entry points) follow the chain, before the units that call
 // line_loudness; wav.hip, comm.hip, then pcm16.h, meter.hip, r128.hip, qc.hip, spectrum.hip, ceiling.hip, level.hip,
-// resample.hip (with mm_master* / mm_deliver*: a master call with or without a delivery) and album.hip
-// come at the end.
+// resample.hip (with mm_master* / mm_deliver*: a master call with or without a delivery), fir.hip, album.hip
+// and tracks.hip (the level's driver and the end of a master call) come at the end.
 #include <rccl/rccl.h>
 
 #include <algorithm>
@@ -32,7 +32,7 @@ using namespace mm;
 #include "context.h"
 #include "decode.hip"
 
-// ceiling.hip: the end of a master call for delivered buffer i, the level (a delivery's) or the
+// tracks.hip: the end of a master call for delivered buffer i, the level (a delivery's) or the
 // ceiling and then the report
 static int finish_delivered(mm_ctx *c, void *d_out, int kind, int64_t frames, int channels, int i, int32_t ceiling_q28,
                             int32_t window, int meter_on, const mm_job *loud, int32_t level_clu = 0);

@@ -3,8 +3,9 @@
 // kind MM_OUT_F32 holds int16 / 32768 exactly, interleaved, with 1 or 2 channels.  Device:
 // a sample and a frame decoded to ints and encoded back, and the wave reductions of the
 // stages' statistics.  Host: the bytes of a sample, the refusal of a (kind, channels,
-// frames) and the choice of a kernel's instantiation.  Included by mastering.hip after
-// ops.hip and before meter.hip.
+// frames), the choice of a kernel's instantiation, and for the stages' entries over n tracks
+// the tracks' way to the device and back and the refusal of a batch.  Included by
+// mastering.hip after ops.hip and before meter.hip.
 #pragma once
 
 namespace mm {
@@ -113,6 +114,54 @@ int pcm_upload(mm_ctx *c, const char *name, const void *pcm, size_t bytes, char 
 int pcm_download(mm_ctx *c, void *pcm, const char *d, size_t bytes) {
     if (bytes) HIPCHK(c, hipMemcpyAsync(pcm, d, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MM_OK;
+}
+
+// n host tracks into one context buffer, each on a 16-byte boundary: their device pointers
+// (pcm null: laid out, nothing copied)
+int album_upload(mm_ctx *c, const char *name, const void *const *pcm, int kind, const int64_t *frames, int n, int channels,
+                 std::vector<void *> &d) {
+    size_t total = 0;
+    for (int t = 0; t < n; ++t) total += (pcm_bytes(kind, frames[t], channels) + 15) & ~(size_t)15;
+    char *base;
+    RET(get_buf(c, name, std::max<size_t>(total, 1), &base));
+    d.resize((size_t)n);
+    for (int t = 0; t < n; ++t) {
+        const size_t bytes = pcm_bytes(kind, frames[t], channels);
+        d[(size_t)t] = base;
+        if (bytes && pcm) HIPCHK(c, hipMemcpyAsync(base, pcm[t], bytes, hipMemcpyHostToDevice, c->stream));
+        base += (bytes + 15) & ~(size_t)15;
+    }
+    return MM_OK;
+}
+
+// d[t] back into pcm[t] for the tracks `pick` names (null: all), synchronous
+int batch_download(mm_ctx *c, void *const *pcm, const std::vector<void *> &d, int kind, const int64_t *frames, int n,
+                   int channels, const char *pick) {
+    for (int t = 0; t < n; ++t) {
+        const size_t bytes = pcm_bytes(kind, frames[t], channels);
+        if (bytes && (!pick || pick[t])) HIPCHK(c, hipMemcpyAsync(pcm[t], d[(size_t)t], bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MM_OK;
+}
+
+// Refuses what is not a batch of n tracks for a stage (MM_ERR_ARG, the sentence in mm_last_error
+// names the track), before anything is queued.  rest: the stage's other pointers are there;
+// bad(t): why the stage refuses track t, or null.  Every segmented stage counts frames in 32
+// bits over the whole launch.
+template <typename Bad>
+int batch_check(mm_ctx *c, const void *const *pcm, int kind, const int64_t *frames, int n, int channels, bool rest, Bad &&bad) {
+    if (n < 1 || n > MM_ALBUM_TRACKS) return set_err(c, MM_ERR_ARG, "batch: %d tracks out of range [1, %d]", n, MM_ALBUM_TRACKS);
+    if (!pcm || !frames || !rest) return set_err(c, MM_ERR_ARG, "bad arguments");
+    if (!pcm_kind_ok(kind)) return set_err(c, MM_ERR_ARG, PCM_BAD_KIND, kind);
+    int64_t total = 0;
+    for (int t = 0; t < n; ++t) {
+        if (const char *why = bad(t)) return set_err(c, MM_ERR_ARG, "batch: track %d: %s", t, why);
+        if (frames[t] > 0 && !pcm[t]) return set_err(c, MM_ERR_ARG, "batch: track %d: null pointer", t);
+        total += frames[t];
+        if (total >= (int64_t)1 << 31) return set_err(c, MM_ERR_ARG, "batch: track %d: 2^31 frames or more in all", t);
+    }
     return MM_OK;
 }
 

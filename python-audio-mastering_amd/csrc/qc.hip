@@ -26,9 +26,9 @@
 //
 // The grid is the need grid of tracks.h (tracks_need_spans: it counts m in [0, frames + 11), so
 // a track's last span may hold no frame and then writes an empty record, the operator's
-// identity).  Included at the end of mastering.hip after r128.hip (r128_bound, r128_hop_of: the
-// hops are the R 128 report's) and before tracks.hip, whose finish_delivered runs the report
-// beside the other two; the launch over many tracks (qc_tracks_kernel) is in tracks.hip.
+// identity), laid over the spans of all tracks of a call: a single signal is a call of one
+// track.  Included at the end of mastering.hip after r128.hip (r128_bound, r128_hop_of: the
+// hops are the R 128 report's).
 
 namespace mm {
 
@@ -378,11 +378,14 @@ __device__ __forceinline__ void qc_span(const T *__restrict__ in, const QcTrack 
     }
 }
 
-// one signal: workgroup b is its span b
+// qc_span over the spans of all tracks: a record lands among its track's own, a hop piece in its
+// track's own rows, and every frame index is the track's
 template <int CH, typename T>
-__global__ void __launch_bounds__(QC_THREADS) qc_kernel(QcLaunch L) {
-    const QcTrack tr = L.tr[0];
-    qc_span<CH, T>(static_cast<const T *>(tr.pcm), tr, (int64_t)blockIdx.x, L.rate, L.q, L.r, L.rec, L.hops);
+__global__ void __launch_bounds__(QC_THREADS) qc_tracks_kernel(QcLaunch L) {
+    const int t = tracks_find(L.first, L.n, blockIdx.x);
+    const QcTrack tr = L.tr[t];
+    qc_span<CH, T>(static_cast<const T *>(tr.pcm), tr, (int64_t)(blockIdx.x - L.first[t]), L.rate, L.q, L.r,
+                   L.rec + L.first[t], L.hops + 3 * tr.hop0);
 }
 
 // Workgroup t folds track t's records in span order: thread i the i-th contiguous chunk, then a
@@ -424,13 +427,11 @@ const char *qc_refusal(int channels, int64_t frames, int rate, int q, int r) {
 }
 
 // The reports of n checked device-resident tracks into out[n] (synchronous on return): one
-// upload of the track table, one memset of the results and the hop table, the span launch
-// `spans(L, grid)` (one track: qc_kernel; many: tracks.hip's qc_tracks_kernel), the fold launch
-// and one read-back, then the tail of step 5.  hops_out (may be null): the tables of all tracks
-// back to back.  The host tables live until the synchronisation.
-template <typename Spans>
-int qc_run(mm_ctx *c, const void *const *d_pcm, const int64_t *frames, int n, int channels, int rate, int q, int r,
-           mm_qc *out, int64_t *hops_out, Spans &&spans) {
+// upload of the track table, one memset of the results and the hop table, the span launch, the
+// fold launch and one read-back, then the tail of step 5.  hops_out (may be null): the tables
+// of all tracks back to back.  The host tables live until the synchronisation.
+int qc_run(mm_ctx *c, const void *const *d_pcm, int kind, const int64_t *frames, int n, int channels, int rate, int q, int r,
+           mm_qc *out, int64_t *hops_out) {
     const size_t N = (size_t)n;
     std::vector<QcTrack> tr(N);
     std::vector<int64_t> wgs(N);
@@ -463,7 +464,11 @@ int qc_run(mm_ctx *c, const void *const *d_pcm, const int64_t *frames, int n, in
     L.r = r;
     HIPCHK(c, hipMemcpyAsync(d_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(d_out, 0, out_bytes, c->stream));
-    if (grid) RET(spans(L, grid));
+    if (grid)
+        RET(dispatch_pcm(kind, channels, [&](auto ch, auto t) {
+            using T = decltype(t);
+            return launch(c, "qc_tracks", qc_tracks_kernel<ch, T>, dim3(grid), dim3(QC_THREADS), 0, L);
+        }));
     RET(launch(c, "qc_fold", qc_fold_kernel, dim3((unsigned)n), dim3(QC_THREADS), 0, L));
     HIPCHK(c, hipMemcpyAsync(back.data(), d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -476,20 +481,33 @@ int qc_run(mm_ctx *c, const void *const *d_pcm, const int64_t *frames, int n, in
     return MM_OK;
 }
 
+// Refuses what is not a batch to check (MM_ERR_ARG, the sentence names the track), before
+// anything is queued.
+int batch_qc_check(mm_ctx *c, const void *const *pcm, int kind, const int64_t *frames, int n, int channels, int rate, int q,
+                   int r, const mm_qc *out) {
+    return batch_check(c, pcm, kind, frames, n, channels, out != nullptr,
+                       [&](int t) { return qc_refusal(channels, frames[t], rate, q, r); });
+}
+
+// The QC reports of n checked device-resident tracks (synchronous on return).  Only c->qcs is
+// set: the levels, ceilings and R 128 reports of the context's last call stay.
+int batch_qc_device(mm_ctx *c, const void *const *d_pcm, int kind, const int64_t *frames, int n, int channels, int rate, int q,
+                    int r, mm_qc *out) {
+    RET(qc_run(c, d_pcm, kind, frames, n, channels, rate, q, r, out, nullptr));
+    c->qcs.assign(out, out + n);
+    return MM_OK;
+}
+
 }  // namespace
 
-// The QC report of a device-resident signal (synchronous on return).
+// The QC report of a device-resident signal (synchronous on return): a call of one track, which
+// leaves the context's results as they are.
 static int qc_device(mm_ctx *c, const void *d_pcm, int kind, int64_t frames, int channels, int rate, int q, int r,
                      mm_qc *out, int64_t *hops_out) {
     if (!c || !out || (frames > 0 && !d_pcm)) return set_err(c, MM_ERR_ARG, "bad arguments");
     if (!pcm_kind_ok(kind)) return set_err(c, MM_ERR_ARG, PCM_BAD_KIND, kind);
     if (const char *why = qc_refusal(channels, frames, rate, q, r)) return set_err(c, MM_ERR_ARG, "QC: %s", why);
-    return qc_run(c, &d_pcm, &frames, 1, channels, rate, q, r, out, hops_out, [&](const QcLaunch &L, uint32_t grid) {
-        return dispatch_pcm(kind, channels, [&](auto ch, auto t) {
-            using T = decltype(t);
-            return launch(c, "qc", qc_kernel<ch, T>, dim3(grid), dim3(QC_THREADS), 0, L);
-        });
-    });
+    return qc_run(c, &d_pcm, kind, &frames, 1, channels, rate, q, r, out, hops_out);
 }
 
 extern "C" {
@@ -599,6 +617,24 @@ int mm_qc_pcm(mm_ctx *c, const void *pcm, int kind, int64_t frames, int channels
     char *din;
     RET(pcm_upload(c, "qc_in", pcm, pcm_bytes(kind, frames, channels), &din));
     return qc_device(c, din, kind, frames, channels, rate, silence_lsb, min_run, out, hops_out);
+}
+
+int mm_batch_qc_device(mm_ctx *c, const void *const *d_pcm, int kind, const int64_t *frames, int n, int channels,
+                       int32_t rate, int32_t silence_lsb, int32_t min_run, mm_qc *out) {
+    if (!c) return MM_ERR_ARG;
+    RET(batch_qc_check(c, d_pcm, kind, frames, n, channels, rate, silence_lsb, min_run, out));
+    HIPCHK(c, hipSetDevice(c->device));
+    return batch_qc_device(c, d_pcm, kind, frames, n, channels, rate, silence_lsb, min_run, out);
+}
+
+int mm_batch_qc_pcm(mm_ctx *c, const void *const *pcm, int kind, const int64_t *frames, int n, int channels, int32_t rate,
+                    int32_t silence_lsb, int32_t min_run, mm_qc *out) {
+    if (!c) return MM_ERR_ARG;
+    RET(batch_qc_check(c, pcm, kind, frames, n, channels, rate, silence_lsb, min_run, out));
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<void *> d;
+    RET(album_upload(c, "batch_qc_in", pcm, kind, frames, n, channels, d));
+    return batch_qc_device(c, d.data(), kind, frames, n, channels, rate, silence_lsb, min_run, out);
 }
 
 int mm_last_qc(mm_ctx *c, int cap, mm_qc *out) {

@@ -9,9 +9,11 @@
 // end in: they differ in e[] only.  Its steps 4-7 are r128_figures, which an album's pooled
 // windows end in too (album.hip).
 //
-// The GPU pass is ONE launch of the K-weighting with lookback.h's carry, a lane per tile of
-// R128_TILE frames, followed by a fixed-order reduction of the tile partials to the hops
-// (no floating-point atomics: two runs are bit-identical).  A lane runs every channel of
+// The GPU pass (AlbumPass: a single track is the pass over one track, an album or a batch the
+// pass over n) is ONE launch of the K-weighting with lookback.h's carry over the workgroups of
+// all its tracks, a lane per tile of R128_TILE frames, followed by a fixed-order reduction of
+// the tile partials to the hops (no floating-point atomics: two runs are bit-identical), and one
+// read-back of the hop energies and the look-back's error word whatever n.  A lane runs every channel of
 // its tile: mono is a 4-dimensional state (lb_carry<4, 1>), stereo ONE 8-dimensional state
 // of two independent 2-section cascades, L | R (lb_carry<8, 1, 2>, the block structure of
 // the crossover's LP | HP).  The pass owns its geometry: the transition tables are built
@@ -25,8 +27,7 @@
 // the int16 grid, and store them frame-major with a row stride of LB_THREADS + 1 dwords,
 // so the stores are at most two to a bank and a lane's reads of its own frames none.
 //
-// Included at the end of mastering.hip (one translation unit) after meter.hip, before
-// tracks.hip, whose finish_delivered runs the report next to the meter.
+// Included at the end of mastering.hip (one translation unit) after meter.hip.
 
 namespace mm {
 
@@ -54,7 +55,7 @@ __host__ __device__ __forceinline__ int64_t r128_bound(int64_t i, int rate) { re
 __host__ __device__ __forceinline__ int64_t r128_hop_of(int64_t f, int rate) { return (10 * f + 9) / rate; }
 
 struct R128Args {
-    int64_t N, G, H;    // frames, tiles, complete hops
+    int64_t N, G;       // frames, tiles
     int rate;
     double sos[2][5];
     double *part;       // [G][2] energies of the tile's frames in its first hop and in the next
@@ -116,7 +117,7 @@ __device__ __forceinline__ void r128_pass(const R128Args &a, const T *__restrict
 // a.part_hop the line's own partials.  The line's first tile resets the carry, so a block
 // waits on predecessors back to the line's first block only, which publishes an inclusive
 // prefix at once: what a workgroup computes depends on its line alone, wherever the line
-// lies in the launch (the album pass below puts many lines into one).
+// lies in the launch (the pass below puts many lines into one).
 template <int CH, typename T>
 __device__ __forceinline__ void r128_kweight_block(const R128Args &a, const T *__restrict__ in, const LbArgs &lb, int blk,
                                                    int64_t g0, double *smem, uint32_t *stage) {
@@ -139,15 +140,6 @@ __device__ __forceinline__ void r128_kweight_block(const R128Args &a, const T *_
     a.part_hop[g] = h0;
 }
 
-template <int CH, typename T>
-__global__ void __launch_bounds__(LB_THREADS) r128_kweight_kernel(R128Args a, const T *__restrict__ in, LbArgs lb) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    uint32_t *stage = reinterpret_cast<uint32_t *>(smem + lb_lds_bytes<8, 1>() / sizeof(double));
-    __shared__ int ticket_slot;
-    const int blk = lb_ticket(lb, &ticket_slot);
-    r128_kweight_block<CH, T>(a, in, lb, blk, (int64_t)blk * LB_THREADS, smem, stage);
-}
-
 // Hop s of a line from its tile partials: lane k takes tiles g0 + k, g0 + k + 64, ..., then
 // a butterfly; the order is fixed by the line's geometry alone.
 __device__ __forceinline__ double r128_hop_sum(const double *part, const int64_t *part_hop, int64_t s, int rate, int lane) {
@@ -162,22 +154,12 @@ __device__ __forceinline__ double r128_hop_sum(const double *part, const int64_t
     return acc;
 }
 
-// Tile partials to hop energies, e[s] for s < H (so frames at or after B[H] belong to no
-// hop): one wave per hop.
-__global__ void __launch_bounds__(256) r128_reduce_kernel(R128Args a, double *e) {
-    const int64_t s = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (s >= a.H) return;  // wave-uniform
-    const double acc = r128_hop_sum(a.part, a.part_hop, s, a.rate, lane);
-    if (lane == 0) e[s] = acc;
-}
-
-// ---- the album pass: every track of an album in ONE launch of either kernel (album.hip).
-// The tracks stay where they are.  Track t owns ceil(G_t / LB_THREADS) consecutive
-// workgroups from wg0 and the partials of wg0 * LB_THREADS tiles on; its hops are
-// e[hop0 .. hop0 + H_t).  Inside its track a workgroup is r128_kweight_block as the
-// stand-alone launch runs it: the same tiles, staging and chain of predecessors back to
-// the block that resets, so a track's hop energies are those of r128_hops on it alone.
+// ---- the pass: every track of a call in ONE launch of either kernel.  The tracks stay where
+// they are.  Track t owns ceil(G_t / LB_THREADS) consecutive workgroups from wg0 and the
+// partials of wg0 * LB_THREADS tiles on; its hops are e[hop0 .. hop0 + H_t).  Inside its track
+// a workgroup is r128_kweight_block on the track's own tiles, staging and chain of
+// predecessors back to the block that resets, so a track's hop energies are those of a pass
+// over it alone.
 struct R128Track {
     const void *pcm;
     int64_t N;     // frames
@@ -205,7 +187,6 @@ __global__ void __launch_bounds__(LB_THREADS) r128_album_kweight_kernel(R128Albu
     R128Args a;
     a.N = tr.N;
     a.G = (tr.N + R128_TILE - 1) / R128_TILE;
-    a.H = 0;  // (the reduction's)
     a.rate = al.rate;
 #pragma unroll
     for (int k = 0; k < 10; ++k) a.sos[k / 5][k % 5] = al.sos[k / 5][k % 5];
@@ -215,7 +196,8 @@ __global__ void __launch_bounds__(LB_THREADS) r128_album_kweight_kernel(R128Albu
 }
 
 // e[s] for s < H: a wave finds the track of its hop in the prefix hop0 (the last track that
-// starts at or before s: a track without hops is never found), then sums as r128_reduce_kernel.
+// starts at or before s: a track without hops is never found); one wave a hop, so frames at or
+// after a track's B[H_t] belong to no hop.
 __global__ void __launch_bounds__(256) r128_album_reduce_kernel(R128AlbumArgs al, double *e) {
     const int64_t s = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -383,37 +365,81 @@ int r128_upload_tables(mm_ctx *c, const double sos[2][5], int channels, LbArgs &
     return MM_OK;
 }
 
-// The hop energies of a device-resident signal into `e` (H = floor(10 N / R) of them;
-// none: nothing is launched).  Arguments already checked.  Synchronous on return.
-int r128_hops(mm_ctx *c, const void *d_pcm, int kind, int64_t frames, int channels, int rate, const double sos[2][5],
-              std::vector<double> &e) {
-    R128Args a{};
-    a.N = frames;
-    a.G = (frames + R128_TILE - 1) / R128_TILE;
-    a.H = 10 * frames / rate;
-    a.rate = rate;
-    memcpy(a.sos, sos, sizeof a.sos);
-    e.assign((size_t)a.H, 0.0);
-    if (a.H == 0) return MM_OK;
-    double *d_e;
-    RET(get_buf(c, "r128_part", (size_t)a.G * 2, &a.part));
-    RET(get_buf(c, "r128_part_hop", (size_t)a.G, &a.part_hop));
-    RET(get_buf(c, "r128_hops", (size_t)a.H, &d_e));
+// The measuring pass over n >= 1 tracks, laid out once: every track on a workgroup boundary,
+// its hops at hop0[t] of the pass's.  The host table lives as long as the pass, so its upload
+// needs no synchronisation of its own: album_pass_hops, which every prepared pass with a hop
+// runs, ends in one.
+struct AlbumPass {
+    R128AlbumArgs a{};
+    unsigned nblk = 0;
+    int kind = 0, channels = 0;
+    std::vector<int64_t> hops;  // [n] H_t
+    std::vector<char> tab;      // the tracks, the track of every workgroup, the zero error word: one upload
+    unsigned *d_error = nullptr;  // the look-back's error word
+    bool zeroed = false;          // by the table's upload: the first measurement needs no memset
+    double *d_e = nullptr;
+};
+
+// Lays the pass out and queues the upload of its table.  Arguments already checked.
+int album_pass_prepare(mm_ctx *c, const void *const *d_pcm, int kind, const int64_t *frames, int n, int channels, int rate,
+                       const double sos[2][5], AlbumPass &p) {
+    int64_t wg = 0, hop = 0;
+    p.hops.resize((size_t)n);
+    std::vector<R128Track> tracks((size_t)n);
+    std::vector<int> wg_track;
+    for (int t = 0; t < n; ++t) {
+        const int64_t G = (frames[t] + R128_TILE - 1) / R128_TILE, nwg = (G + LB_THREADS - 1) / LB_THREADS;
+        tracks[(size_t)t] = R128Track{d_pcm[t], frames[t], wg, hop};
+        wg_track.insert(wg_track.end(), (size_t)nwg, t);
+        p.hops[(size_t)t] = 10 * frames[t] / rate;
+        wg += nwg;
+        hop += p.hops[(size_t)t];
+    }
+    p.nblk = (unsigned)wg;
+    p.kind = kind;
+    p.channels = channels;
+    p.a.n = n;
+    p.a.rate = rate;
+    p.a.H = hop;
+    memcpy(p.a.sos, sos, sizeof p.a.sos);
+    if (hop == 0) return MM_OK;  // nothing to measure: nothing is queued
+    const size_t tb = (size_t)n * sizeof(R128Track), o_err = tb + (size_t)wg * sizeof(int);
+    p.tab.assign(o_err + sizeof(unsigned), 0);
+    memcpy(p.tab.data(), tracks.data(), tb);
+    memcpy(p.tab.data() + tb, wg_track.data(), (size_t)wg * sizeof(int));
+    char *d_tab;
+    RET(get_buf(c, "album_tab", p.tab.size(), &d_tab));
+    RET(get_buf(c, "album_part", (size_t)wg * LB_THREADS * 2, &p.a.part));
+    RET(get_buf(c, "album_part_hop", (size_t)wg * LB_THREADS, &p.a.part_hop));
+    RET(get_buf(c, "album_hops", (size_t)hop, &p.d_e));
+    HIPCHK(c, hipMemcpyAsync(d_tab, p.tab.data(), p.tab.size(), hipMemcpyHostToDevice, c->stream));
+    p.a.tracks = reinterpret_cast<const R128Track *>(d_tab);
+    p.a.wg_track = reinterpret_cast<const int *>(d_tab + tb);
+    p.d_error = reinterpret_cast<unsigned *>(d_tab + o_err);
+    p.zeroed = true;
+    return MM_OK;
+}
+
+// One measurement: the hop energies of the pass's tracks into `e`, track after track
+// (H_t = floor(10 N_t / R) of track t; none at all: nothing is launched).  Two launches, one
+// read-back.  Synchronous on return.
+int album_pass_hops(mm_ctx *c, AlbumPass &p, std::vector<double> &e) {
+    e.assign((size_t)p.a.H, 0.0);
+    if (p.a.H == 0) return MM_OK;
     LbArgs lb{};
-    RET(r128_upload_tables(c, sos, channels, lb));
-    const unsigned nblk = blocks_for(a.G, LB_THREADS);
-    RET(lb_prepare(c, nblk, 1, lb));
-    RET(get_buf(c, "r128_lb_error", 4, &lb.error));
-    HIPCHK(c, hipMemsetAsync(lb.error, 0, 4, c->stream));
+    RET(r128_upload_tables(c, p.a.sos, p.channels, lb));
+    RET(lb_prepare(c, p.nblk, 1, lb));
+    lb.error = p.d_error;
+    if (!p.zeroed) HIPCHK(c, hipMemsetAsync(lb.error, 0, 4, c->stream));
+    p.zeroed = false;
     const size_t lds = (size_t)lb_lds_bytes<8, 1>() + (size_t)R128_CHUNK * R128_ROW * sizeof(uint32_t);
-    RET(dispatch_pcm(kind, channels, [&](auto ch, auto t) {
+    RET(dispatch_pcm(p.kind, p.channels, [&](auto ch, auto t) {
         using T = decltype(t);
-        return launch(c, "r128_kweight", r128_kweight_kernel<ch, T>, dim3(nblk), dim3(LB_THREADS), lds, a,
-                      static_cast<const T *>(d_pcm), lb);
+        return launch(c, "r128_album_kweight", r128_album_kweight_kernel<ch, T>, dim3(p.nblk), dim3(LB_THREADS), lds, p.a, lb);
     }));
-    RET(launch(c, "r128_reduce", r128_reduce_kernel, dim3(blocks_for(a.H, 4)), dim3(256), 0, a, d_e));
+    RET(launch(c, "r128_album_reduce", r128_album_reduce_kernel, dim3(blocks_for(p.a.H, 4)), dim3(256), 0, p.a, p.d_e));
     unsigned err = 0;
-    HIPCHK(c, hipMemcpyAsync(e.data(), d_e, (size_t)a.H * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(e.data(), p.d_e, (size_t)p.a.H * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(&err, lb.error, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     resolve_events(c);
@@ -429,8 +455,10 @@ static int r128_device(mm_ctx *c, const void *d_pcm, int kind, int64_t frames, i
     if (!c || !out || !sos || (frames > 0 && !d_pcm)) return set_err(c, MM_ERR_ARG, "bad arguments");
     if (!pcm_kind_ok(kind)) return set_err(c, MM_ERR_ARG, PCM_BAD_KIND, kind);
     if (const char *why = r128_refusal(channels, frames, rate)) return set_err(c, MM_ERR_ARG, "R 128: %s", why);
+    AlbumPass pass;  // (of one track: the context's other results stay as they are)
     std::vector<double> e;
-    RET(r128_hops(c, d_pcm, kind, frames, channels, rate, sos, e));
+    RET(album_pass_prepare(c, &d_pcm, kind, &frames, 1, channels, rate, sos, pass));
+    RET(album_pass_hops(c, pass, e));
     mm_r128_from_hops(e.data(), (int64_t)e.size(), rate, out);
     out->frames = frames;
     out->channels = channels;
@@ -507,8 +535,11 @@ int mm_op_r128_hops(mm_ctx *c, const void *pcm, int kind, int64_t frames, int ch
     HIPCHK(c, hipSetDevice(c->device));
     char *din;
     RET(pcm_upload(c, "r128_in", pcm, pcm_bytes(kind, frames, channels), &din));
+    const void *d_pcm = din;
+    AlbumPass pass;
     std::vector<double> e;
-    RET(r128_hops(c, din, kind, frames, channels, rate, sos, e));
+    RET(album_pass_prepare(c, &d_pcm, kind, &frames, 1, channels, rate, sos, pass));
+    RET(album_pass_hops(c, pass, e));
     for (size_t i = 0; i < std::min(e.size(), (size_t)cap); ++i) hops_host[i] = e[i];
     return (int)std::min<size_t>(e.size(), (size_t)INT32_MAX);
 }

@@ -12,8 +12,8 @@
 // instruction), the host restatement in int64; the results are the same
 // integers, so nothing depends on the launch geometry.
 //
-// One kernel body (resample_span; resample_kernel runs it on the one signal of a call, and
-// tracks.hip's resample_tracks_kernel on every track of a batch in one launch).  A workgroup
+// One kernel (resample_tracks_kernel runs the body resample_span on the spans of every track
+// of a call in one launch; a single signal is a call of one track).  A workgroup
 // owns RS_SPAN consecutive output frames and stages the input
 // frames they read in LDS: a line of int16 for mono, and for stereo one dword a frame
 // (left in the low half).  Two de-interleaved int16 lines, as the meter stages its lines,
@@ -26,9 +26,9 @@
 // the taps is kept transposed and in output order, D[k][n mod L] = c[(n mod L) * M % L][k],
 // so the lanes of a wave (consecutive n) read consecutive words of one row of D.
 //
-// Included last in mastering.hip, after pcm16.h (its frames and wave reductions are shared
-// with the meter and the ceiling, not their line layout), meter.hip, ceiling.hip and the
-// WAV helpers.  mm_master / mm_deliver and mm_master_wav / mm_deliver_wav are here, one
+// Included in mastering.hip after pcm16.h (its frames and wave reductions are shared
+// with the meter and the ceiling, not their line layout), meter.hip, ceiling.hip, level.hip
+// (a delivery's refusals) and the WAV helpers.  mm_master / mm_deliver and mm_master_wav / mm_deliver_wav are here, one
 // implementation each with the delivery optional.
 
 namespace mm {
@@ -66,8 +66,7 @@ struct RsArgs {
 // the item's first output's samples (always in range) and is not stored.
 //
 // resample_span is that workgroup: one span of one signal, `n0` its first output frame and
-// every position relative to the signal's own start.  resample_kernel runs it on the one
-// signal of a call; resample_tracks_kernel (tracks.hip) on the span of a track of a batch.
+// every position relative to the signal's own start.
 template <int CH, typename T>
 __device__ __forceinline__ void resample_span(const T *__restrict__ in, T *__restrict__ out, RsArgs a, int64_t n0) {
     // mono: int16 samples; stereo: one dword a frame, left in the low half
@@ -189,9 +188,25 @@ __device__ __forceinline__ void resample_span(const T *__restrict__ in, T *__res
     }
 }
 
+static_assert(TRACKS_RS_SPAN == RS_SPAN, "tracks.h restates the span");
+
+struct RsTrack {  // one a track, uploaded once a call
+    const void *in;
+    void *out;
+    int64_t N, Nout;  // the track's own input and output frames
+};
+
+// One launch over the RS_SPAN spans of output frames of all tracks (tracks.h).  a.N, a.Nout and
+// a.st are the launch's: st[n], and every workgroup takes N and Nout from its track
 template <int CH, typename T>
-__global__ void __launch_bounds__(RS_THREADS) resample_kernel(const T *__restrict__ in, T *__restrict__ out, RsArgs a) {
-    resample_span<CH, T>(in, out, a, (int64_t)blockIdx.x * RS_SPAN);
+__global__ void __launch_bounds__(RS_THREADS) resample_tracks_kernel(const RsTrack *tr, const uint32_t *first, int n, RsArgs a) {
+    const int t = tracks_find(first, n, blockIdx.x);
+    const RsTrack k = tr[t];
+    a.N = k.N;
+    a.Nout = k.Nout;
+    a.st += t;
+    resample_span<CH, T>(static_cast<const T *>(k.in), static_cast<T *>(k.out), a,
+                         (int64_t)(blockIdx.x - first[t]) * RS_SPAN);
 }
 
 }  // namespace mm
@@ -289,39 +304,83 @@ static int resample_taps_device(mm_ctx *c, const mm_resampler *rs, const int32_t
     return MM_OK;
 }
 
-// Convert a device-resident signal into d_out (synchronous on return).
+// Refuses what is not a batch to convert (MM_ERR_ARG, the sentence names the track), before
+// anything is queued.  The table itself is checked where it is uploaded (resample_taps_device),
+// which queues nothing before it has refused.
+static int batch_resample_check(mm_ctx *c, const void *const *in, int kind, const int64_t *frames, int n, int channels,
+                                const mm_resampler *rs, void *const *out_pcm, const mm_resample *out) {
+    if (n < 1 || n > MM_ALBUM_TRACKS) return set_err(c, MM_ERR_ARG, "batch: %d tracks out of range [1, %d]", n, MM_ALBUM_TRACKS);
+    if (!in || !frames || !rs || !out_pcm || !out) return set_err(c, MM_ERR_ARG, "bad arguments");
+    if (!pcm_kind_ok(kind)) return set_err(c, MM_ERR_ARG, PCM_BAD_KIND, kind);
+    if (const char *why = resample_bad_geometry(rs->L, rs->M, rs->K)) return set_err(c, MM_ERR_ARG, "resampler: %s", why);
+    int64_t total_in = 0, total_out = 0;
+    for (int t = 0; t < n; ++t) {
+        if (const char *why = resample_bad_signal(frames[t], channels, rs->L, rs->M))
+            return set_err(c, MM_ERR_ARG, "batch: track %d: %s", t, why);
+        if (frames[t] > 0 && (!in[t] || !out_pcm[t])) return set_err(c, MM_ERR_ARG, "batch: track %d: null pointer", t);
+        total_in += frames[t];
+        total_out += rs_frames(frames[t], rs->L, rs->M);
+        if (total_in >= R128_MAX_FRAMES || total_out >= R128_MAX_FRAMES)
+            return set_err(c, MM_ERR_ARG, "batch: track %d: 2^31 frames or more in all", t);
+    }
+    return MM_OK;
+}
+
+// Convert n device-resident tracks, track t from d_in[t] into d_out[t] (synchronous on return):
+// one upload (the track table and, behind it, the n result blocks as zeros), one launch over the
+// spans of all tracks, one read-back.  Arguments already checked, D the device copy of the taps
+// (resample_taps_device).  The host table lives until the synchronisation at the end.
+static int batch_resample_device(mm_ctx *c, const void *const *d_in, int kind, const int64_t *frames, int n, int channels,
+                                 const mm_resampler *rs, const int32_t *D, void *const *d_out, mm_resample *out) {
+    RsArgs a{};
+    a.D = D;
+    const size_t N = (size_t)n, tb = N * sizeof(RsTrack), o_st = (tb + (N + 1) * sizeof(uint32_t) + 7) & ~(size_t)7;
+    std::vector<char> tab(o_st + N * sizeof(RsDev));  // the tracks, the grid's prefix sums, the zeroed results
+    RsTrack *tr = reinterpret_cast<RsTrack *>(tab.data());
+    uint32_t *first = reinterpret_cast<uint32_t *>(tab.data() + tb);
+    std::vector<int64_t> wgs(N);
+    for (int t = 0; t < n; ++t) {
+        resample_clear(&out[t], frames[t], channels, rs);
+        tr[t] = RsTrack{d_in[t], d_out[t], frames[t], out[t].frames_out};
+        wgs[(size_t)t] = tracks_resample_spans(out[t].frames_out);
+    }
+    const uint32_t grid = tracks_prefix(wgs.data(), n, first);
+    if (grid == 0) return MM_OK;  // no track has frames
+    char *d_tab;
+    RET(get_buf(c, "rs_tracks", tab.size(), &d_tab));
+    HIPCHK(c, hipMemcpyAsync(d_tab, tab.data(), tab.size(), hipMemcpyHostToDevice, c->stream));
+    a.st = reinterpret_cast<RsDev *>(d_tab + o_st);
+    a.L = rs->L;
+    a.M = rs->M;
+    a.K = rs->K;
+    a.sub = resample_sub(rs);
+    RET(dispatch_pcm(kind, channels, [&](auto ch, auto t) {
+        using T = decltype(t);
+        return launch(c, "resample_tracks", resample_tracks_kernel<ch, T>, dim3(grid), dim3(RS_THREADS), 0,
+                      reinterpret_cast<const RsTrack *>(d_tab), reinterpret_cast<const uint32_t *>(d_tab + tb), n, a);
+    }));
+    std::vector<RsDev> h(N);
+    HIPCHK(c, hipMemcpyAsync(h.data(), a.st, N * sizeof(RsDev), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int t = 0; t < n; ++t)
+        for (int ch = 0; ch < channels; ++ch) {
+            out[t].clipped[ch] = (int64_t)h[(size_t)t].clipped[ch];
+            out[t].peak[ch] = h[(size_t)t].peak[ch];
+        }
+    resolve_events(c);
+    return MM_OK;
+}
+
+// Convert a device-resident signal into d_out (synchronous on return): a batch of one track.
 static int resample_device(mm_ctx *c, const void *d_in, int kind, int64_t frames, int channels, const mm_resampler *rs,
                            void *d_out, mm_resample *out) {
     if (!c || !out || !rs || (frames > 0 && (!d_in || !d_out))) return set_err(c, MM_ERR_ARG, "bad arguments");
     if (!pcm_kind_ok(kind)) return set_err(c, MM_ERR_ARG, PCM_BAD_KIND, kind);
     if (const char *why = resample_bad_geometry(rs->L, rs->M, rs->K)) return set_err(c, MM_ERR_ARG, "resampler: %s", why);
     if (const char *why = resample_bad_signal(frames, channels, rs->L, rs->M)) return set_err(c, MM_ERR_ARG, "%s", why);
-    RsArgs a{};
-    RET(resample_taps_device(c, rs, &a.D));
-    resample_clear(out, frames, channels, rs);
-    if (out->frames_out == 0) return MM_OK;
-    RET(get_buf(c, "rs_res", 1, &a.st));
-    HIPCHK(c, hipMemsetAsync(a.st, 0, sizeof(RsDev), c->stream));
-    a.N = frames;
-    a.Nout = out->frames_out;
-    a.L = rs->L;
-    a.M = rs->M;
-    a.K = rs->K;
-    a.sub = resample_sub(rs);
-    const dim3 grid((unsigned)tracks_resample_spans(a.Nout)), block(RS_THREADS);
-    RET(dispatch_pcm(kind, channels, [&](auto ch, auto t) {
-        using T = decltype(t);
-        return launch(c, "resample", resample_kernel<ch, T>, grid, block, 0, static_cast<const T *>(d_in), static_cast<T *>(d_out), a);
-    }));
-    RsDev h;
-    HIPCHK(c, hipMemcpyAsync(&h, a.st, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int ch = 0; ch < channels; ++ch) {
-        out->clipped[ch] = (int64_t)h.clipped[ch];
-        out->peak[ch] = h.peak[ch];
-    }
-    resolve_events(c);
-    return MM_OK;
+    const int32_t *D;
+    RET(resample_taps_device(c, rs, &D));
+    return batch_resample_device(c, &d_in, kind, &frames, 1, channels, rs, D, &d_out, out);
 }
 
 // why (job, delivery) is refused, or null
@@ -443,6 +502,32 @@ int mm_resample_pcm(mm_ctx *c, const void *in, int kind, int64_t frames, int cha
     RET(get_buf(c, "rs_out", std::max<size_t>(out_bytes, 1), &dout));
     RET(resample_device(c, din, kind, frames, channels, rs, dout, out));
     return pcm_download(c, out_pcm, dout, out_bytes);
+}
+
+int mm_batch_resample_device(mm_ctx *c, const void *const *d_in, int kind, const int64_t *frames, int n, int channels,
+                             const mm_resampler *rs, void *const *d_out, mm_resample *out) {
+    if (!c) return MM_ERR_ARG;
+    RET(batch_resample_check(c, d_in, kind, frames, n, channels, rs, d_out, out));
+    HIPCHK(c, hipSetDevice(c->device));
+    const int32_t *D;
+    RET(resample_taps_device(c, rs, &D));
+    return batch_resample_device(c, d_in, kind, frames, n, channels, rs, D, d_out, out);
+}
+
+int mm_batch_resample_pcm(mm_ctx *c, const void *const *in, int kind, const int64_t *frames, int n, int channels,
+                          const mm_resampler *rs, void *const *out_pcm, mm_resample *out) {
+    if (!c) return MM_ERR_ARG;
+    RET(batch_resample_check(c, in, kind, frames, n, channels, rs, out_pcm, out));
+    HIPCHK(c, hipSetDevice(c->device));
+    const int32_t *D;
+    RET(resample_taps_device(c, rs, &D));  // (a table it refuses: before a track is uploaded)
+    std::vector<int64_t> frames_out((size_t)n);
+    for (int t = 0; t < n; ++t) frames_out[(size_t)t] = rs_frames(frames[t], rs->L, rs->M);
+    std::vector<void *> din, dout;
+    RET(album_upload(c, "batch_rs_in", in, kind, frames, n, channels, din));
+    RET(album_upload(c, "batch_rs_out", nullptr, kind, frames_out.data(), n, channels, dout));  // (laid out, nothing copied)
+    RET(batch_resample_device(c, din.data(), kind, frames, n, channels, rs, D, dout.data(), out));
+    return batch_download(c, out_pcm, dout, kind, frames_out.data(), n, channels, nullptr);
 }
 
 // The definition restated in plain C++ on the host (no context, no GPU): what the kernel

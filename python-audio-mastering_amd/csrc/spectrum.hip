@@ -6,7 +6,7 @@
 // mm_spectrum_pcm on what it delivered.  The bins end in mm_spectrum_from_bins, the one tail
 // of the host restatement (mm_spectrum_host: its own radix-2 FFT in double) and the GPU path.
 //
-// The GPU path is two launches on the context's stream, with no atomic.  spec_frames: a
+// The GPU path is two launches on the context's stream, with no atomic.  spec_tracks: a
 // workgroup of 256 threads owns a group of G consecutive frames of one track (spectrum.h) and
 // runs, a frame, ONE complex 8192-point FFT on z = w * (L + iR) with 32 points a thread:
 //   n = 256 a + t, k = k1 + 32 (p + 16 q), t = 16 b + c
@@ -29,9 +29,8 @@
 // spec_fold: one thread a (track, bin, column) sums the track's records in group order and
 // divides by F (no frame: NaN); stream order gives it the records.
 //
-// Included at the end of mastering.hip after qc.hip and before tracks.hip, whose
-// finish_delivered runs the report beside the other three and which holds the launch over
-// many tracks (spec_tracks_kernel).
+// The frames launch lies over the groups of all tracks of a call (tracks.h's prefix sums): a
+// single signal is a call of one track.  Included at the end of mastering.hip after qc.hip.
 
 #include "spectrum.h"
 
@@ -277,11 +276,13 @@ __device__ __forceinline__ void spec_frames_group(const T *__restrict__ in, int6
     }
 }
 
-// one signal: workgroup g is its group g
+// spec_frames_group over the groups of all tracks: a record lands among its track's own, and
+// every frame index is the track's
 template <int CH, typename T>
-__global__ void __launch_bounds__(SPEC_THREADS) spec_kernel(SpecLaunch L) {
-    const SpecTrack tr = L.tr[0];
-    spec_frames_group<CH, T>(static_cast<const T *>(tr.pcm), tr.F, (int64_t)blockIdx.x, L.tab,
+__global__ void __launch_bounds__(SPEC_THREADS) spec_tracks_kernel(SpecLaunch L) {
+    const int t = tracks_find(L.first, L.n, blockIdx.x);
+    const SpecTrack tr = L.tr[t];
+    spec_frames_group<CH, T>(static_cast<const T *>(tr.pcm), tr.F, (int64_t)(blockIdx.x - L.first[t]), L.tab,
                              L.rec + (size_t)blockIdx.x * SPEC_REC);
 }
 
@@ -383,12 +384,10 @@ int spec_tables(mm_ctx *c, SpecTables *tab) {
 }
 
 // The reports of n checked device-resident tracks into out[n], their bin tables into bins[n]
-// (synchronous on return): one upload of the track table, the frames launch `groups(L, grid)`
-// (one track: spec_kernel; many: tracks.hip's spec_tracks_kernel), the fold launch and one
-// read-back, then the tail.  The host tables live until the synchronisation.
-template <typename Groups>
-int spectrum_run(mm_ctx *c, const void *const *d_pcm, const int64_t *frames, int n, int channels, int rate, mm_spectrum *out,
-                 std::vector<std::vector<double>> &bins, Groups &&groups) {
+// (synchronous on return): one upload of the track table, the frames launch, the fold launch
+// and one read-back, then the tail.  The host tables live until the synchronisation.
+int spectrum_run(mm_ctx *c, const void *const *d_pcm, int kind, const int64_t *frames, int n, int channels, int rate,
+                 mm_spectrum *out, std::vector<std::vector<double>> &bins) {
     const size_t N = (size_t)n;
     std::vector<SpecTrack> tr(N);
     std::vector<int64_t> wgs(N);
@@ -413,7 +412,11 @@ int spectrum_run(mm_ctx *c, const void *const *d_pcm, const int64_t *frames, int
     L.first = reinterpret_cast<const uint32_t *>(d_tab + N * sizeof(SpecTrack));
     L.n = n;
     HIPCHK(c, hipMemcpyAsync(d_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
-    if (grid) RET(groups(L, grid));
+    if (grid)
+        RET(dispatch_pcm(kind, channels, [&](auto ch, auto t) {
+            using T = decltype(t);
+            return launch(c, "spec_tracks", spec_tracks_kernel<ch, T>, dim3(grid), dim3(SPEC_THREADS), 0, L);
+        }));
     RET(launch(c, "spec_fold", spec_fold_kernel, dim3(blocks_for(SPEC_REC, SPEC_THREADS), (unsigned)n), dim3(SPEC_THREADS), 0, L));
     HIPCHK(c, hipMemcpyAsync(back.data(), L.out, N * SPEC_REC * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -435,21 +438,35 @@ void spectrum_clear(mm_spectrum *o, int channels) {
     o->total_ms[0] = o->total_ms[1] = NAN;
 }
 
+// Refuses what is not a batch to take the spectra of, as batch_qc_check does.
+int batch_spectrum_check(mm_ctx *c, const void *const *pcm, int kind, const int64_t *frames, int n, int channels, int rate,
+                         const mm_spectrum *out) {
+    return batch_check(c, pcm, kind, frames, n, channels, out != nullptr,
+                       [&](int t) { return spectrum_refusal(channels, frames[t], rate); });
+}
+
+// The spectrum reports of n checked device-resident tracks (synchronous on return).  Only
+// c->spectra and the bin tables are set: the other results of the context's last call stay.
+int batch_spectrum_device(mm_ctx *c, const void *const *d_pcm, int kind, const int64_t *frames, int n, int channels, int rate,
+                          mm_spectrum *out) {
+    std::vector<std::vector<double>> bins;
+    RET(spectrum_run(c, d_pcm, kind, frames, n, channels, rate, out, bins));
+    c->spectra.assign(out, out + n);
+    c->spectrum_bins.swap(bins);
+    return MM_OK;
+}
+
 }  // namespace
 
-// The spectrum report of a device-resident signal (synchronous on return); the bin table into *bins.
+// The spectrum report of a device-resident signal (synchronous on return), a call of one track
+// that leaves the context's results as they are; the bin table into *bins.
 static int spectrum_device(mm_ctx *c, const void *d_pcm, int kind, int64_t frames, int channels, int rate, mm_spectrum *out,
                            std::vector<double> *bins) {
     if (!c || !out || (frames > 0 && !d_pcm)) return set_err(c, MM_ERR_ARG, "bad arguments");
     if (!pcm_kind_ok(kind)) return set_err(c, MM_ERR_ARG, PCM_BAD_KIND, kind);
     if (const char *why = spectrum_refusal(channels, frames, rate)) return set_err(c, MM_ERR_ARG, "spectrum: %s", why);
     std::vector<std::vector<double>> all;
-    RET(spectrum_run(c, &d_pcm, &frames, 1, channels, rate, out, all, [&](const SpecLaunch &L, uint32_t grid) {
-        return dispatch_pcm(kind, channels, [&](auto ch, auto t) {
-            using T = decltype(t);
-            return launch(c, "spec_frames", spec_kernel<ch, T>, dim3(grid), dim3(SPEC_THREADS), 0, L);
-        });
-    }));
+    RET(spectrum_run(c, &d_pcm, kind, &frames, 1, channels, rate, out, all));
     if (bins) bins->swap(all[0]);
     return MM_OK;
 }
@@ -562,6 +579,24 @@ int mm_spectrum_pcm(mm_ctx *c, const void *pcm, int kind, int64_t frames, int ch
     RET(spectrum_device(c, din, kind, frames, channels, rate, out, &bins));
     spectrum_outputs(bins, frames, channels, rate, out, bands, bins_out);
     return MM_OK;
+}
+
+int mm_batch_spectrum_device(mm_ctx *c, const void *const *d_pcm, int kind, const int64_t *frames, int n, int channels,
+                             int32_t rate, mm_spectrum *out) {
+    if (!c) return MM_ERR_ARG;
+    RET(batch_spectrum_check(c, d_pcm, kind, frames, n, channels, rate, out));
+    HIPCHK(c, hipSetDevice(c->device));
+    return batch_spectrum_device(c, d_pcm, kind, frames, n, channels, rate, out);
+}
+
+int mm_batch_spectrum_pcm(mm_ctx *c, const void *const *pcm, int kind, const int64_t *frames, int n, int channels,
+                          int32_t rate, mm_spectrum *out) {
+    if (!c) return MM_ERR_ARG;
+    RET(batch_spectrum_check(c, pcm, kind, frames, n, channels, rate, out));
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<void *> d;
+    RET(album_upload(c, "batch_spec_in", pcm, kind, frames, n, channels, d));
+    return batch_spectrum_device(c, d.data(), kind, frames, n, channels, rate, out);
 }
 
 int mm_last_spectrum(mm_ctx *c, int cap, mm_spectrum *out) {

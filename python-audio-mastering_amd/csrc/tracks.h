@@ -1,4 +1,5 @@
-// tracks.h — the layout of a launch over n tracks (tracks.hip): every track owns a run of
+// tracks.h — the layout of a launch over n tracks (the ceiling, the converter, the QC and
+// spectrum reports and the level's gain, each in its own file): every track owns a run of
 // consecutive workgroups, one a span of its frames, and a workgroup finds its track by a
 // search over the prefix sums of those runs.  Plain integer arithmetic, host and device
 // alike, with no other header of the library: the tables the host uploads, the kernels and
@@ -12,8 +13,8 @@
 // (tracks_resample_spans of ceil(frames * L / M)).  The need grid's prefix sums also place
 // the planes: track t's r - 1 plane holds whole spans at first_need[t] * TRACKS_METER_SPAN of
 // one buffer of first_need[n] * TRACKS_METER_SPAN entries, so planes neither overlap nor
-// leave their spans' 16-byte alignment.  A single-track launch (ceiling.hip, meter.hip,
-// resample.hip) is the case n = 1 and counts its spans and its plane with the same functions.
+// leave their spans' 16-byte alignment.  A single signal is the case n = 1 of the same launch
+// (the search then reads no table); meter.hip counts its spans with the same functions.
 #pragma once
 
 #include <stdint.h>

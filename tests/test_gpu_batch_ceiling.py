@@ -1,4 +1,4 @@
-"""The segmented true-peak ceiling on the GPU (csrc/tracks.hip: the need, apply, peak and trim
+"""The segmented true-peak ceiling on the GPU (csrc/ceiling.hip: the need, apply, peak and trim
 launches over all tracks of a batch, every track with its own ceiling) against the host
 restatement mm_ceiling_host run on every track alone: equal samples, every mm_ceiling field
 equal.  The shapes are the smallest at which a halo, a plane mask, a span count or the

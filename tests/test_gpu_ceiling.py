@@ -133,19 +133,27 @@ def test_branch_under_the_ceiling_writes_nothing(branches):
         assert raw.tobytes() == before.tobytes()
         assert st == ref_ceiling(pcm, q28(-1.0), 220)[1]
         assert st["limited_frames"] == 0 and st["trim_q16"] == ONE and st["tp_out_q28"] == st["tp_in_q28"]
-        assert "ceil_need" in stats and "ceil_apply" in stats and "ceil_trim" not in stats
+        # one call: need, apply and the peak pass (which skips the untouched track) once each
+        assert stats["ceil_tracks_need"][1] == stats["ceil_tracks_apply"][1] == stats["ceil_tracks_peak"][1] == 1
+        assert "ceil_tracks_trim" not in stats and "meter_i16" not in stats
 
 
 @pytest.mark.parametrize("W", [1, 16, 220, 1024])
 def test_branch_limited_without_a_trim(branches, W):
     (want, st), stats = timed(lambda: check(branches["limited"], q28(-1.0), W))
-    assert st["trim_q16"] == ONE and st["limited_frames"] > 0 and "ceil_trim" not in stats
+    assert st["trim_q16"] == ONE and st["limited_frames"] > 0 and "ceil_tracks_trim" not in stats
+    # two calls (int16 and f32), each one need, one apply and one peak pass
+    assert stats["ceil_tracks_need"][1] == stats["ceil_tracks_apply"][1] == stats["ceil_tracks_peak"][1] == 2
+    assert "meter_i16" not in stats
 
 
 @pytest.mark.parametrize("W", [1, 16, 220])
 def test_branch_trimmed(branches, W):
     (want, st), stats = timed(lambda: check(branches["trimmed"], q28(-1.0), W))
-    assert (st["trim_q16"] != ONE) == (W != 220) == ("ceil_trim" in stats)
+    assert (st["trim_q16"] != ONE) == (W != 220) == ("ceil_tracks_trim" in stats)
+    # two calls (int16 and f32): the peak pass twice a call only with a trim
+    assert stats["ceil_tracks_need"][1] == stats["ceil_tracks_apply"][1] == 2 and "meter_i16" not in stats
+    assert stats["ceil_tracks_peak"][1] == (4 if W != 220 else 2) and stats.get("ceil_tracks_trim", (0, 0))[1] == (2 if W != 220 else 0)
     assert st["tp_out_q28"] <= q28(-1.0) < st["tp_in_q28"]
 
 
@@ -198,7 +206,8 @@ def test_chain_ceiling_is_the_reference_on_the_plain_output(smoke_runs, name, db
     assert info["ceiling"]["ceiling_dbtp"] == 20 * np.log10(q28(db) / 2 ** 28)
     assert info["ceiling"]["trimmed"] == (st["trim_q16"] != ONE)
     assert info["loudness"] == info0["loudness"] and info["gain_linear"] == info0["gain_linear"]
-    assert "ceil_need" in stats and "ceil_apply" in stats
+    assert stats["ceil_tracks_need"][1] == stats["ceil_tracks_apply"][1] == 1
+    assert ("meter_i16" in stats) == (name == "both")  # the meter's kernel runs for the report alone
     assert set(info) - {"ceiling", "report"} == set(info0)
     if name == "deep":  # whatever the smoke output's own peak, this one is limited
         assert st["limited_frames"] > 0 and st["tp_in_q28"] > q28(db) >= st["tp_out_q28"]

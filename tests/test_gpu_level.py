@@ -245,7 +245,7 @@ def test_without_the_key_nothing_changes(track):
         ctx.kernel_stats()
         a, ia = engine.master_pcm(track, RATE, params)
         names = set(ctx.kernel_stats())
-        assert "ceil_need" in names and "r128_kweight" in names and "level_tracks_gain" not in names
+        assert "ceil_tracks_need" in names and "r128_album_kweight" in names and "level_tracks_gain" not in names
         with pytest.raises(RuntimeError, match="no loudness target"):
             engine.levels(ctx)
         b, ib = engine.master_pcm(track, RATE, dict(params, deliver_lufs=None))

@@ -1,4 +1,4 @@
-"""The delivery QC report on the GPU (csrc/qc.hip, csrc/tracks.hip): the span kernel, its
+"""The delivery QC report on the GPU (csrc/qc.hip): the span kernel, its
 records and the fold against the sequential host restatement mm_qc_host, every field of mm_qc
 and the whole hop table, at the places where the run operator and the hop pieces can go wrong
 (runs that end on, start on, cross and cover spans; silence at either end and across seams;

@@ -245,7 +245,7 @@ def test_chain_is_the_composition(chain, kind):
     assert info["rate"] == 44100 and info["frames"] == len(chain["want"]) == rst["frames_out"]
     assert set(info) - {"resample", "rate", "ceiling", "report"} == set(chain["info0"])
     assert info["loudness"] == chain["info0"]["loudness"] and info["gain_linear"] == chain["info0"]["gain_linear"]
-    assert "resample" in stats and "resample" not in chain["stats0"]
+    assert stats["resample_tracks"][1] == 1 and "resample_tracks" not in chain["stats0"]
 
 
 def test_chain_without_a_ceiling_or_report(chain):

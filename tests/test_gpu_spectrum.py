@@ -1,4 +1,4 @@
-"""The spectrum report on the GPU (csrc/spectrum.hip, csrc/tracks.hip): the frames kernel (one
+"""The spectrum report on the GPU (csrc/spectrum.hip): the frames kernel (one
 complex 8192-point FFT a frame in registers and LDS, float64 accumulators), its records and the
 fold against the host restatement mm_spectrum_host, within the tolerance derived below, at the
 lengths where the groups of frames can go wrong, for both buffer kinds, mono and stereo, on

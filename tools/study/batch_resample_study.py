@@ -77,7 +77,7 @@ if mode == "single":
     call = lambda: single_call(d.data_ptr(), len(x), o.data_ptr(), m)  # noqa: E731
     timed(call, 3)
     wall = timed(call, 15)
-    ks = [kernel_ms(call, "resample")[0] for _ in range(10)]
+    ks = [kernel_ms(call, "resample_tracks")[0] for _ in range(10)]
     print(json.dumps(dict(mode=mode, pkg=pkg, sha=native.library_sha(), wall_ms=med(wall), kernel_ms=med(ks),
                           checksum=int(o.to(torch.int64).sum().item()))))
 
@@ -110,7 +110,7 @@ elif mode in ("a", "b"):
         rounds["batch_wall"] += timed(batch, 1)
         rounds["singles_wall"] += timed(singles, 1)
         rounds["batch_kernel"].append(kernel_ms(batch, "resample_tracks")[0])
-        rounds["singles_kernel"].append(kernel_ms(singles, "resample")[0])
+        rounds["singles_kernel"].append(kernel_ms(singles, "resample_tracks")[0])
     print(json.dumps(dict(mode=mode, n=n, seconds=seconds, byte_equal=True, **{k: med(v) for k, v in rounds.items()})))
 
 elif mode == "c":
